@@ -488,7 +488,7 @@ def test_bench_two_ranks_product_flow():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--no-secondary", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True,
+                        "--full", "--no-secondary", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -544,8 +544,8 @@ def test_bench_line_carries_issue_figures():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "GNF_DIST_BACKEND", "GNF_FORCE_DIST"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-secondary",
-                        "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full",
+                        "--no-secondary", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["scaling"] == "weak" and out["config"]["global_batch"] == 100
@@ -595,8 +595,8 @@ def test_bench_rccl_branch_at_world_size_one():
     env = dict(os.environ, GNF_FORCE_DIST="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "GNF_DIST_BACKEND"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-secondary",
-                        "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full",
+                        "--no-secondary", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -606,6 +606,44 @@ def test_bench_rccl_branch_at_world_size_one():
     assert out["allreduce_ms_per_step"] is not None and 0 < out["allreduce_ms_per_step"] < 50
     assert len(out["ms_per_step_per_rank"]) == 1
     assert out["rccl_world_size"] == 1 and len(out["rank_devices"]) == 1 and "name=" in out["rank_devices"][0]
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline and none of the figures --full adds; `--dump-outputs DIR`
+    writes what the last timed step computed: the loss, and per trainable parameter its value after the step and the
+    step's gradient, float32, named after the flow's parameters, well under 64 MB."""
+    import json
+    import subprocess
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "GNF_DIST_BACKEND", "GNF_FORCE_DIST"):
+        env.pop(k, None)
+    dump = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--dump-outputs",
+                        str(dump)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["unit"] == "samples/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32" and abs(out["value"] - 100 * 2 / (out["ms_per_step"] * 2e-3)) < 1e-6 * out["value"]
+    for k in ("roofline", "roofline_other", "ops_ms", "secondary", "measured_peaks", "cpu_baseline"):
+        assert k not in out, k
+    flow = _bench().build_flow()                          # the seeded initial parameters
+    params = [(n, p) for n, p in flow.named_parameters() if p.requires_grad]
+    assert sorted(os.listdir(dump)) == sorted(["loss.npy"] + ["%s.%s.npy" % (kind, n) for n, _ in params
+                                                              for kind in ("param", "grad")])
+    loss = np.load(dump / "loss.npy")
+    assert loss.dtype == np.float32 and loss.shape == (1,) and np.isfinite(loss).all()
+    total, moved = loss.nbytes, 0
+    for n, p in params:
+        for kind in ("param", "grad"):
+            a = np.load(dump / ("%s.%s.npy" % (kind, n)))
+            assert a.dtype == np.float32 and a.shape == tuple(p.shape) and np.isfinite(a).all(), (kind, n)
+            total += a.nbytes
+        moved += not np.array_equal(np.load(dump / ("param.%s.npy" % n)), p.detach().numpy())
+    assert total < 64 << 20
+    assert moved == len(params), "%d of %d parameters unchanged by three Adam steps" % (len(params) - moved, len(params))
 
 
 def test_train_uci_two_ranks_dual_updates_stay_in_lockstep(tmp_path):

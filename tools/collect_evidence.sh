@@ -3,8 +3,8 @@
 # copy what is kept to profiles/)
 tag=${1:-r06}; out=gpurun_out; mkdir -p $out
 export TMPDIR=/tmp
-python bench.py --steps 20 --warmup 3 2> $out/${tag}_bench.err | tail -1 > $out/${tag}_bench.json
-( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/${tag}_kt -o p -- python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline > /dev/null 2>&1 )
+python bench.py --full --steps 20 --warmup 3 2> $out/${tag}_bench.err | tail -1 > $out/${tag}_bench.json
+( cd "$TMPDIR" && rocprofv3 --kernel-trace --stats --output-format csv -d "$TMPDIR/${tag}_kt" -o p -- python3 "$OLDPWD/bench.py" --full --steps 20 --warmup 3 --no-cpu-baseline > /dev/null 2>&1 )
 cp $(find /tmp/${tag}_kt -name "*kernel_stats.csv" | head -1) $out/${tag}_bench_kernel_stats.csv
 # the conv pair: the PMC-derived inputs bench.py reads (incl. the Monotonic kernels), the full counter set, the per-phase cycle account
 python tools/make_bench_inputs.py $out/${tag}_bench_inputs.json > /dev/null 2>&1
