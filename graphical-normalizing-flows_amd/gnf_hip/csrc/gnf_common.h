@@ -12,6 +12,101 @@
     if (e__ != hipSuccess) return (int)e__;        \
   } while (0)
 
+// Launch `kernel` with `lds` bytes of dynamic LDS: raises the kernel's dynamic-LDS limit to that size (above the 64 KB
+// default a launch fails without it; set on every call), launches, returns the launch status.
+template <typename... P, typename... A>
+static inline hipError_t gnf_launch_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s,
+                                        const A&... args) {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Device support shared by every translation unit: vector types, buffer descriptors, MFMA wrappers, the bf16 split.
+// All at global scope like the rest of this header; the units keep their kernels in their own (anonymous) namespaces.
+// ---------------------------------------------------------------------------------------------------------------------
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+// the same with dword alignment: a dwordx2 / dwordx4 at ANY dword address (rows of K = 630 floats).  Never interchangeable
+// with the 16-byte aligned types above.
+typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
+typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+
+typedef __amdgpu_buffer_rsrc_t rsrc_t;
+// raw buffer descriptor over [base, base + bytes): loads past the end return zeros, stores past it are dropped
+__device__ __forceinline__ rsrc_t make_rsrc(const void* base, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);   // word 3: DATA_FORMAT = 32 bit
+}
+
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+// v_mfma_f32_16x16x4_f32
+__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+// v_mfma_f32_16x16x32_bf16 on operands held as four packed bf16 pairs
+__device__ __forceinline__ f32x4 mfma_bf16(const u32x4& a, const u32x4& b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+// max(x, 0) as ONE v_max_f32: fmaxf() is compiled into a canonicalising v_max(x, x) plus the maximum (NaN quieting the
+// kernels do not need: a NaN pre-activation stays a NaN either way)
+__device__ __forceinline__ float relu1(float x) { float y; asm("v_max_f32 %0, 0, %1" : "=v"(y) : "v"(x)); return y; }
+// Values the compiler must not recognise as loop-invariant: everything derived from them (fragment offsets, the small
+// vectors w1x / wL / b_l in LDS) would otherwise be hoisted out of the node loop and held in registers -- 80 VGPRs of
+// hoisted LDS reads and 200 SGPR offsets in the first build of mono_bwd_wide_k, spilled in turn.
+__device__ __forceinline__ int opaque_v(int x) { asm volatile("" : "+v"(x)); return x; }
+__device__ __forceinline__ int opaque_s(int x) { asm volatile("" : "+s"(x)); return x; }
+
+// Exact 3 x bf16 split x = hi + mid + lo (hi = rne_bf16(x), mid = rne_bf16(x - hi), lo = x - hi - mid; the method:
+// gnf_gemm_split.hip).  cvt_pk_bf16: packed pair of RNE bf16, lo half = bf16(a), hi half = bf16(b).
+// (v_cvt_pk_bf16_f32 through the conversion builtin, NOT inline asm: the results feed MFMAs a few instructions later, and the
+// compiler's hazard recognizer inserts the VALU-write -> MFMA-read wait states only for instructions it can see.  With the asm
+// form mono_fwd_x_k<split> read stale operands: errors of 1e-2 .. 1 that moved with every rebuild)
+__device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));
+}
+// x0, x1 -> packed (hi, mid, lo) pairs; the two remainders of a level as ONE packed subtraction (v_pk_add_f32): 9 VALU
+// instructions per two elements.  The subtractions are exact (Sterbenz-like: hi is x rounded to 8 significant bits, so
+// x - hi has at most 16, and x - hi - mid at most 8)
+__device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
+  h = cvt_pk_bf16(x0, x1);
+  const f32x2 r = f32x2{x0, x1} - f32x2{__uint_as_float(h << 16), __uint_as_float(h & 0xffff0000u)};   // exact
+  m = cvt_pk_bf16(r[0], r[1]);
+  const f32x2 q = r - f32x2{__uint_as_float(m << 16), __uint_as_float(m & 0xffff0000u)};                // exact
+  l = cvt_pk_bf16(q[0], q[1]);
+}
+// The same split with the conversions as inline asm, for ONE caller: store_split of mono_fwd_wide_split_k, which writes the
+// planes to LDS -- no result reaches an MFMA from registers, so the hazard above cannot occur there.  Kept because that
+// kernel is 1 .. 5 % slower with the builtin form (the same instructions in another schedule, 41 instead of 117 s_nop:
+// profiles/device_header_ab.txt).  NEVER where a result feeds an MFMA.
+__device__ __forceinline__ unsigned cvt_pk_bf16_asm(float a, float b) {
+  unsigned r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ void split3_pair_asm(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
+  h = cvt_pk_bf16_asm(x0, x1);
+  const f32x2 r = f32x2{x0, x1} - f32x2{__uint_as_float(h << 16), __uint_as_float(h & 0xffff0000u)};   // exact
+  m = cvt_pk_bf16_asm(r[0], r[1]);
+  const f32x2 q = r - f32x2{__uint_as_float(m << 16), __uint_as_float(m & 0xffff0000u)};                // exact
+  l = cvt_pk_bf16_asm(q[0], q[1]);
+}
+// one value: x -> (hi, mid, lo) as bf16 bit patterns (gemm_split_k, element by element on the way into LDS)
+__device__ __forceinline__ void split3(float x, unsigned short& h, unsigned short& m, unsigned short& l) {
+  const unsigned ph = cvt_pk_bf16(x, 0.f) & 0xffffu;
+  const float r1 = x - __uint_as_float(ph << 16);
+  const unsigned pm = cvt_pk_bf16(r1, 0.f) & 0xffffu;
+  const float r2 = r1 - __uint_as_float(pm << 16);
+  const unsigned pl = cvt_pk_bf16(r2, 0.f) & 0xffffu;
+  h = (unsigned short)ph; m = (unsigned short)pm; l = (unsigned short)pl;
+}
+
 static inline int gnf_pow2_ge(int64_t v, int cap) {
   int g = 1;
   while (g < v && g < cap) g <<= 1;

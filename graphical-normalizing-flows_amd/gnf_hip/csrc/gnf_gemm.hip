@@ -14,9 +14,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-
 constexpr int BK = 16;
 constexpr int PAD = 4;
 
@@ -142,11 +139,9 @@ __global__ __launch_bounds__(256) void gemm_k(GemmArgs g) {
 // [rows][32+1] (odd stride: conflict-free fragment reads and scattered writes), a row-contiguous one
 // k-major [32][rows+4] with ds_write_b128.  Same MFMA tiling and epilogue as gemm_k.
 // ---------------------------------------------------------------------------------------------
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 // global side: only dword alignment is assumed.  gfx950 executes global_load_dwordx4 at any dword address (checked by
 // tools/unaligned_vec.hip), so operands with odd leading strides (MADE's K = 630, the 30-wide embedding outputs) take
 // the vector path too; the LDS side keeps its 16-B aligned layout.
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 constexpr int BKV = 32;
 
 template <int BX, bool KF>
@@ -159,10 +154,10 @@ struct Slab {            // staging of one operand: BX rows/cols x 32 k
     if (KF) { x = idx / (BKV / 4); k = 4 * (idx % (BKV / 4)); }
     else { x = 4 * (idx % (BX / 4)); k = idx / (BX / 4); }
   }
-  static __device__ __forceinline__ f32x4v load(const float* __restrict__ P, const float* __restrict__ Mk,
+  static __device__ __forceinline__ f32x4 load(const float* __restrict__ P, const float* __restrict__ Mk,
                                                  int64_t sx, int64_t sk, int64_t gx, int64_t gk, int64_t X,
                                                  int64_t kend) {
-    f32x4v v = {0.f, 0.f, 0.f, 0.f};
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
     if (KF) {
       if (gx < X) {
         const int64_t o = gx * sx + gk;
@@ -190,12 +185,12 @@ struct Slab {            // staging of one operand: BX rows/cols x 32 k
     }
     return v;
   }
-  static __device__ __forceinline__ void store(float* S, int x, int k, const f32x4v& v) {
+  static __device__ __forceinline__ void store(float* S, int x, int k, const f32x4& v) {
     if (KF) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) S[x * (BKV + 1) + k + c] = v[c];
     } else {
-      *reinterpret_cast<f32x4v*>(S + k * (BX + 4) + x) = v;
+      *reinterpret_cast<f32x4*>(S + k * (BX + 4) + x) = v;
     }
   }
   static __device__ __forceinline__ float frag(const float* S, int x, int k) {
@@ -239,7 +234,7 @@ __global__ __launch_bounds__(256) void gemm_vec_k(GemmArgs g) {
     }
   }
 
-  f32x4v ra[SA::NV], rb[SB::NV];
+  f32x4 ra[SA::NV], rb[SB::NV];
   f32x16 acc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
@@ -330,8 +325,6 @@ __global__ __launch_bounds__(256) void gemm_vec_k(GemmArgs g) {
 // fragment reads); B: [k][n] with pitch 132 == 4 (mod 32): MFMA step r contracts k = 16 kg + 4 q + r, four conflict-free
 // b32 reads per fragment.  90 TFLOP/s (tools/wide_gemm.hip): 0.60 -> 0.51 ms.
 // ---------------------------------------------------------------------------------------------
-typedef float f32x4w __attribute__((ext_vector_type(4)));
-typedef float f32x4wu __attribute__((ext_vector_type(4), aligned(4)));
 constexpr int WK = 128, WBM = 128, WBN = 128, WWAVES = 8, WLDB = WBN + 4;
 constexpr size_t kWideLds = (size_t)(WBM * WK + 2 * 64 * WLDB) * sizeof(float);
 
@@ -345,7 +338,6 @@ __global__ __launch_bounds__(64 * WWAVES, 1) void gemm_wide_k(GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) float wsm[];
   float* As = wsm;                        // [WBM][WK], chunk-swizzled
   float* Bs = wsm + WBM * WK;             // 2 x [64][WLDB]
-  typedef unsigned int u32x4w __attribute__((ext_vector_type(4)));
   const int64_t M = g.M;
   const int N = (int)g.N, sam = (int)g.sam, sbk = (int)g.sbk, scm = (int)g.scm;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -355,25 +347,24 @@ __global__ __launch_bounds__(64 * WWAVES, 1) void gemm_wide_k(GemmArgs g) {
   const int ntile = (N + WBN - 1) / WBN;
   const int64_t units = nblk * ntile;
   const int64_t u0 = units * blockIdx.x / gridDim.x, u1 = units * (blockIdx.x + 1) / gridDim.x;
-  const __amdgpu_buffer_rsrc_t rsB =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.B), 0, (int)(((int64_t)(WK - 1) * sbk + N) * 4), 0x00020000);
-  f32x4w pre[2][4];
-  auto fetch = [&](f32x4w (&dst)[4], int64_t u, int h) {
+  const rsrc_t rsB = make_rsrc(g.B, (int)(((int64_t)(WK - 1) * sbk + N) * 4));
+  f32x4 pre[2][4];
+  auto fetch = [&](f32x4 (&dst)[4], int64_t u, int h) {
     const int t = (int)(u % ntile);
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const int P = p * 512 + tid, k = P >> 5, n4 = P & 31;          // k 0..63, 4 consecutive n
       const int gn = WBN * t + 4 * n4;                               // N % 4 == 0: a quad is inside the row or past it
       const unsigned off = gn < N ? (unsigned)((64 * h + k) * sbk + gn) * 4u : 0xfffffff0u;
-      dst[p] = __builtin_bit_cast(f32x4w, __builtin_amdgcn_raw_buffer_load_b128(rsB, off, 0, 0));
+      dst[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, off, 0, 0));
     }
   };
-  auto stash = [&](const f32x4w (&src)[4], int buf) {
+  auto stash = [&](const f32x4 (&src)[4], int buf) {
     float* base = Bs + buf * (64 * WLDB);
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const int P = p * 512 + tid, k = P >> 5, n4 = P & 31;
-      *reinterpret_cast<f32x4w*>(base + k * WLDB + 4 * n4) = src[p];
+      *reinterpret_cast<f32x4*>(base + k * WLDB + 4 * n4) = src[p];
     }
   };
   int64_t cur_blk = -1;
@@ -389,22 +380,21 @@ __global__ __launch_bounds__(64 * WWAVES, 1) void gemm_wide_k(GemmArgs g) {
     const int rows = (int)(M - m0 < WBM ? M - m0 : WBM);
     if (blk != cur_blk) {                   // (re)load the A block: 4096 16-B chunks, 8 per thread
       __syncthreads();
-      const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.A) + m0 * sam, 0,
-                                                                           ((rows - 1) * sam + WK) * 4, 0x00020000);
+      const rsrc_t rsA = make_rsrc(g.A + m0 * sam, ((rows - 1) * sam + WK) * 4);
 #pragma unroll
       for (int p = 0; p < 8; ++p) {
         const int P = p * 512 + tid, row = P >> 5, c = P & 31;
         const unsigned off = row < rows ? (unsigned)(row * sam + 4 * c) * 4u : 0xfffffff0u;      // rows past M: zeros
-        const f32x4w v = __builtin_bit_cast(f32x4w, __builtin_amdgcn_raw_buffer_load_b128(rsA, off, 0, 0));
-        *reinterpret_cast<f32x4w*>(As + row * WK + 4 * ((c & ~7) | ((c & 7) ^ ((row >> 1) & 7)))) = v;
+        const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, off, 0, 0));
+        *reinterpret_cast<f32x4*>(As + row * WK + 4 * ((c & ~7) | ((c & 7) ^ ((row >> 1) & 7)))) = v;
       }
       cur_blk = blk;
     }
-    f32x4w acc[2][4];
+    f32x4 acc[2][4];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-      for (int b = 0; b < 4; ++b) acc[a][b] = f32x4w{0.f, 0.f, 0.f, 0.f};
+      for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       __syncthreads();
@@ -415,12 +405,12 @@ __global__ __launch_bounds__(64 * WWAVES, 1) void gemm_wide_k(GemmArgs g) {
         fetch(pre[1], u + 1 < u1 ? u + 1 : u, 1);           // (a clamped unit past the end is never used)
       }
       const float* Bh = Bs + h * (64 * WLDB);
-      f32x4w af[2][2], bf[2][4];
+      f32x4 af[2][2], bf[2][4];
       auto frags = [&](int kg, int slot) {
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
           const int row = (wm * 2 + a) * 16 + j, c = 16 * h + 4 * kg + q;
-          af[slot][a] = *reinterpret_cast<const f32x4w*>(As + row * WK + 4 * ((c & ~7) | ((c & 7) ^ ((row >> 1) & 7))));
+          af[slot][a] = *reinterpret_cast<const f32x4*>(As + row * WK + 4 * ((c & ~7) | ((c & 7) ^ ((row >> 1) & 7))));
         }
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
@@ -451,8 +441,7 @@ __global__ __launch_bounds__(64 * WWAVES, 1) void gemm_wide_k(GemmArgs g) {
 #pragma unroll
     for (int p = 0; p < 4; ++p) asm volatile("" : "+v"(pre[0][p]), "+v"(pre[1][p]));     // both requests complete HERE
     __builtin_amdgcn_sched_barrier(0);
-    const __amdgpu_buffer_rsrc_t rsC =
-        __builtin_amdgcn_make_buffer_rsrc(g.C + m0 * scm, 0, ((rows - 1) * scm + N) * 4, 0x00020000);
+    const rsrc_t rsC = make_rsrc(g.C + m0 * scm, ((rows - 1) * scm + N) * 4);
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
       const int n = WBN * t + (wn * 4 + b) * 16 + j;
@@ -502,11 +491,11 @@ __global__ __launch_bounds__(128 * WR, 4 / WR) void gemm_tall_k(GemmArgs g) {
   const int64_t ntiles = (M + BM - 1) / BM;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t m0 = tile * BM;
-    f32x4w acc[TMW][4];
+    f32x4 acc[TMW][4];
 #pragma unroll
     for (int a = 0; a < TMW; ++a)
 #pragma unroll
-      for (int b = 0; b < 4; ++b) acc[a][b] = f32x4w{0.f, 0.f, 0.f, 0.f};
+      for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
     // this thread's 16-B pieces of a slab: piece p covers position P = p * NT + tid -> row P / 8, chunk position P % 8,
     // holding the row's logical chunk (P % 8) ^ ((row >> 1) & 7).  The first PA pieces are rows of A, the rest rows of B
     // (BM * 8 is a multiple of NT).  One buffer descriptor per operand (A: per row block), a 32-bit lane offset that does
@@ -516,10 +505,8 @@ __global__ __launch_bounds__(128 * WR, 4 / WR) void gemm_tall_k(GemmArgs g) {
     constexpr int PIECES = (BM + TBN) * 8 / NT, PA = BM * 8 / NT;
     static_assert((BM + TBN) * 8 % NT == 0 && BM * 8 % NT == 0, "whole pieces per thread, A and B pieces apart");
     const int rows = (int)(M - m0 < BM ? M - m0 : BM);
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.A) + m0 * g.sam, 0,
-                                                                         (int)(((int64_t)(rows - 1) * g.sam + K) * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.B), 0,
-                                                                         (int)(((int64_t)(N - 1) * g.sbn + K) * 4), 0x00020000);
+    const rsrc_t rsA = make_rsrc(g.A + m0 * g.sam, (int)(((int64_t)(rows - 1) * g.sam + K) * 4));
+    const rsrc_t rsB = make_rsrc(g.B, (int)(((int64_t)(N - 1) * g.sbn + K) * 4));
     unsigned voff[PIECES];
 #pragma unroll
     for (int p = 0; p < PIECES; ++p) {
@@ -528,16 +515,16 @@ __global__ __launch_bounds__(128 * WR, 4 / WR) void gemm_tall_k(GemmArgs g) {
       if (p < PA) voff[p] = row < rows ? (unsigned)(row * (int)g.sam + 4 * c) * 4u : 0xfffffff0u;
       else voff[p] = row - BM < N ? (unsigned)((row - BM) * (int)g.sbn + 4 * c) * 4u : 0xfffffff0u;
     }
-    f32x4w pre[PIECES];
+    f32x4 pre[PIECES];
     auto fetch = [&](int k0) {
 #pragma unroll
       for (int p = 0; p < PIECES; ++p)
-        pre[p] = __builtin_bit_cast(f32x4w, __builtin_amdgcn_raw_buffer_load_b128(p < PA ? rsA : rsB, voff[p], k0 * 4, 0));
+        pre[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(p < PA ? rsA : rsB, voff[p], k0 * 4, 0));
     };
     auto stash = [&](int stage) {
       float* base = tsm + stage * SLAB + tid * 4;
 #pragma unroll
-      for (int p = 0; p < PIECES; ++p) *reinterpret_cast<f32x4w*>(base + p * NT * 4) = pre[p];
+      for (int p = 0; p < PIECES; ++p) *reinterpret_cast<f32x4*>(base + p * NT * 4) = pre[p];
     };
     fetch(0);
     stash(0);
@@ -549,16 +536,16 @@ __global__ __launch_bounds__(128 * WR, 4 / WR) void gemm_tall_k(GemmArgs g) {
       const float* Bs = As + BM * TBK;
 #pragma unroll
       for (int kg = 0; kg < 2; ++kg) {
-        f32x4w af[TMW], bf[4];
+        f32x4 af[TMW], bf[4];
 #pragma unroll
         for (int a = 0; a < TMW; ++a) {
           const int row = (wm * TMW + a) * 16 + j;
-          af[a] = *reinterpret_cast<const f32x4w*>(As + row * TBK + 4 * ((4 * kg + q) ^ ((row >> 1) & 7)));
+          af[a] = *reinterpret_cast<const f32x4*>(As + row * TBK + 4 * ((4 * kg + q) ^ ((row >> 1) & 7)));
         }
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
           const int row = (wn * 4 + b) * 16 + j;
-          bf[b] = *reinterpret_cast<const f32x4w*>(Bs + row * TBK + 4 * ((4 * kg + q) ^ ((row >> 1) & 7)));
+          bf[b] = *reinterpret_cast<const f32x4*>(Bs + row * TBK + 4 * ((4 * kg + q) ^ ((row >> 1) & 7)));
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r)
@@ -619,7 +606,6 @@ constexpr int KMK = 64, KMN = 128, KMLDS = 2 * KMK * (128 + KMN) * (int)sizeof(f
 
 __global__ __launch_bounds__(512, 1) void gemm_kmajor_k(GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) float ksm[];
-  typedef float f32x2w __attribute__((ext_vector_type(2)));
   constexpr int SLAB = KMK * (128 + KMN);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int q = lane >> 4, j = lane & 15;
@@ -631,20 +617,18 @@ __global__ __launch_bounds__(512, 1) void gemm_kmajor_k(GemmArgs g) {
   if (k0 >= g.K) return;
   const int kn = (int)(g.K - k0 < g.k_per_split ? g.K - k0 : g.k_per_split);
   const int n0 = tile * KMN;
-  const __amdgpu_buffer_rsrc_t rsA =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.A) + k0 * sak, 0, ((kn - 1) * sak + M) * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsB =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.B) + k0 * sbk, 0, ((kn - 1) * sbk + N) * 4, 0x00020000);
+  const rsrc_t rsA = make_rsrc(g.A + k0 * sak, ((kn - 1) * sak + M) * 4);
+  const rsrc_t rsB = make_rsrc(g.B + k0 * sbk, ((kn - 1) * sbk + N) * 4);
   // 16-B pieces of a slab: 64 rows x 32 quads per operand, 4 + 4 per thread
-  f32x4w pa[4], pb[4];
+  f32x4 pa[4], pb[4];
   auto fetch = [&](int s) {
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const int P = p * 512 + tid, row = s * KMK + (P >> 5), c = P & 31;
-      pa[p] = __builtin_bit_cast(f32x4w, __builtin_amdgcn_raw_buffer_load_b128(
+      pa[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
                                              rsA, 4 * c < M ? (unsigned)(row * sak + 4 * c) * 4u : 0xfffffff0u, 0, 0));
       const int gn = n0 + 4 * c;
-      pb[p] = __builtin_bit_cast(f32x4w, __builtin_amdgcn_raw_buffer_load_b128(
+      pb[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
                                              rsB, gn < N ? (unsigned)(row * sbk + gn) * 4u : 0xfffffff0u, 0, 0));
     }
   };
@@ -654,15 +638,15 @@ __global__ __launch_bounds__(512, 1) void gemm_kmajor_k(GemmArgs g) {
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const int P = p * 512 + tid, row = P >> 5, c = P & 31;
-      *reinterpret_cast<f32x4w*>(a + row * 128 + 4 * c) = pa[p];
-      *reinterpret_cast<f32x4w*>(b + row * KMN + 4 * c) = pb[p];
+      *reinterpret_cast<f32x4*>(a + row * 128 + 4 * c) = pa[p];
+      *reinterpret_cast<f32x4*>(b + row * KMN + 4 * c) = pb[p];
     }
   };
-  f32x4w acc[4][2];
+  f32x4 acc[4][2];
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = f32x4w{0.f, 0.f, 0.f, 0.f};
+    for (int b = 0; b < 2; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int nslab = (kn + KMK - 1) / KMK;
   fetch(0);
   stash(0);
@@ -673,8 +657,8 @@ __global__ __launch_bounds__(512, 1) void gemm_kmajor_k(GemmArgs g) {
     const float* Bs = As + KMK * 128;
 #pragma unroll
     for (int kk = 0; kk < KMK / 4; ++kk) {
-      const f32x4w af = *reinterpret_cast<const f32x4w*>(As + (4 * kk + q) * 128 + 64 * wm + 4 * j);
-      const f32x2w bf = *reinterpret_cast<const f32x2w*>(Bs + (4 * kk + q) * KMN + 32 * wn + 2 * j);
+      const f32x4 af = *reinterpret_cast<const f32x4*>(As + (4 * kk + q) * 128 + 64 * wm + 4 * j);
+      const f32x2 bf = *reinterpret_cast<const f32x2*>(Bs + (4 * kk + q) * KMN + 32 * wn + 2 * j);
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
         acc[a][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[a], bf[0], acc[a][0], 0, 0, 0);
@@ -690,7 +674,7 @@ __global__ __launch_bounds__(512, 1) void gemm_kmajor_k(GemmArgs g) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int m = 64 * wm + 4 * (4 * q + r) + a, n = n0 + 32 * wn + 2 * j;
-      if (m < M && n < N) *reinterpret_cast<f32x2w*>(out + (int64_t)m * g.scm + n) = f32x2w{acc[a][0][r], acc[a][1][r]};
+      if (m < M && n < N) *reinterpret_cast<f32x2*>(out + (int64_t)m * g.scm + n) = f32x2{acc[a][0][r], acc[a][1][r]};
     }
 }
 
@@ -747,12 +731,8 @@ int gnf_gemm_launch(GemmArgs g, int splits, hipStream_t s) {
       g.sak >= g.M && g.sbk >= g.N &&       // rows past a K range must lie past the descriptor's extent (they read as zeros)
       (((uintptr_t)g.A | (uintptr_t)g.B) & 15) == 0 && (((uintptr_t)g.C | (uintptr_t)(g.c_split_stride * 4)) & 7) == 0 &&
       g.k_per_split * (g.sak > g.sbk ? g.sak : g.sbk) < (1 << 28) && ((g.N + KMN - 1) / KMN) * nsp >= 64 && nsp <= 4096) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kmajor_k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              KMLDS);
-    hipLaunchKernelGGL(gemm_kmajor_k, dim3((unsigned)(((g.N + KMN - 1) / KMN) * nsp)), dim3(512), KMLDS, s, g);
     g_last_kernel = "gemm_kmajor_k";
-    GNF_LAUNCH_CHECK();
-    return 0;
+    return (int)gnf_launch_lds(gemm_kmajor_k, dim3((unsigned)(((g.N + KMN - 1) / KMN) * nsp)), dim3(512), KMLDS, s, g);
   }
   // short K, wide N, tall M, no epilogue options (fc1 data gradient): the persistent unit-range kernel
   if (g.K == WK && nsp == 1 && !g.grp && g.sak == 1 && g.sbn == 1 && g.scn == 1 && !g.bias && !g.Bmask && !g.Cmask &&
@@ -760,12 +740,8 @@ int gnf_gemm_launch(GemmArgs g, int splits, hipStream_t s) {
       // 32-bit lane offsets inside a row block / inside B, 16-B aligned quads
       g.sam % 4 == 0 && g.sbk % 4 == 0 && (((uintptr_t)g.A | (uintptr_t)g.B) & 15) == 0 && g.N < (1 << 24) &&
       (int64_t)WBM * g.sam < (1 << 28) && (int64_t)WBM * g.scm < (1 << 28) && (int64_t)WK * g.sbk < (1 << 28)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_wide_k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)kWideLds);
-    hipLaunchKernelGGL(gemm_wide_k, dim3(256), dim3(64 * WWAVES), kWideLds, s, g);
     g_last_kernel = "gemm_wide_k";
-    GNF_LAUNCH_CHECK();
-    return 0;
+    return (int)gnf_launch_lds(gemm_wide_k, dim3(256), dim3(64 * WWAVES), kWideLds, s, g);
   }
   // vector path: A and B each have a unit-stride dimension (any leading stride, dword alignment)
   const bool akf = g.sak == 1, amf = !akf && g.sam == 1;
@@ -790,17 +766,11 @@ int gnf_gemm_launch(GemmArgs g, int splits, hipStream_t s) {
     if (tmw) {
       const int64_t bm = 16 * wr * tmw, tiles = (g.M + bm - 1) / bm, slots = 256 * (4 / wr);
       const unsigned tgrid = (unsigned)(tiles < slots ? tiles : slots);
-#define GNF_TALL_LAUNCH(T, W)                                                                                     \
-  do {                                                                                                            \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tall_k<T, W>),                                   \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)tall_lds<T, W>());                  \
-    hipLaunchKernelGGL((gemm_tall_k<T, W>), dim3(tgrid), dim3(128 * W), (tall_lds<T, W>()), s, g);                 \
-  } while (0)
-      if (tmw == 5) GNF_TALL_LAUNCH(5, 4); else if (tmw == 4) GNF_TALL_LAUNCH(4, 4); else GNF_TALL_LAUNCH(3, 4);
-#undef GNF_TALL_LAUNCH
       g_last_kernel = "gemm_tall_k";
-      GNF_LAUNCH_CHECK();
-      return 0;
+      const dim3 tg(tgrid), tb(128 * wr);
+      if (tmw == 5) return (int)gnf_launch_lds(gemm_tall_k<5, 4>, tg, tb, tall_lds<5, 4>(), s, g);
+      if (tmw == 4) return (int)gnf_launch_lds(gemm_tall_k<4, 4>, tg, tb, tall_lds<4, 4>(), s, g);
+      return (int)gnf_launch_lds(gemm_tall_k<3, 4>, tg, tb, tall_lds<3, 4>(), s, g);
     }
   }
   // otherwise pick the tile height that leaves the fewest tile-rows on the busiest CU

@@ -17,27 +17,7 @@
 #include "gnf_gemm.h"
 #include <stdlib.h>
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
 namespace {
-
-// packed pair of RNE bf16: lo half = bf16(a), hi half = bf16(b)
-__device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
-// x -> (hi, mid, lo) as bf16 bit patterns
-__device__ __forceinline__ void split3(float x, unsigned short& h, unsigned short& m, unsigned short& l) {
-  const unsigned ph = cvt_pk_bf16(x, 0.f) & 0xffffu;
-  const float r1 = x - __uint_as_float(ph << 16);                   // exact (Sterbenz-like: hi is x rounded to 8 bits)
-  const unsigned pm = cvt_pk_bf16(r1, 0.f) & 0xffffu;
-  const float r2 = r1 - __uint_as_float(pm << 16);                  // exact; <= 8 significant bits are left
-  const unsigned pl = cvt_pk_bf16(r2, 0.f) & 0xffffu;
-  h = (unsigned short)ph; m = (unsigned short)pm; l = (unsigned short)pl;
-}
 
 constexpr int TS = 64;          // tile edge
 constexpr int KS = 32;          // K-slab = one bf16 MFMA
@@ -134,19 +114,6 @@ __global__ __launch_bounds__(256) void gemm_split_k(SplitArgs g) {
 
 
 // ------------------------------------------------------------------------------------------------ dedicated kernels
-// x0, x1 -> packed (hi, mid, lo) pairs: 11 VALU instructions per two elements
-__device__ __forceinline__ void split3_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-  h = cvt_pk_bf16(x0, x1);
-  const float r0 = x0 - __uint_as_float(h << 16), r1 = x1 - __uint_as_float(h & 0xffff0000u);
-  m = cvt_pk_bf16(r0, r1);
-  const float q0 = r0 - __uint_as_float(m << 16), q1 = r1 - __uint_as_float(m & 0xffff0000u);
-  l = cvt_pk_bf16(q0, q1);
-}
-
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-__device__ __forceinline__ bf16x8 as_bf16x8(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
-
 // The small operand of a dedicated kernel (the fc1 weight in either orientation), split ONCE per call into FRAGMENT-MAJOR
 // bf16 planes: planes[p][slab][ntile][lane] = the 16 bytes lane `lane` of a wavefront feeds to v_mfma_f32_16x16x32_bf16 as
 // the B operand of (K-slab `slab`, 16-column tile `ntile`): n = 16 ntile + (lane & 15), k = 32 slab + 8 (lane >> 4) .. + 7.
@@ -296,20 +263,20 @@ __global__ __launch_bounds__(TL_THREADS) void gemm_split_tall_k(TallArgs g) {
       const unsigned char* stage = lds + u * TL_STAGE + frag;
 #pragma unroll
       for (int i = 0; i < 5; ++i) {
-        const bf16x8 ah = as_bf16x8(*reinterpret_cast<const u32x4*>(stage + i * 16 * TL_PITCH));
-        const bf16x8 am = as_bf16x8(*reinterpret_cast<const u32x4*>(stage + i * 16 * TL_PITCH + TL_PLANE));
-        const bf16x8 al = as_bf16x8(*reinterpret_cast<const u32x4*>(stage + i * 16 * TL_PITCH + 2 * TL_PLANE));
+        const u32x4 ah = *reinterpret_cast<const u32x4*>(stage + i * 16 * TL_PITCH);
+        const u32x4 am = *reinterpret_cast<const u32x4*>(stage + i * 16 * TL_PITCH + TL_PLANE);
+        const u32x4 al = *reinterpret_cast<const u32x4*>(stage + i * 16 * TL_PITCH + 2 * TL_PLANE);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          const bf16x8 bh = as_bf16x8(breg[u][j][0]), bm = as_bf16x8(breg[u][j][1]), bl = as_bf16x8(breg[u][j][2]);
+          const u32x4 bh = breg[u][j][0], bm = breg[u][j][1], bl = breg[u][j][2];
           f32x4 r = acc[1][i][j];
-          r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, r, 0, 0, 0);
-          r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, r, 0, 0, 0);
-          r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bm, r, 0, 0, 0);
-          r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bh, r, 0, 0, 0);
-          r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm, r, 0, 0, 0);
+          r = mfma_bf16(al, bh, r);
+          r = mfma_bf16(ah, bl, r);
+          r = mfma_bf16(am, bm, r);
+          r = mfma_bf16(am, bh, r);
+          r = mfma_bf16(ah, bm, r);
           acc[1][i][j] = r;
-          acc[0][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc[0][i][j], 0, 0, 0);
+          acc[0][i][j] = mfma_bf16(ah, bh, acc[0][i][j]);
         }
       }
       load_b(s0 + u + 2, breg[u]);
@@ -416,20 +383,20 @@ __global__ __launch_bounds__(512) void gemm_split_wide_k(WideArgs g) {
 #pragma unroll
       for (int i = 0; i < 5; ++i) {
         const unsigned char* ap = afrag + i * 16 * WD_PITCH + 64 * slab;
-        const bf16x8 ah = as_bf16x8(*reinterpret_cast<const u32x4*>(ap));
-        const bf16x8 am = as_bf16x8(*reinterpret_cast<const u32x4*>(ap + WD_PLANE));
-        const bf16x8 al = as_bf16x8(*reinterpret_cast<const u32x4*>(ap + 2 * WD_PLANE));
+        const u32x4 ah = *reinterpret_cast<const u32x4*>(ap);
+        const u32x4 am = *reinterpret_cast<const u32x4*>(ap + WD_PLANE);
+        const u32x4 al = *reinterpret_cast<const u32x4*>(ap + 2 * WD_PLANE);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          const bf16x8 bh = as_bf16x8(breg[slab & 1][j][0]), bm = as_bf16x8(breg[slab & 1][j][1]), bl = as_bf16x8(breg[slab & 1][j][2]);
+          const u32x4 bh = breg[slab & 1][j][0], bm = breg[slab & 1][j][1], bl = breg[slab & 1][j][2];
           f32x4 r = acc[1][i][j];                            // (B fragment first: the tile comes out transposed, see above)
-          r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, al, r, 0, 0, 0);
-          r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl, ah, r, 0, 0, 0);
-          r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bm, am, r, 0, 0, 0);
-          r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, am, r, 0, 0, 0);
-          r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bm, ah, r, 0, 0, 0);
+          r = mfma_bf16(bh, al, r);
+          r = mfma_bf16(bl, ah, r);
+          r = mfma_bf16(bm, am, r);
+          r = mfma_bf16(bh, am, r);
+          r = mfma_bf16(bm, ah, r);
           acc[1][i][j] = r;
-          acc[0][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, ah, acc[0][i][j], 0, 0, 0);
+          acc[0][i][j] = mfma_bf16(bh, ah, acc[0][i][j]);
         }
       }
       // (pinned: left to itself the machine scheduler sinks these requests to just in front of their first use two slabs
@@ -540,20 +507,20 @@ __global__ __launch_bounds__(512) void gemm_split_kmajor_k(KmArgs g) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const unsigned char* bp = stage + j * 16 * KM_PITCH + 64 * ks;
-          const bf16x8 bh = as_bf16x8(*reinterpret_cast<const u32x4*>(bp));
-          const bf16x8 bm = as_bf16x8(*reinterpret_cast<const u32x4*>(bp + KM_PLANE));
-          const bf16x8 bl = as_bf16x8(*reinterpret_cast<const u32x4*>(bp + 2 * KM_PLANE));
+          const u32x4 bh = *reinterpret_cast<const u32x4*>(bp);
+          const u32x4 bm = *reinterpret_cast<const u32x4*>(bp + KM_PLANE);
+          const u32x4 bl = *reinterpret_cast<const u32x4*>(bp + 2 * KM_PLANE);
 #pragma unroll
           for (int i = 0; i < 2; ++i) {
-            const bf16x8 ah = as_bf16x8(areg[ks][i][0]), am = as_bf16x8(areg[ks][i][1]), al = as_bf16x8(areg[ks][i][2]);
+            const u32x4 ah = areg[ks][i][0], am = areg[ks][i][1], al = areg[ks][i][2];
             f32x4 r = acc[1][i][j];                              // (B fragment first: a lane holds four consecutive columns)
-            r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, al, r, 0, 0, 0);
-            r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl, ah, r, 0, 0, 0);
-            r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bm, am, r, 0, 0, 0);
-            r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, am, r, 0, 0, 0);
-            r = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bm, ah, r, 0, 0, 0);
+            r = mfma_bf16(bh, al, r);
+            r = mfma_bf16(bl, ah, r);
+            r = mfma_bf16(bm, am, r);
+            r = mfma_bf16(bh, am, r);
+            r = mfma_bf16(bm, ah, r);
             acc[1][i][j] = r;
-            acc[0][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh, ah, acc[0][i][j], 0, 0, 0);
+            acc[0][i][j] = mfma_bf16(bh, ah, acc[0][i][j]);
           }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -654,10 +621,8 @@ extern "C" int gnf_gemm_split_bf16(const float* A, int64_t sam, int64_t sak, con
                          nslab, (u32x4*)ws);
       GNF_LAUNCH_CHECK();
       TallArgs t{A, sam, (const u32x4*)ws, C, scm, bias, relu, M, (int)N, nslab};
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_split_tall_k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                TL_LDS);
-      hipLaunchKernelGGL(gemm_split_tall_k, dim3((unsigned)((M + TL_BM - 1) / TL_BM)), dim3(TL_THREADS), TL_LDS, s, t);
-      GNF_LAUNCH_CHECK();
+      if (hipError_t e = gnf_launch_lds(gemm_split_tall_k, dim3((unsigned)((M + TL_BM - 1) / TL_BM)), dim3(TL_THREADS), TL_LDS, s, t))
+        return (int)e;
       g_split_last = "gemm_split_tall_k";
       return 0;
     }
@@ -671,10 +636,8 @@ extern "C" int gnf_gemm_split_bf16(const float* A, int64_t sam, int64_t sak, con
       GNF_LAUNCH_CHECK();
       float* part = (float*)((char*)ws + 3 * frags * 16);
       KmArgs ka{(const u32x4*)ws, B, sbk, part, M, N, K, nslab, stages};
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_split_kmajor_k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                KM_LDS);
-      hipLaunchKernelGGL(gemm_split_kmajor_k, dim3((unsigned)((N / KM_BN) * splits)), dim3(512), KM_LDS, s, ka);
-      GNF_LAUNCH_CHECK();
+      if (hipError_t e = gnf_launch_lds(gemm_split_kmajor_k, dim3((unsigned)((N / KM_BN) * splits)), dim3(512), KM_LDS, s, ka))
+        return (int)e;
       const int64_t n4 = M * N / 4;
       hipLaunchKernelGGL(split_reduce_k, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, part, splits, n4, n4, (f32x4*)C,
                          scm / 4, N / 4);
@@ -689,10 +652,8 @@ extern "C" int gnf_gemm_split_bf16(const float* A, int64_t sam, int64_t sak, con
                          ntiles, 4, (u32x4*)ws);
       GNF_LAUNCH_CHECK();
       WideArgs wa{A, sam, (const u32x4*)ws, C, scm, (float*)((char*)ws + 3 * frags * 16), M, (int)N};
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_split_wide_k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                WD_LDS);
-      hipLaunchKernelGGL(gemm_split_wide_k, dim3((unsigned)((M + WD_BM - 1) / WD_BM)), dim3(512), WD_LDS, s, wa);
-      GNF_LAUNCH_CHECK();
+      if (hipError_t e = gnf_launch_lds(gemm_split_wide_k, dim3((unsigned)((M + WD_BM - 1) / WD_BM)), dim3(512), WD_LDS, s, wa))
+        return (int)e;
       g_split_last = "gemm_split_wide_k";
       return 0;
     }

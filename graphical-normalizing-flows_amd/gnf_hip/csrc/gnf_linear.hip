@@ -33,14 +33,6 @@ extern "C" int gnf_colsum(const float* a, int64_t lda, float* out, int64_t M, in
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));     // dwordx4 at any dword address
-typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
-
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 // mask(o, i) of a layer with weight [N out][K in]: the full 0/1 tensor (row-major [N][K]) or, when drow != NULL, the
 // degree rule dcol[i] <= drow[o] (strict: <).  Neither: no mask.
 struct LinMask {

@@ -22,19 +22,9 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 // row loads: a dwordx4 of row `r` at column c0 (a multiple of 4) through a bounds-checked descriptor -- dword alignment
 // is enough on gfx950, a request past the end of the buffer returns zeros -- with the columns >= ncols (the next row's
 // first floats when ncols is not a multiple of 4, or a whole chunk of padding) cleared
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
 __device__ __forceinline__ f32x4 ldrow(rsrc_t rs, int r, int ncols, int c0) {
   // always issued (no branch around a load: the requests of a tile must go out back to back); what lies outside the
   // row is cleared afterwards
@@ -50,9 +40,8 @@ __device__ __forceinline__ f32x4 ldrowx(const float* base, rsrc_t rs, int r, int
   if constexpr (KX) return *reinterpret_cast<const f32x4*>(base + (int64_t)r * ncols + c0);
   else return ldrow(rs, r, ncols, c0);
 }
-__device__ __forceinline__ rsrc_t mkrsrc(const float* p, int64_t floats) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, (int)(floats * 4), 0x00020000);
-}
+// descriptor over `floats` floats (a 64-bit count: rows x row pitch)
+__device__ __forceinline__ rsrc_t mkrsrc(const float* p, int64_t floats) { return make_rsrc(p, (int)(floats * 4)); }
 
 // ------------------------------------------------------------------------------------------------------------- forward
 template <int NT, int KC, bool KX>  // N <= 16 NT out units, K <= 16 KC inputs (KX: K == 16 KC exactly)

@@ -5,8 +5,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int IMG = 28, C1 = 26, C2 = 24, PO = 12, NCH = 16;
 constexpr int ROWE = 36, ESZ = IMG * ROWE;            // padded input image
 constexpr int ROW = 40, CH = C1 * ROW;                // conv1 activations: [16][26][40], CH = 1040 == 16 mod 32
@@ -18,15 +16,10 @@ constexpr int PROW = NCH * 144 + NCH * 16 + NCH;      // per-wave gradient parti
 
 static_assert(CH % 32 == 16 && CHD % 32 == 16, "channel strides must sit 16 banks apart");
 
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 // Packed fp32 VALU (2 flops per lane per op) for the Winograd transforms.  One row (t0,t1,t2,t3) of B^T d held as
 // A = (t0,t1), B = (t2,t3) gives the four outputs of (B^T d) B in two instructions:
 //   A - B                       = (t0 - t2, t1 - t3) = (v0, v3)
 //   (A.hi + B.lo, -A.hi + B.lo) = (t1 + t2, t2 - t1) = (v1, v2)      [op_sel picks the halves, neg_hi negates src0]
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 pk_v12(f32x2 a, f32x2 b) {
   f32x2 r;
   asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,0] neg_hi:[1,0]" : "=v"(r) : "v"(a), "v"(b));
@@ -62,10 +55,6 @@ struct CnnArgs {
   const int32_t* plan; float* gec; int dplan;                             // backward, column plan (gnf_hip.h) or NULL
 };
 
-// max(x, 0) as ONE v_max_f32: fmaxf() compiles into a canonicalising v_max(x, x) plus the maximum
-__device__ __forceinline__ float relu1(float x) { float y; asm("v_max_f32 %0, 0, %1" : "=v"(y) : "v"(x)); return y; }
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 // conv1 + ReLU of NU units starting at unit u0, on v_mfma_f32_16x16x1_4b_f32 (four independent 16 x 16 x 1 products per
 // instruction): block b = the 16-position tile 4 u + b, ONE tap per instruction -- 9 instructions per 64 positions where
 // the 16x16x4 form takes 4 x 3 K-steps (a quarter of them multiplying the zero taps 9..11).  B operand = the lane's OWN

@@ -242,10 +242,8 @@ __device__ __forceinline__ void cnn_bwd_body(const CnnArgs& a, float* smem) {
   // the per-image streams go through buffer descriptors built per image in SGPRs (base = the image's first byte, extent
   // = one image or 0 behind the last one: out-of-range lanes read 0 / store nothing): ONE 32-bit lane offset per stream
   // instead of a 64-bit address computation per load -- the scatter interval S is VALU-bound
-  typedef __amdgpu_buffer_rsrc_t rsrc_t;
   auto rsrc_of = [&](const void* base, int64_t im, int bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(static_cast<const char*>(base)) + im * bytes, 0,
-                                             im < a.n ? bytes : 0, 0x00020000);
+    return make_rsrc(static_cast<const char*>(base) + im * bytes, im < a.n ? bytes : 0);
   };
   const int vo_e = tid * 4, vo_g = ((tid >> 5) * (PO * PO) + (tid & 31)) * 4, vo_a = (tid >> 5) * (PO * PO) + (tid & 31);
   auto prefetch_e = [&](int64_t im) {        // the prefetch synchronous
@@ -708,10 +706,8 @@ int gnf_mnistcnn_conv_bwd_cols(const float* e, const float* W1, const float* b1,
   a.n = n_img;
   a.plan = plan; a.gec = ge_cols; a.dplan = (int)d_plan;
   // fixed grid: every workgroup (also one without images) writes its partial rows
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cnn_bwd_wino_k),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBwdWinoLds);
-  hipLaunchKernelGGL(cnn_bwd_wino_k, dim3(kBwdGrid), dim3(64 * BWD_WAVES), kBwdWinoLds, (hipStream_t)stream, a);
-  GNF_LAUNCH_CHECK();
+  if (hipError_t e = gnf_launch_lds(cnn_bwd_wino_k, dim3(kBwdGrid), dim3(64 * BWD_WAVES), kBwdWinoLds, (hipStream_t)stream, a))
+    return (int)e;
   // one partial row per workgroup -> the four gradients, one launch
   hipLaunchKernelGGL(cnn_reduce_unpack_k, dim3((PROW + 63) / 64), dim3(1024), 0, (hipStream_t)stream, (const float*)ws,
                      (int)kBwdGrid, gW1, gb1, gW2, gb2);

@@ -196,7 +196,6 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void cnn_fwd_wino_k(CnnArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, q = lane >> 4, j = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   constexpr int NW = FWD_WAVES, NT = 64 * FWD_WAVES;
-  typedef __amdgpu_buffer_rsrc_t rsrc_t;
 
   if (tid < 9 * NCH) w1_s[tid] = a.W1[(tid & 15) * 9 + (tid >> 4)];
   f32x4 b1v, b2v;
@@ -224,8 +223,7 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void cnn_fwd_wino_k(CnnArgs a) {
   }
 
   auto rsrc_of = [&](const void* base, int64_t im, int bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(static_cast<const char*>(base)) + im * bytes, 0,
-                                             im < a.n ? bytes : 0, 0x00020000);
+    return make_rsrc(static_cast<const char*>(base) + im * bytes, im < a.n ? bytes : 0);
   };
   constexpr int EPT = (IMG * IMG + NT - 1) / NT;
   float pre[EPT];
@@ -458,18 +456,11 @@ int gnf_mnistcnn_conv_fwd(const float* e, const float* W1, const float* b1, cons
   CnnArgs a{};
   a.e = e; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.pooled = pooled; a.arg = argmax; a.n = n_img;
   if (exact_ties) {                                 // direct implicit GEMM: bit-equal outputs for equal patches
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cnn_fwd_k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)kFwdLds);
     const unsigned grid = n_img < kFwdGrid ? (unsigned)n_img : kFwdGrid;
-    hipLaunchKernelGGL(cnn_fwd_k, dim3(grid), dim3(64 * FWD_WAVES), kFwdLds, (hipStream_t)stream, a);
-  } else {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cnn_fwd_wino_k),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWinoLds);
-    const unsigned grid = n_img < kWinoGrid ? (unsigned)n_img : kWinoGrid;
-    hipLaunchKernelGGL(cnn_fwd_wino_k, dim3(grid), dim3(64 * FWD_WAVES), kWinoLds, (hipStream_t)stream, a);
+    return (int)gnf_launch_lds(cnn_fwd_k, dim3(grid), dim3(64 * FWD_WAVES), kFwdLds, (hipStream_t)stream, a);
   }
-  GNF_LAUNCH_CHECK();
-  return 0;
+  const unsigned grid = n_img < kWinoGrid ? (unsigned)n_img : kWinoGrid;
+  return (int)gnf_launch_lds(cnn_fwd_wino_k, dim3(grid), dim3(64 * FWD_WAVES), kWinoLds, (hipStream_t)stream, a);
 }
 
 }  // extern "C"

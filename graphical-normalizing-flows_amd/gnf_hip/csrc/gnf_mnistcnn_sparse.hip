@@ -37,9 +37,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int IMG = 28, NPIX = IMG * IMG, NCH = 16;
 constexpr int CROP = 14, ES = 16, ESZ = CROP * ES;     // crop of the masked image, row stride 16
 constexpr int A1 = 12, PL = A1 * A1;                   // conv1 activations [16][12][12]; PL = 144 == 16 mod 64 banks
@@ -48,9 +45,6 @@ constexpr int NORIG = 64;                              // crop origins (r0, c0) 
 constexpr int WAVES = 4;
 constexpr int WLDS = ESZ + NCH * PL;                   // floats of LDS per wavefront
 
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 // Winograd F(2x2,3x3) input transform B^T d B of a 4x4 patch given as 4 rows x 2 column pairs; out[xi = 4 xi_y + xi_x] (the dense
 // kernels' routine, gnf_mnistcnn.h: two v_pk_add_f32 per row of B^T d)
 __device__ __forceinline__ f32x2 pk_v12(f32x2 a, f32x2 b) {

@@ -5,8 +5,6 @@
 
 namespace gnfmono {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kWaves = 4;          // wavefronts per workgroup
 constexpr int kMaxNH = GNF_MONO_MAX_LAYERS - 1;
 constexpr int kNarrowQ = 3 * 3 * (256 + 128);   // words of one bf16-split 48 x 48 block (MonoLayout::o_Wq)
@@ -143,15 +141,11 @@ __device__ __forceinline__ void store_inverse(const MonoArgs& a, int64_t e, floa
     a.xo[e] = v;
   }
 }
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 // 16 B per lane global -> LDS without passing through registers (global_load_lds_dwordx4): the LDS destination of a
 // wave-instruction is lane-linear, which a contiguous copy is.  Completion: s_waitcnt vmcnt(0) before the barrier.
 __device__ __forceinline__ void glds16(const float* g, float* l) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
                                    (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 // sum over the 4 lane-slots q (lanes j, j+16, j+32, j+48), result in all of them.  gfx950's v_permlane16_swap /
 // v_permlane32_swap exchange 16- / 32-lane rows between two registers on the VALU: swapping a value with its own copy

@@ -70,7 +70,7 @@ __global__ void mono_pack_k(PackArgs a, float* __restrict__ pack) {
       }
       unsigned word = 0;
       for (int pl = 0; pl <= plane; ++pl) {
-        asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(word) : "v"(x[0]), "v"(x[1]));
+        word = cvt_pk_bf16(x[0], x[1]);
         x[0] -= __uint_as_float(word << 16);
         x[1] -= __uint_as_float(word & 0xffff0000u);
       }
@@ -94,7 +94,7 @@ __global__ void mono_pack_k(PackArgs a, float* __restrict__ pack) {
       }
       unsigned word = 0;
       for (int pl = 0; pl <= plane; ++pl) {           // hi, then the rounded remainders (exact subtractions)
-        asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(word) : "v"(x[0]), "v"(x[1]));
+        word = cvt_pk_bf16(x[0], x[1]);
         x[0] -= __uint_as_float(word << 16);
         x[1] -= __uint_as_float(word & 0xffff0000u);
       }
@@ -357,39 +357,17 @@ __device__ __forceinline__ void eval2x(const float* wp, const MonoLayout& L, con
 // accumulator and the five small terms in another.  72 MFMAs of 17 cycles per layer and node pair instead of 72 of 32.5, and
 // VALU work next to bf16 MFMAs is not serialised the way it is next to fp32 MFMAs (profiles/r06_mfma_k16_rate.txt).  The
 // peeled units, layer 1, the last layer and the quadrature are the fp32 code of eval2x.
-typedef unsigned u32x4n __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2n __attribute__((ext_vector_type(2)));
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8n;
-typedef __attribute__((ext_vector_type(4))) short s16x4n;
-typedef float f32x2n __attribute__((ext_vector_type(2)));
-// (v_cvt_pk_bf16_f32 through the conversion builtin, NOT inline asm: the results feed MFMAs a few instructions later, and the
-// compiler's hazard recognizer inserts the VALU-write -> MFMA-read wait states only for instructions it can see.  With the asm
-// form this kernel read stale operands: errors of 1e-2 .. 1 that moved with every rebuild)
-typedef __bf16 bf16x2n __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned cvt_pk_bf16n(float a, float b) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2n{a, b}, bf16x2n));
-}
-__device__ __forceinline__ void split3_pairn(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-  h = cvt_pk_bf16n(x0, x1);
-  const f32x2n r = f32x2n{x0, x1} - f32x2n{__uint_as_float(h << 16), __uint_as_float(h & 0xffff0000u)};   // exact
-  m = cvt_pk_bf16n(r[0], r[1]);
-  const f32x2n q = r - f32x2n{__uint_as_float(m << 16), __uint_as_float(m & 0xffff0000u)};                // exact
-  l = cvt_pk_bf16n(q[0], q[1]);
-}
 // the lane's 12 values of one node (tiles 0..2 of a 48-unit layer) -> B operands: K = 32 (tiles 0, 1) and K = 16 (tile 2), 3 planes
-__device__ __forceinline__ void split_acts48(const f32x4 (&a)[3], u32x4n (&b32)[3], u32x2n (&b16)[3]) {
+__device__ __forceinline__ void split_acts48(const f32x4 (&a)[3], u32x4 (&b32)[3], u32x2 (&b16)[3]) {
   unsigned h[6], m[6], l[6];
 #pragma unroll
   for (int t = 0; t < 3; ++t) {
-    split3_pairn(a[t][0], a[t][1], h[2 * t], m[2 * t], l[2 * t]);
-    split3_pairn(a[t][2], a[t][3], h[2 * t + 1], m[2 * t + 1], l[2 * t + 1]);
+    split3_pair(a[t][0], a[t][1], h[2 * t], m[2 * t], l[2 * t]);
+    split3_pair(a[t][2], a[t][3], h[2 * t + 1], m[2 * t + 1], l[2 * t + 1]);
   }
-  b32[0] = u32x4n{h[0], h[1], h[2], h[3]}; b16[0] = u32x2n{h[4], h[5]};
-  b32[1] = u32x4n{m[0], m[1], m[2], m[3]}; b16[1] = u32x2n{m[4], m[5]};
-  b32[2] = u32x4n{l[0], l[1], l[2], l[3]}; b16[2] = u32x2n{l[4], l[5]};
-}
-__device__ __forceinline__ f32x4 mfma_bf32(const u32x4n& a, const u32x4n& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8n, a), __builtin_bit_cast(bf16x8n, b), c, 0, 0, 0);
+  b32[0] = u32x4{h[0], h[1], h[2], h[3]}; b16[0] = u32x2{h[4], h[5]};
+  b32[1] = u32x4{m[0], m[1], m[2], m[3]}; b16[1] = u32x2{m[4], m[5]};
+  b32[2] = u32x4{l[0], l[1], l[2], l[3]}; b16[2] = u32x2{l[4], l[5]};
 }
 // The 16-wide remainder of the contraction (tile 2) ALSO goes through the K = 32 instruction, upper half zero.  The legacy
 // v_mfma_f32_16x16x16_bf16 takes the same 17 cycles on gfx950 (profiles/r06_mfma_k16_rate.txt), so nothing is lost -- and with
@@ -397,27 +375,27 @@ __device__ __forceinline__ f32x4 mfma_bf32(const u32x4n& a, const u32x4n& b, f32
 // operand planes verified bit-identical by device printf).  Cause NOT isolated: the instruction alone and the two forms
 // chained on one accumulator are correct in stand-alone kernels (tools/mfma_chain_check.hip).  The K = 32 form is correct in
 // every build of this kernel; tests/test_gpu_mono_split.py::test_narrow_* pin it against fp64.
-__device__ __forceinline__ f32x4 mfma_bf16k(const u32x2n& a, const u32x2n& b, f32x4 c) {
-  return mfma_bf32(u32x4n{a[0], a[1], 0u, 0u}, u32x4n{b[0], b[1], 0u, 0u}, c);
+__device__ __forceinline__ f32x4 mfma_bf16k(const u32x2& a, const u32x2& b, f32x4 c) {
+  return mfma_bf16(u32x4{a[0], a[1], 0u, 0u}, u32x4{b[0], b[1], 0u, 0u}, c);
 }
 // out[mt] (+)= W_main[16 mt + ., :48] x acts for two nodes; big: hi hi, sml: the five small terms.  Q: the matrix' planes (LDS)
 // (ONE: a single accumulator class -- the backward kernel, whose registers are full: the same error level as the fp32 MFMA)
 template <bool ONE = false>
-__device__ __forceinline__ void block48_split(const unsigned* Q, int lane, const u32x4n (&b32)[2][3], const u32x2n (&b16)[2][3],
+__device__ __forceinline__ void block48_split(const unsigned* Q, int lane, const u32x4 (&b32)[2][3], const u32x2 (&b16)[2][3],
                                               f32x4 (&big)[2][3], f32x4 (&sml)[2][3]) {
 #pragma unroll
   for (int mt = 0; mt < 3; ++mt) {
-    u32x4n A32[3];
-    u32x2n A16[3];
+    u32x4 A32[3];
+    u32x2 A16[3];
 #pragma unroll
     for (int p = 0; p < 3; ++p) {
-      A32[p] = *reinterpret_cast<const u32x4n*>(Q + (p * 3 + mt) * 384 + 4 * lane);
-      A16[p] = *reinterpret_cast<const u32x2n*>(Q + (p * 3 + mt) * 384 + 256 + 2 * lane);
+      A32[p] = *reinterpret_cast<const u32x4*>(Q + (p * 3 + mt) * 384 + 4 * lane);
+      A16[p] = *reinterpret_cast<const u32x2*>(Q + (p * 3 + mt) * 384 + 256 + 2 * lane);
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       auto term = [&](int pa, int pb, f32x4& c) {
-        c = mfma_bf32(A32[pa], b32[u][pb], c);
+        c = mfma_bf16(A32[pa], b32[u][pb], c);
         c = mfma_bf16k(A16[pa], b16[u][pb], c);
       };
       f32x4& cs = ONE ? big[u][mt] : sml[u][mt];
@@ -453,8 +431,8 @@ __device__ __forceinline__ void eval2x_split(const float* wp, const unsigned* wq
   }
   for (int l = 1; l < L.NH; ++l) {
     const float* W = wp + L.o_W[l];
-    u32x4n b32[2][3];
-    u32x2n b16[2][3];
+    u32x4 b32[2][3];
+    u32x2 b16[2][3];
     split_acts48(a[0], b32[0], b16[0]);
     split_acts48(a[1], b32[1], b16[1]);
     f32x4 big[2][HM], sml[2][HM];
@@ -1855,8 +1833,8 @@ __global__ __launch_bounds__(64 * kWaves, 1) void mono_bwd_pair_x_k(MonoArgs a) 
         for (int mt = 0; mt < HM; ++mt) { o[0][mt] = ld4(Wbias + 16 * mt + 4 * q); o[1][mt] = o[0][mt]; }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (SP) {
-          u32x4n b32[2][3];
-          u32x2n b16[2][3];
+          u32x4 b32[2][3];
+          u32x2 b16[2][3];
           split_acts48(act[0], b32[0], b16[0]);
           split_acts48(act[1], b32[1], b16[1]);
           block48_split<true>(reinterpret_cast<const unsigned*>(sQ) + (l - 1) * kNarrowQ, lane, b32, b16, o, o);
@@ -1987,8 +1965,8 @@ __global__ __launch_bounds__(64 * kWaves, 1) void mono_bwd_pair_x_k(MonoArgs a) 
 #pragma unroll
         for (int mt = 0; mt < HM; ++mt) { da[0][mt] = z4; da[1][mt] = z4; }
         if constexpr (SP) {
-          u32x4n b32[2][3];
-          u32x2n b16[2][3];
+          u32x4 b32[2][3];
+          u32x2 b16[2][3];
           split_acts48(dp[0], b32[0], b16[0]);
           split_acts48(dp[1], b32[1], b16[1]);
           block48_split<true>(reinterpret_cast<const unsigned*>(sQ) + (NH - 1 + l - 1) * kNarrowQ, lane, b32, b16, da, da);
@@ -2266,6 +2244,59 @@ MonoLayout net_layout(const gnf_mono_net* net, int HT) {
   return L;
 }
 
+// The launches of launch_fwd whose kernels differ only in template arguments.  wlds: the weight image is LDS-resident (more
+// than the 64 KB a kernel may have by default: gnf_launch_lds); otherwise the WM = 0 instantiation, a plain launch.
+template <int EX>     // mono_inv_ks_x_k of a peeled net with EX leftover units
+int launch_inv_ks(const MonoArgs& a, int epg, int ks_waves, unsigned gq, size_t lds_k, hipStream_t s) {
+  const dim3 grid(gq), block(64 * ks_waves);
+  if (epg == 2) {
+    if (ks_waves <= 8) return (int)gnf_launch_lds(mono_inv_ks_x_k<3, EX, 2, 8>, grid, block, lds_k, s, a);
+    return (int)gnf_launch_lds(mono_inv_ks_x_k<3, EX, 2, kSplitWavesX>, grid, block, lds_k, s, a);
+  }
+  if (ks_waves <= 8) return (int)gnf_launch_lds(mono_inv_ks_x_k<3, EX, 4, 8>, grid, block, lds_k, s, a);
+  return (int)gnf_launch_lds(mono_inv_ks_x_k<3, EX, 4, kSplitWavesX>, grid, block, lds_k, s, a);
+}
+template <int EX, int EPG>
+int launch_inv_x(const MonoArgs& a, bool wlds, unsigned grid, int nw, size_t lds, hipStream_t s) {
+  if (wlds) return (int)gnf_launch_lds(mono_inv_split_x_k<3, EX, 1, EPG>, dim3(grid), dim3(64 * nw), lds, s, a);
+  hipLaunchKernelGGL((mono_inv_split_x_k<3, EX, 0, EPG>), dim3(grid), dim3(64 * nw), lds, s, a);
+  GNF_LAUNCH_CHECK();
+  return 0;
+}
+template <int HT, int EPG>
+int launch_inv_ht(const MonoArgs& a, bool wlds, unsigned grid, int nw, size_t lds, hipStream_t s) {
+  if (wlds) return (int)gnf_launch_lds(mono_inv_split_k<HT, 1, EPG>, dim3(grid), dim3(64 * nw), lds, s, a);
+  hipLaunchKernelGGL((mono_inv_split_k<HT, 0, EPG>), dim3(grid), dim3(64 * nw), lds, s, a);
+  GNF_LAUNCH_CHECK();
+  return 0;
+}
+template <int EPG>
+int launch_inv(const MonoArgs& a, bool wlds, unsigned grid, int nw, size_t lds, hipStream_t s) {
+  switch (a.L.HT) {
+    case 2: return launch_inv_ht<2, EPG>(a, wlds, grid, nw, lds, s);
+    case 4: return launch_inv_ht<4, EPG>(a, wlds, grid, nw, lds, s);
+    case 7: return launch_inv_ht<7, EPG>(a, wlds, grid, nw, lds, s);
+    case 10: return launch_inv_ht<10, EPG>(a, wlds, grid, nw, lds, s);
+    case 16: return launch_inv_ht<16, EPG>(a, wlds, grid, nw, lds, s);
+    default: return GNF_ESHAPE;
+  }
+}
+template <int EX, bool INV>
+int launch_fwd_x(const MonoArgs& a, bool wlds, unsigned grid, size_t lds, hipStream_t s) {
+  if (wlds) return (int)gnf_launch_lds(mono_fwd_x_k<3, EX, 1, INV>, dim3(grid), dim3(64 * kWaves), lds, s, a);
+  hipLaunchKernelGGL((mono_fwd_x_k<3, EX, 0, INV>), dim3(grid), dim3(64 * kWaves), 0, s, a);
+  GNF_LAUNCH_CHECK();
+  return 0;
+}
+template <int HT, bool INV>
+int launch_fwd_ht(const MonoArgs& a, bool wlds, bool swap, unsigned grid, size_t lds, size_t lds_one, hipStream_t s) {
+  if (wlds) return (int)gnf_launch_lds(mono_fwd_k<HT, 1, INV>, dim3(grid), dim3(64 * kWaves), lds, s, a);
+  if (swap) return (int)gnf_launch_lds(mono_fwd_k<HT, 2, INV>, dim3(grid), dim3(64 * kWaves), lds_one, s, a);
+  hipLaunchKernelGGL((mono_fwd_k<HT, 0, INV>), dim3(grid), dim3(64 * kWaves), 0, s, a);
+  GNF_LAUNCH_CHECK();
+  return 0;
+}
+
 template <bool INV>
 int launch_fwd(const MonoArgs& a, hipStream_t s) {
   const int HT = a.L.HT;
@@ -2288,94 +2319,28 @@ int launch_fwd(const MonoArgs& a, hipStream_t s) {
     if (a.L.EX > 0 && quarter && wlds && !one_pt && ks_waves <= kSplitWavesX && a.S <= 31) {   // (32 node slots per point)
       const size_t lds_k = lds + (size_t)(2 * 32 + 2 * 3 * 32 * epg + 2 * 3 * epg) * sizeof(float);
       const unsigned gq = (unsigned)((a.n + epg - 1) / epg);
-#define GNF_INVKS_W(EX_, EPG_, MW_)                                                                            \
-      {                                                                                                        \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_inv_ks_x_k<3, EX_, EPG_, MW_>),          \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_k);                     \
-        hipLaunchKernelGGL((mono_inv_ks_x_k<3, EX_, EPG_, MW_>), dim3(gq), dim3(64 * ks_waves), lds_k, s, a);  \
-      }
-#define GNF_INVKS(EX_, EPG_) { if (ks_waves <= 8) GNF_INVKS_W(EX_, EPG_, 8) else GNF_INVKS_W(EX_, EPG_, kSplitWavesX) }
-      if (a.L.EX <= 2) { if (epg == 2) GNF_INVKS(2, 2) else GNF_INVKS(2, 4) }
-      else { if (epg == 2) GNF_INVKS(3, 2) else GNF_INVKS(3, 4) }
-#undef GNF_INVKS
-#undef GNF_INVKS_W
-      GNF_LAUNCH_CHECK();
-      return 0;
+      return a.L.EX <= 2 ? launch_inv_ks<2>(a, epg, ks_waves, gq, lds_k, s) : launch_inv_ks<3>(a, epg, ks_waves, gq, lds_k, s);
     }
     if (a.L.EX > 0 && quarter) {
       const int nwq = (pairs + 3) / 4 < kSplitWavesX ? (pairs + 3) / 4 : kSplitWavesX;
       const size_t lds_q = (wlds ? lds : 0) + 2 * nwq * 16 * sizeof(float);
       const unsigned gq = (unsigned)((a.n + 3) / 4);
-#define GNF_INVXQ(EX_)                                                                                         \
-      if (wlds) {                                                                                              \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_inv_split_x_k<3, EX_, 1, 4>),            \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q);                     \
-        hipLaunchKernelGGL((mono_inv_split_x_k<3, EX_, 1, 4>), dim3(gq), dim3(64 * nwq), lds_q, s, a);         \
-      } else {                                                                                                 \
-        hipLaunchKernelGGL((mono_inv_split_x_k<3, EX_, 0, 4>), dim3(gq), dim3(64 * nwq), lds_q, s, a);         \
-      }
-      if (a.L.EX <= 2) { GNF_INVXQ(2) } else { GNF_INVXQ(3) }
-#undef GNF_INVXQ
-      GNF_LAUNCH_CHECK();
-      return 0;
+      return a.L.EX <= 2 ? launch_inv_x<2, 4>(a, wlds, gq, nwq, lds_q, s) : launch_inv_x<3, 4>(a, wlds, gq, nwq, lds_q, s);
     }
     if (a.L.EX > 0) {                                                 // peeled narrow net: up to 16 wavefronts per group
       const int nwx = pairs < kSplitWavesX ? pairs : kSplitWavesX;
       const size_t lds_x = (wlds ? lds : 0) + 2 * nwx * 16 * sizeof(float);
-#define GNF_INVX(EX_)                                                                                          \
-      if (wlds) {                                                                                              \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_inv_split_x_k<3, EX_, 1>),               \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_x);                     \
-        hipLaunchKernelGGL((mono_inv_split_x_k<3, EX_, 1>), dim3((unsigned)ngroups), dim3(64 * nwx), lds_x, s, a); \
-      } else {                                                                                                 \
-        hipLaunchKernelGGL((mono_inv_split_x_k<3, EX_, 0>), dim3((unsigned)ngroups), dim3(64 * nwx), lds_x, s, a); \
-      }
-      if (a.L.EX <= 2) { GNF_INVX(2) } else { GNF_INVX(3) }
-#undef GNF_INVX
-      GNF_LAUNCH_CHECK();
-      return 0;
+      return a.L.EX <= 2 ? launch_inv_x<2, 16>(a, wlds, (unsigned)ngroups, nwx, lds_x, s)
+                         : launch_inv_x<3, 16>(a, wlds, (unsigned)ngroups, nwx, lds_x, s);
     }
     if (quarter) {
       const int nwq = (pairs + 3) / 4 < kSplitWaves ? (pairs + 3) / 4 : kSplitWaves;
       const size_t lds_q = (wlds ? lds : 0) + 2 * nwq * 16 * sizeof(float);
-      const unsigned gq = (unsigned)((a.n + 3) / 4);
-#define GNF_INVQ_CASE(HT_)                                                                                     \
-  case HT_:                                                                                                   \
-    if (wlds) {                                                                                               \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_inv_split_k<HT_, 1, 4>),                  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q);                      \
-      hipLaunchKernelGGL((mono_inv_split_k<HT_, 1, 4>), dim3(gq), dim3(64 * nwq), lds_q, s, a);               \
-    } else {                                                                                                  \
-      hipLaunchKernelGGL((mono_inv_split_k<HT_, 0, 4>), dim3(gq), dim3(64 * nwq), lds_q, s, a);               \
-    }                                                                                                         \
-    break;
-      switch (HT) {
-        GNF_INVQ_CASE(2) GNF_INVQ_CASE(4) GNF_INVQ_CASE(7) GNF_INVQ_CASE(10) GNF_INVQ_CASE(16)
-        default: return GNF_ESHAPE;
-      }
-#undef GNF_INVQ_CASE
-      GNF_LAUNCH_CHECK();
-      return 0;
+      return launch_inv<4>(a, wlds, (unsigned)((a.n + 3) / 4), nwq, lds_q, s);
     }
     const int nw = pairs < kSplitWaves ? pairs : kSplitWaves;
     const size_t lds_split = (wlds ? lds : 0) + 2 * nw * 16 * sizeof(float);
-#define GNF_INV_CASE(HT_)                                                                                      \
-  case HT_:                                                                                                   \
-    if (wlds) {                                                                                               \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_inv_split_k<HT_, 1>),                     \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_split);                  \
-      hipLaunchKernelGGL((mono_inv_split_k<HT_, 1>), dim3((unsigned)ngroups), dim3(64 * nw), lds_split, s, a); \
-    } else {                                                                                                  \
-      hipLaunchKernelGGL((mono_inv_split_k<HT_, 0>), dim3((unsigned)ngroups), dim3(64 * nw), lds_split, s, a); \
-    }                                                                                                         \
-    break;
-    switch (HT) {
-      GNF_INV_CASE(2) GNF_INV_CASE(4) GNF_INV_CASE(7) GNF_INV_CASE(10) GNF_INV_CASE(16)
-      default: return GNF_ESHAPE;
-    }
-#undef GNF_INV_CASE
-    GNF_LAUNCH_CHECK();
-    return 0;
+    return launch_inv<16>(a, wlds, (unsigned)ngroups, nw, lds_split, s);
   }
   const int64_t per_cu = ((wlds && lds > (size_t)kLdsBudget / 2) || swap) ? 1 : 2;   // resident workgroups per CU
   if (grid > 256 * per_cu) grid = 256 * per_cu;                      // persistent
@@ -2384,58 +2349,28 @@ int launch_fwd(const MonoArgs& a, hipStream_t s) {
       const size_t lds_sp = lds + (size_t)(a.L.NH - 1) * kNarrowQ * 4;
       if (wlds && a.L.NH > 1 && !a.f32only && gnf_gemm_split_enabled() && lds_sp <= (size_t)kLdsBudget / 2) {
         g_fwd_kernel = "mono_fwd_x_k<split>";
-#define GNF_FWDXS(EX_)                                                                                         \
-        {                                                                                                      \
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_fwd_x_k<3, EX_, 1, false, true>),      \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sp);                  \
-          hipLaunchKernelGGL((mono_fwd_x_k<3, EX_, 1, false, true>), dim3((unsigned)grid), dim3(64 * kWaves), lds_sp, s, a); \
-        }
-        if (a.L.EX <= 2) GNF_FWDXS(2) else GNF_FWDXS(3)
-#undef GNF_FWDXS
-        GNF_LAUNCH_CHECK();
-        return 0;
+        const dim3 g((unsigned)grid), b(64 * kWaves);
+        return (int)(a.L.EX <= 2 ? gnf_launch_lds(mono_fwd_x_k<3, 2, 1, false, true>, g, b, lds_sp, s, a)
+                                 : gnf_launch_lds(mono_fwd_x_k<3, 3, 1, false, true>, g, b, lds_sp, s, a));
       }
     }
-#define GNF_FWDX(EX_)                                                                                          \
-    if (wlds) {                                                                                                \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_fwd_x_k<3, EX_, 1, INV>),                  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
-      hipLaunchKernelGGL((mono_fwd_x_k<3, EX_, 1, INV>), dim3((unsigned)grid), dim3(64 * kWaves), lds, s, a);  \
-    } else {                                                                                                   \
-      hipLaunchKernelGGL((mono_fwd_x_k<3, EX_, 0, INV>), dim3((unsigned)grid), dim3(64 * kWaves), 0, s, a);    \
-    }
-    if (a.L.EX <= 2) { GNF_FWDX(2) } else { GNF_FWDX(3) }
-#undef GNF_FWDX
-    GNF_LAUNCH_CHECK();
-    return 0;
+    return a.L.EX <= 2 ? launch_fwd_x<2, INV>(a, wlds, (unsigned)grid, lds, s) : launch_fwd_x<3, INV>(a, wlds, (unsigned)grid, lds, s);
   }
-#define GNF_FWD_CASE(HT_)                                                                                     \
-  case HT_:                                                                                                  \
-    if (wlds) {                                                                                              \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_fwd_k<HT_, 1, INV>),                     \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                             \
-      hipLaunchKernelGGL((mono_fwd_k<HT_, 1, INV>), dim3((unsigned)grid), dim3(64 * kWaves), lds, s, a);     \
-    } else if (swap) {                                                                                       \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_fwd_k<HT_, 2, INV>),                     \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_one);                         \
-      hipLaunchKernelGGL((mono_fwd_k<HT_, 2, INV>), dim3((unsigned)grid), dim3(64 * kWaves), lds_one, s, a); \
-    } else {                                                                                                 \
-      hipLaunchKernelGGL((mono_fwd_k<HT_, 0, INV>), dim3((unsigned)grid), dim3(64 * kWaves), 0, s, a);       \
-    }                                                                                                        \
-    break;
   switch (HT) {
-    GNF_FWD_CASE(2) GNF_FWD_CASE(4) GNF_FWD_CASE(7) GNF_FWD_CASE(10) GNF_FWD_CASE(16)
+    case 2: return launch_fwd_ht<2, INV>(a, wlds, swap, (unsigned)grid, lds, lds_one, s);
+    case 4: return launch_fwd_ht<4, INV>(a, wlds, swap, (unsigned)grid, lds, lds_one, s);
+    case 7: return launch_fwd_ht<7, INV>(a, wlds, swap, (unsigned)grid, lds, lds_one, s);
+    case 10: return launch_fwd_ht<10, INV>(a, wlds, swap, (unsigned)grid, lds, lds_one, s);
+    case 16: return launch_fwd_ht<16, INV>(a, wlds, swap, (unsigned)grid, lds, lds_one, s);
     default: return GNF_ESHAPE;
   }
-#undef GNF_FWD_CASE
-  GNF_LAUNCH_CHECK();
-  return 0;
 }
 
 template <int HT, int NH>
 int launch_bwd_one(const MonoArgs& a, unsigned grid, hipStream_t s) {
   const size_t lds_all = (size_t)a.L.total_floats * sizeof(float);
   const size_t lds_one = (size_t)a.L.HP * a.L.LDW * sizeof(float);
+  const dim3 g(grid), b(64 * kWaves);
   if constexpr (HT <= 4 && NH > 1) {
     if (a.indw == 2) {                          // two nodes per pass, image without W1h / W1h^T, 5 tiles per wavefront
       const size_t lds_pair = ((size_t)a.L.o_W1h + (size_t)(NH - 1) * (2 * a.L.HP * a.L.LDW + a.L.HP) +
@@ -2450,77 +2385,39 @@ int launch_bwd_one(const MonoArgs& a, unsigned grid, hipStream_t s) {
             const size_t lds_wcomb = (size_t)kWaves * (NH - 1) * a.L.HP * a.L.HP * sizeof(float);
             if (!a.f32only && gnf_gemm_split_enabled() && lds_sp <= (size_t)kLdsBudget && (!a.wcomb || lds_wcomb <= lds_sp)) {
               g_bwd_kernel = "mono_bwd_pair_x_k<split>";
-              if (a.L.EX <= 2) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_bwd_pair_x_k<3, NH, 2, kRP, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sp);
-                hipLaunchKernelGGL((mono_bwd_pair_x_k<3, NH, 2, kRP, true>), dim3(grid), dim3(64 * kWaves), lds_sp, s, a);
-              } else {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_bwd_pair_x_k<3, NH, 3, false, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sp);
-                hipLaunchKernelGGL((mono_bwd_pair_x_k<3, NH, 3, false, true>), dim3(grid), dim3(64 * kWaves), lds_sp, s, a);
-              }
-              GNF_LAUNCH_CHECK();
-              return 0;
+              if (a.L.EX <= 2) return (int)gnf_launch_lds(mono_bwd_pair_x_k<3, NH, 2, kRP, true>, g, b, lds_sp, s, a);
+              return (int)gnf_launch_lds(mono_bwd_pair_x_k<3, NH, 3, false, true>, g, b, lds_sp, s, a);
             }
           }
-          if (a.L.EX <= 2) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_bwd_pair_x_k<3, NH, 2, kRP>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pair);
-            hipLaunchKernelGGL((mono_bwd_pair_x_k<3, NH, 2, kRP>), dim3(grid), dim3(64 * kWaves), lds_pair, s, a);
-          } else {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_bwd_pair_x_k<3, NH, 3>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pair);
-            hipLaunchKernelGGL((mono_bwd_pair_x_k<3, NH, 3>), dim3(grid), dim3(64 * kWaves), lds_pair, s, a);
-          }
-          GNF_LAUNCH_CHECK();
-          return 0;
+          if (a.L.EX <= 2) return (int)gnf_launch_lds(mono_bwd_pair_x_k<3, NH, 2, kRP>, g, b, lds_pair, s, a);
+          return (int)gnf_launch_lds(mono_bwd_pair_x_k<3, NH, 3>, g, b, lds_pair, s, a);
         }
       }
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_bwd_pair_k<HT, NH>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pair);
-      hipLaunchKernelGGL((mono_bwd_pair_k<HT, NH>), dim3(grid), dim3(64 * kWaves), lds_pair, s, a);
-      GNF_LAUNCH_CHECK();
-      return 0;
+      return (int)gnf_launch_lds(mono_bwd_pair_k<HT, NH>, g, b, lds_pair, s, a);
     }
     if (a.indw) {                               // whole image + per-wavefront element-major tiles, one workgroup per CU
       const size_t lds_in = ((size_t)(a.L.total_floats + 3) / 4 * 4 + (size_t)kWaves * NH * 16 * kTS) * sizeof(float);
       if (lds_in > (size_t)kLdsBudget) return GNF_ESHAPE;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_bwd_k<HT, NH, 1, true, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_in);
-      hipLaunchKernelGGL((mono_bwd_k<HT, NH, 1, true, true>), dim3(grid), dim3(64 * kWaves), lds_in, s, a);
-      GNF_LAUNCH_CHECK();
-      return 0;
+      return (int)gnf_launch_lds(mono_bwd_k<HT, NH, 1, true, true>, g, b, lds_in, s, a);
     }
     if (a.ones) {                               // everything but the transposed hidden matrices resident, two workgroups per CU
       const size_t lds_res = (size_t)(a.L.fwd_floats + a.L.CP * a.L.LDW) * sizeof(float);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_bwd_k<HT, NH, 4, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_res);
-      hipLaunchKernelGGL((mono_bwd_k<HT, NH, 4, true>), dim3(grid), dim3(64 * kWaves), lds_res, s, a);
-      GNF_LAUNCH_CHECK();
-      return 0;
+      return (int)gnf_launch_lds(mono_bwd_k<HT, NH, 4, true>, g, b, lds_res, s, a);
     }
   }
   if constexpr (HT <= 4) {                      // whole image resident
     if (lds_all > (size_t)150 * 1024) return GNF_ESHAPE;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_bwd_k<HT, NH, 1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_all);
-    hipLaunchKernelGGL((mono_bwd_k<HT, NH, 1>), dim3(grid), dim3(64 * kWaves), lds_all, s, a);
+    return (int)gnf_launch_lds(mono_bwd_k<HT, NH, 1>, g, b, lds_all, s, a);
   } else if constexpr (HT <= 10) {
     const size_t lds_res = lds_one * (NH > 1 ? NH - 1 : 1);
-    if (NH > 1 && lds_res <= (size_t)150 * 1024) {          // all hidden->hidden matrices resident (H <= 112, 3 hidden layers)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_bwd_k<HT, NH, 3>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_res);
-      hipLaunchKernelGGL((mono_bwd_k<HT, NH, 3>), dim3(grid), dim3(64 * kWaves), lds_res, s, a);
-    } else {                                                 // one matrix at a time
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_bwd_k<HT, NH, 2>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_one);
-      hipLaunchKernelGGL((mono_bwd_k<HT, NH, 2>), dim3(grid), dim3(64 * kWaves), lds_one, s, a);
-    }
+    if (NH > 1 && lds_res <= (size_t)150 * 1024)            // all hidden->hidden matrices resident (H <= 112, 3 hidden layers)
+      return (int)gnf_launch_lds(mono_bwd_k<HT, NH, 3>, g, b, lds_res, s, a);
+    return (int)gnf_launch_lds(mono_bwd_k<HT, NH, 2>, g, b, lds_one, s, a);   // one matrix at a time
   } else {
-    hipLaunchKernelGGL((mono_bwd_k<HT, NH, 0>), dim3(grid), dim3(64 * kWaves), 0, s, a);
+    hipLaunchKernelGGL((mono_bwd_k<HT, NH, 0>), g, b, 0, s, a);
+    GNF_LAUNCH_CHECK();
+    return 0;
   }
-  GNF_LAUNCH_CHECK();
-  return 0;
 }
 
 template <int HT>

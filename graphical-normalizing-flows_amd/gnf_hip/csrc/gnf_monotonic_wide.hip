@@ -56,17 +56,7 @@ struct WidePlan {
 // A fragment of the pack through a buffer descriptor: descriptor and fragment offset (soff, bytes) in SGPRs, 16 lane
 // bytes in ONE VGPR -- no 64-bit per-lane addresses (flat loads reach +-4 KB by immediate, a matrix is 100 KB: hipcc
 // hoisted two dozen address pairs per matrix out of the node loop and spilled them)
-// Values the compiler must not recognise as loop-invariant: everything derived from them (fragment offsets, the small
-// vectors w1x / wL / b_l in LDS) would otherwise be hoisted out of the node loop and held in registers -- 80 VGPRs of
-// hoisted LDS reads and 200 SGPR offsets in the first build of this kernel, spilled in turn.
-__device__ __forceinline__ int opaque_v(int x) { asm volatile("" : "+v"(x)); return x; }
-__device__ __forceinline__ int opaque_s(int x) { asm volatile("" : "+s"(x)); return x; }
-// max(x, 0) as ONE v_max_f32: fmaxf() is compiled into a canonicalising v_max(x, x) plus the maximum (NaN quieting the
-// kernels do not need: a NaN pre-activation stays a NaN either way)
-__device__ __forceinline__ float relu1(float x) { float y; asm("v_max_f32 %0, 0, %1" : "=v"(y) : "v"(x)); return y; }
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
 __device__ __forceinline__ f32x4 ldfrag(rsrc_t rs, int voff, int soff) {
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0);
   return __builtin_bit_cast(f32x4, v);
 }
@@ -144,33 +134,14 @@ __device__ __forceinline__ void layer_pass(rsrc_t rs, int voff, int soff, int so
 // ---------------------------------------------------------------------------------------------------------------------
 // bf16 matrix pipe with exact 3 x bf16 operand splits (round 6; see mono_fwd_wide_split_k below for the method)
 // ---------------------------------------------------------------------------------------------------------------------
-typedef unsigned u32x4w __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2w __attribute__((ext_vector_type(2)));
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8w;
-
-__device__ __forceinline__ unsigned cvt_pk_bf16w(float a, float b) {
-  unsigned r; asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r;
-}
-typedef float f32x2w __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split3_pairw(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-  // the two remainders of a level as ONE packed subtraction (v_pk_add_f32): 9 instead of 11 instructions per pair
-  h = cvt_pk_bf16w(x0, x1);
-  const f32x2w r = f32x2w{x0, x1} - f32x2w{__uint_as_float(h << 16), __uint_as_float(h & 0xffff0000u)};   // exact
-  m = cvt_pk_bf16w(r[0], r[1]);
-  const f32x2w q = r - f32x2w{__uint_as_float(m << 16), __uint_as_float(m & 0xffff0000u)};                // exact
-  l = cvt_pk_bf16w(q[0], q[1]);
-}
-__device__ __forceinline__ u32x4w ldfragu(rsrc_t rs, int voff, int soff) {
+__device__ __forceinline__ u32x4 ldfragu(rsrc_t rs, int voff, int soff) {
   return __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0);
-}
-__device__ __forceinline__ f32x4 mfma_bf(const u32x4w& a, const u32x4w& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8w, a), __builtin_bit_cast(bf16x8w, b), c, 0, 0, 0);
 }
 
 // fragments (plane p, the wavefront's tiles, k tile t) of one matrix: full tile mi at soff + ((p HT + mi) KT + t) KB, the shared
 // tile at soffx + (p HT KT + t) KB
 template <int HT, int MF, int XT, int KT>
-__device__ __forceinline__ void fragp_load(rsrc_t rs, int voff, int soff, int soffx, int p, int t, u32x4w (&A)[MF + XT]) {
+__device__ __forceinline__ void fragp_load(rsrc_t rs, int voff, int soff, int soffx, int p, int t, u32x4 (&A)[MF + XT]) {
 #pragma unroll
   for (int mi = 0; mi < MF; ++mi) A[mi] = ldfragu(rs, voff, soff + ((p * HT + mi) * KT + t) * 1024);
   if constexpr (XT) A[MF] = ldfragu(rs, voff, soffx + (p * HT * KT + t) * 1024);
@@ -185,9 +156,9 @@ __device__ __forceinline__ void fragp_load(rsrc_t rs, int voff, int soff, int so
 //   bsrc: LDS address (floats) of (pair (slot 0, element j), position 8 q); slot 1 adds 32 P; k tile t adds 32
 template <int HT, int MF, int XT, int KT, int P>
 __device__ __forceinline__ void layer_pass_split32(rsrc_t rs, int voff, int soff, int soffx, const float* bsrc, const float* bsrcx,
-                                                   u32x4w (&A)[3][MF + XT], f32x4 (&acc)[MF + XT][2]) {
+                                                   u32x4 (&A)[3][MF + XT], f32x4 (&acc)[MF + XT][2]) {
   constexpr int HP = 16 * HT;
-  u32x4w B[3][2 + XT];
+  u32x4 B[3][2 + XT];
   const int qv = (int)(threadIdx.x & 63) >> 4;
   auto loadB = [&](int t) {
 #pragma unroll
@@ -198,21 +169,21 @@ __device__ __forceinline__ void layer_pass_split32(rsrc_t rs, int voff, int soff
         if (32 * t + 8 * qv >= HP) { lo = f32x4{0.f, 0.f, 0.f, 0.f}; hi = lo; }
       }
       unsigned h[4], m[4], l[4];
-      split3_pairw(lo[0], lo[1], h[0], m[0], l[0]);
-      split3_pairw(lo[2], lo[3], h[1], m[1], l[1]);
-      split3_pairw(hi[0], hi[1], h[2], m[2], l[2]);
-      split3_pairw(hi[2], hi[3], h[3], m[3], l[3]);
-      B[0][sl] = u32x4w{h[0], h[1], h[2], h[3]};
-      B[1][sl] = u32x4w{m[0], m[1], m[2], m[3]};
-      B[2][sl] = u32x4w{l[0], l[1], l[2], l[3]};
+      split3_pair(lo[0], lo[1], h[0], m[0], l[0]);
+      split3_pair(lo[2], lo[3], h[1], m[1], l[1]);
+      split3_pair(hi[0], hi[1], h[2], m[2], l[2]);
+      split3_pair(hi[2], hi[3], h[3], m[3], l[3]);
+      B[0][sl] = u32x4{h[0], h[1], h[2], h[3]};
+      B[1][sl] = u32x4{m[0], m[1], m[2], m[3]};
+      B[2][sl] = u32x4{l[0], l[1], l[2], l[3]};
     }
   };
   auto prod = [&](int pa, int pb) {
 #pragma unroll
     for (int mi = 0; mi < MF; ++mi)
 #pragma unroll
-      for (int sl = 0; sl < 2; ++sl) acc[mi][sl] = mfma_bf(A[pa][mi], B[pb][sl], acc[mi][sl]);
-    if constexpr (XT) acc[MF][0] = mfma_bf(A[pa][MF], B[pb][2], acc[MF][0]);
+      for (int sl = 0; sl < 2; ++sl) acc[mi][sl] = mfma_bf16(A[pa][mi], B[pb][sl], acc[mi][sl]);
+    if constexpr (XT) acc[MF][0] = mfma_bf16(A[pa][MF], B[pb][2], acc[MF][0]);
   };
   // Only the lo plane of k tile 0 was requested ahead of the serial section (A[2]; 20 registers live across it instead of
   // 60: with all three the chain role spilled 100 registers and wrote 12 GB of scratch per cfg5 launch); mid and hi follow
@@ -545,7 +516,7 @@ __global__ __launch_bounds__(64 * kWideWaves, 1) void mono_bwd_wide_k(MonoArgs a
   // =======================================================================================================================
   const int mh = wave & 1, nh = wave >> 1;
   const int m0 = mh * (MF + XT);
-  const rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.pack), 0, L.pack_floats * 4, 0x00020000);
+  const rsrc_t rs = make_rsrc(a.pack, L.pack_floats * 4);
   const int prow = (16 * nh + j) * P;                 // slot 0 row of this lane's element (slot 1: + 32 P)
   const int xrow = prow + mh * kGE * P;               // row of the shared tile's slot
   const int ucol_c = 16 * m0 + 4 * q;                 // own unit column of the first full tile (tile mi adds 16)
@@ -617,7 +588,7 @@ __global__ __launch_bounds__(64 * kWideWaves, 1) void mono_bwd_wide_k(MonoArgs a
     bool isj[2];
     f32x4 acc[MT][2];                                 // layer-1 input -> pre-activation -> activation -> dpre of (own units, own pairs)
     f32x4 Apre[SPLIT ? 1 : MT];                       // first weight fragments of the next pass
-    u32x4w Asp[SPLIT ? 3 : 1][MT];                    // ... and, split form, the fragment registers themselves
+    u32x4 Asp[SPLIT ? 3 : 1][MT];                     // ... and, split form, the fragment registers themselves
     constexpr int KT = (HP + 31) / 32;
     // request the first fragments of a pass over matrix `om` (fp32: o_Wf / o_WTf, split: o_Wp / o_WTp of the same layer)
     auto prefetch = [&](int of32, int osp) {
@@ -903,7 +874,7 @@ __global__ __launch_bounds__(64 * kWaves, 2) void mono_fwd_wide_k(MonoArgs a) {
 
   const int mh = wave & 1, nh = wave >> 1;            // as in the backward's chain role
   const int m0 = mh * (MF + XT);
-  const rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.pack), 0, L.pack_floats * 4, 0x00020000);
+  const rsrc_t rs = make_rsrc(a.pack, L.pack_floats * 4);
   const int prow = (16 * nh + j) * P, xrow = prow + mh * kGE * P;
   const int ucol_c = 16 * m0 + 4 * q, xcol_c = 16 * MF + 4 * q;
   auto col = [&](int mi, int uc, int xc) { return mi < MF ? uc + 16 * mi : xc; };
@@ -1103,15 +1074,15 @@ struct WidePlanS {
 // 32 PB, plane p adds PLANE, k tile t adds 64;  bsrcx: the same for the shared tile's slot.
 template <int HT, int MF, int XT, int KT, int PB, int PLANE>
 __device__ __forceinline__ void layer_pass_split(rsrc_t rs, int voff, int soff, int soffx, const unsigned char* bsrc,
-                                                 const unsigned char* bsrcx, u32x4w (&A)[3][MF + XT],
+                                                 const unsigned char* bsrcx, u32x4 (&A)[3][MF + XT],
                                                  f32x4 (&acc)[MF + XT][2][2]) {
-  u32x4w B[3][2 + XT];
+  u32x4 B[3][2 + XT];
   auto loadB = [&](int t) {
 #pragma unroll
     for (int p = 0; p < 3; ++p) {
 #pragma unroll
-      for (int sl = 0; sl < 2; ++sl) B[p][sl] = *reinterpret_cast<const u32x4w*>(bsrc + p * PLANE + sl * kGE * PB + 64 * t);
-      if constexpr (XT) B[p][2] = *reinterpret_cast<const u32x4w*>(bsrcx + p * PLANE + 64 * t);
+      for (int sl = 0; sl < 2; ++sl) B[p][sl] = *reinterpret_cast<const u32x4*>(bsrc + p * PLANE + sl * kGE * PB + 64 * t);
+      if constexpr (XT) B[p][2] = *reinterpret_cast<const u32x4*>(bsrcx + p * PLANE + 64 * t);
     }
   };
   // products of (A plane pa) x (B plane pb) for every tile of the wavefront, into class cl
@@ -1119,8 +1090,8 @@ __device__ __forceinline__ void layer_pass_split(rsrc_t rs, int voff, int soff, 
 #pragma unroll
     for (int mi = 0; mi < MF; ++mi)
 #pragma unroll
-      for (int sl = 0; sl < 2; ++sl) acc[mi][sl][cl] = mfma_bf(A[pa][mi], B[pb][sl], acc[mi][sl][cl]);
-    if constexpr (XT) acc[MF][0][cl] = mfma_bf(A[pa][MF], B[pb][2], acc[MF][0][cl]);
+      for (int sl = 0; sl < 2; ++sl) acc[mi][sl][cl] = mfma_bf16(A[pa][mi], B[pb][sl], acc[mi][sl][cl]);
+    if constexpr (XT) acc[MF][0][cl] = mfma_bf16(A[pa][MF], B[pb][2], acc[MF][0][cl]);
   };
   loadB(0);
 #pragma unroll
@@ -1169,7 +1140,7 @@ __global__ __launch_bounds__(64 * kWaves, 2) void mono_fwd_wide_split_k(MonoArgs
 
   const int mh = wave & 1, nh = wave >> 1;
   const int m0 = mh * (MF + XT);
-  const rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.pack), 0, L.pack_floats * 4, 0x00020000);
+  const rsrc_t rs = make_rsrc(a.pack, L.pack_floats * 4);
   const int prow = (16 * nh + j) * PB, xrow = prow + mh * kGE * PB;       // bytes
   // 16-byte slots of a row are swapped in pairs for rows 4..7, 12..15 (slot ^= (row >> 2) & 1): the plane stores are
   // ds_write_b64 of 16 rows at one column -- 4-way bank conflicts at any 16-byte-aligned pitch, 2-way (their floor: the 16
@@ -1222,7 +1193,7 @@ __global__ __launch_bounds__(64 * kWaves, 2) void mono_fwd_wide_split_k(MonoArgs
     bool isj[2];
     f32x4 acc[MT][2][2];                                // [tile][node slot][class: hi hi | small terms]
     f32x4 val[MT][2];                                   // the layer's outputs after the ReLU
-    u32x4w Apre[3][MT];
+    u32x4 Apre[3][MT];
     auto node_params = [&](int k0) {
 #pragma unroll
       for (int sl = 0; sl < 2; ++sl) {
@@ -1252,12 +1223,12 @@ __global__ __launch_bounds__(64 * kWaves, 2) void mono_fwd_wide_split_k(MonoArgs
 #pragma unroll
         for (int sl = 0; sl < (mi < MF ? 2 : 1); ++sl) {
           unsigned h0_, m0_, l0_, h1_, m1_, l1_;
-          split3_pairw(val[mi][sl][0], val[mi][sl][1], h0_, m0_, l0_);
-          split3_pairw(val[mi][sl][2], val[mi][sl][3], h1_, m1_, l1_);
+          split3_pair_asm(val[mi][sl][0], val[mi][sl][1], h0_, m0_, l0_);      // stored to LDS: see gnf_common.h
+          split3_pair_asm(val[mi][sl][2], val[mi][sl][3], h1_, m1_, l1_);
           unsigned char* dst = planes + (mi < MF ? prow + sl * kGE * PB : xrow) + 32 * (mi < MF ? m0 + mi : MF) + opaque_v(wr8);
-          *reinterpret_cast<u32x2w*>(dst) = u32x2w{h0_, h1_};
-          *reinterpret_cast<u32x2w*>(dst + PLANE) = u32x2w{m0_, m1_};
-          *reinterpret_cast<u32x2w*>(dst + 2 * PLANE) = u32x2w{l0_, l1_};
+          *reinterpret_cast<u32x2*>(dst) = u32x2{h0_, h1_};
+          *reinterpret_cast<u32x2*>(dst + PLANE) = u32x2{m0_, m1_};
+          *reinterpret_cast<u32x2*>(dst + 2 * PLANE) = u32x2{l0_, l1_};
         }
     };
     auto prefetch = [&](int l) {
@@ -1351,11 +1322,7 @@ int launch_wide_fwd_split(const MonoArgs& a, hipStream_t s) {
   const size_t lds = (size_t)WidePlanS<HT, NH>::total_bytes;
   const int64_t groups = (a.n + kGE - 1) / kGE;
   const unsigned grid = (unsigned)(groups < 512 ? groups : 512);        // persistent, two workgroups per CU
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_fwd_wide_split_k<HT, NH>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((mono_fwd_wide_split_k<HT, NH>), dim3(grid), dim3(64 * kWaves), lds, s, a);
-  GNF_LAUNCH_CHECK();
-  return 0;
+  return (int)gnf_launch_lds(mono_fwd_wide_split_k<HT, NH>, dim3(grid), dim3(64 * kWaves), lds, s, a);
 }
 
 template <int HT, int NH>
@@ -1364,21 +1331,13 @@ int launch_wide_fwd(const MonoArgs& a, hipStream_t s) {
   const int64_t groups = (a.n + kGE - 1) / kGE;
   const int per_cu = lds * 3 <= (size_t)160 * 1024 ? 3 : 2;          // workgroups per CU (140 registers: up to 3 per SIMD)
   const unsigned grid = (unsigned)(groups < 256 * per_cu ? groups : 256 * per_cu);   // persistent
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_fwd_wide_k<HT, NH>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((mono_fwd_wide_k<HT, NH>), dim3(grid), dim3(64 * kWaves), lds, s, a);
-  GNF_LAUNCH_CHECK();
-  return 0;
+  return (int)gnf_launch_lds(mono_fwd_wide_k<HT, NH>, dim3(grid), dim3(64 * kWaves), lds, s, a);
 }
 
 template <int HT, int NH, bool SPLIT>
 int launch_wide(const MonoArgs& a, unsigned grid, hipStream_t s) {
   const size_t lds = (size_t)WidePlan<HT, NH>::total * sizeof(float);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mono_bwd_wide_k<HT, NH, SPLIT>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((mono_bwd_wide_k<HT, NH, SPLIT>), dim3(grid), dim3(64 * kWideWaves), lds, s, a);
-  GNF_LAUNCH_CHECK();
-  return 0;
+  return (int)gnf_launch_lds(mono_bwd_wide_k<HT, NH, SPLIT>, dim3(grid), dim3(64 * kWideWaves), lds, s, a);
 }
 
 constexpr size_t kLds = 160 * 1024;

@@ -5,8 +5,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // 8 independent accumulator chains of v_mfma_f32_16x16x4_f32 per wavefront, nothing else in the loop:
 // the sustained rate of this kernel is the practical fp32 matrix ceiling of the chip at its running clock.
 __global__ __launch_bounds__(512) void probe_mfma_k(float* out, int iters) {

@@ -230,7 +230,6 @@ __global__ __launch_bounds__(kBlock) void affine_bwd_elem_k(const float* __restr
 // span of RW d <= 256 floats: every lane moves ONE float4 of x / z and TWO of h (the row-per-lane-group kernels above
 // move 4 B and 8 B per lane and reach 46-48 % of the HBM peak where a float4 copy reaches 70 %); U spans are in flight
 // per wavefront.  The row sums of the log-Jacobian are RW masked wave reductions in a fixed order (deterministic).
-typedef float f32x4r __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -250,7 +249,7 @@ __global__ __launch_bounds__(kBlock) void affine_fwd_flat_k(const float* __restr
 #pragma unroll
   for (int c = 0; c < 4; ++c) rid[c] = (4 * lane + c) / d;
   for (int64_t sp0 = gw * U; sp0 < nspan; sp0 += nw * U) {
-    f32x4r xv[U], ha[U], hb[U];
+    f32x4 xv[U], ha[U], hb[U];
     int ne[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -259,9 +258,9 @@ __global__ __launch_bounds__(kBlock) void affine_fwd_flat_k(const float* __restr
       ne[u] = nrows * d;
       const int64_t base = row0 * d + 4 * lane;
       if (4 * lane + 3 < ne[u]) {
-        xv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4r*>(x + base));
-        ha[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4r*>(h + 2 * base));
-        hb[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4r*>(h + 2 * base + 4));
+        xv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x + base));
+        ha[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(h + 2 * base));
+        hb[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(h + 2 * base + 4));
       } else {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -277,7 +276,7 @@ __global__ __launch_bounds__(kBlock) void affine_fwd_flat_k(const float* __restr
       if (ne[u] == 0) continue;
       const int64_t row0 = (sp0 + u) * RW, base = row0 * d + 4 * lane;
       const float h0[4] = {ha[u][0], ha[u][2], hb[u][0], hb[u][2]}, h1[4] = {ha[u][1], ha[u][3], hb[u][1], hb[u][3]};
-      f32x4r zv, jv;
+      f32x4 zv, jv;
       float ls[4], lq[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
@@ -290,8 +289,8 @@ __global__ __launch_bounds__(kBlock) void affine_fwd_flat_k(const float* __restr
         if (4 * lane + c >= ne[u]) { ls[c] = 0.f; lq[c] = 0.f; }
       }
       if (4 * lane + 3 < ne[u]) {
-        __builtin_nontemporal_store(zv, reinterpret_cast<f32x4r*>(z + base));
-        if (jac) __builtin_nontemporal_store(jv, reinterpret_cast<f32x4r*>(jac + base));
+        __builtin_nontemporal_store(zv, reinterpret_cast<f32x4*>(z + base));
+        if (jac) __builtin_nontemporal_store(jv, reinterpret_cast<f32x4*>(jac + base));
       } else {
 #pragma unroll
         for (int c = 0; c < 4; ++c)
@@ -334,7 +333,7 @@ __global__ __launch_bounds__(kBlock) void affine_bwd_flat_k(const float* __restr
 #pragma unroll
   for (int c = 0; c < 4; ++c) rid[c] = (4 * lane + c) / d;
   for (int64_t sp0 = gw * U; sp0 < nspan; sp0 += nw * U) {
-    f32x4r xv[U], ha[U], hb[U], gv[U], jv[U];
+    f32x4 xv[U], ha[U], hb[U], gv[U], jv[U];
     int ne[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -342,14 +341,14 @@ __global__ __launch_bounds__(kBlock) void affine_bwd_flat_k(const float* __restr
       const int nrows = sp < nspan ? (int)(B - row0 < RW ? B - row0 : RW) : 0;
       ne[u] = nrows * d;
       const int64_t base = row0 * d + 4 * lane;
-      gv[u] = f32x4r{0.f, 0.f, 0.f, 0.f};
+      gv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
       jv[u] = gv[u];
       if (4 * lane + 3 < ne[u]) {
-        xv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4r*>(x + base));
-        ha[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4r*>(h + 2 * base));
-        hb[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4r*>(h + 2 * base + 4));
-        if (gz) gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4r*>(gz + base));
-        if (gjac) jv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4r*>(gjac + base));
+        xv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x + base));
+        ha[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(h + 2 * base));
+        hb[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(h + 2 * base + 4));
+        if (gz) gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(gz + base));
+        if (gjac) jv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(gjac + base));
       } else {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -367,7 +366,7 @@ __global__ __launch_bounds__(kBlock) void affine_bwd_flat_k(const float* __restr
       if (ne[u] == 0) continue;
       const int64_t row0 = (sp0 + u) * RW, base = row0 * d + 4 * lane;
       const float h0[4] = {ha[u][0], ha[u][2], hb[u][0], hb[u][2]}, h1[4] = {ha[u][1], ha[u][3], hb[u][1], hb[u][3]};
-      f32x4r ox, oa, ob;
+      f32x4 ox, oa, ob;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const bool ok = 4 * lane + c < ne[u];
@@ -383,9 +382,9 @@ __global__ __launch_bounds__(kBlock) void affine_bwd_flat_k(const float* __restr
         if (c < 2) { oa[2 * c] = o0; oa[2 * c + 1] = o1; } else { ob[2 * c - 4] = o0; ob[2 * c - 3] = o1; }
       }
       if (4 * lane + 3 < ne[u]) {
-        if (gx) __builtin_nontemporal_store(ox, reinterpret_cast<f32x4r*>(gx + base));
-        __builtin_nontemporal_store(oa, reinterpret_cast<f32x4r*>(gh + 2 * base));
-        __builtin_nontemporal_store(ob, reinterpret_cast<f32x4r*>(gh + 2 * base + 4));
+        if (gx) __builtin_nontemporal_store(ox, reinterpret_cast<f32x4*>(gx + base));
+        __builtin_nontemporal_store(oa, reinterpret_cast<f32x4*>(gh + 2 * base));
+        __builtin_nontemporal_store(ob, reinterpret_cast<f32x4*>(gh + 2 * base + 4));
       } else {
 #pragma unroll
         for (int c = 0; c < 4; ++c)
@@ -508,7 +507,7 @@ __global__ __launch_bounds__(kBlock) void nll_rows_flat_k(const float* __restric
 #pragma unroll
   for (int c = 0; c < 4; ++c) rid[c] = (4 * lane + c) / d;
   for (int64_t sp0 = gw * U; sp0 < nspan; sp0 += nw * U) {
-    f32x4r zv[U], jv[U];
+    f32x4 zv[U], jv[U];
     int ne[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -516,11 +515,11 @@ __global__ __launch_bounds__(kBlock) void nll_rows_flat_k(const float* __restric
       const int nrows = sp < nspan ? (int)(B - row0 < RW ? B - row0 : RW) : 0;
       ne[u] = nrows * d;
       const int64_t base = row0 * d + 4 * lane;
-      zv[u] = f32x4r{0.f, 0.f, 0.f, 0.f};
-      jv[u] = f32x4r{1.f, 1.f, 1.f, 1.f};
+      zv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+      jv[u] = f32x4{1.f, 1.f, 1.f, 1.f};
       if (4 * lane + 3 < ne[u]) {
-        if (logn) zv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4r*>(z + base));
-        if (jac) jv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4r*>(jac + base));
+        if (logn) zv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(z + base));
+        if (jac) jv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(jac + base));
       } else {
 #pragma unroll
         for (int c = 0; c < 4; ++c)
@@ -575,7 +574,7 @@ __global__ __launch_bounds__(kBlock) void nll_rows_bwd_flat_k(const float* __res
 #pragma unroll
   for (int c = 0; c < 4; ++c) rid[c] = (4 * lane + c) / d;
   for (int64_t sp0 = gw * U; sp0 < nspan; sp0 += nw * U) {
-    f32x4r zv[U], jv[U], gv[U];
+    f32x4 zv[U], jv[U], gv[U];
     int ne[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -583,13 +582,13 @@ __global__ __launch_bounds__(kBlock) void nll_rows_bwd_flat_k(const float* __res
       const int nrows = sp < nspan ? (int)(B - row0 < RW ? B - row0 : RW) : 0;
       ne[u] = nrows * d;
       const int64_t base = row0 * d + 4 * lane;
-      zv[u] = f32x4r{0.f, 0.f, 0.f, 0.f};
+      zv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
       gv[u] = zv[u];
-      jv[u] = f32x4r{1.f, 1.f, 1.f, 1.f};
+      jv[u] = f32x4{1.f, 1.f, 1.f, 1.f};
       if (4 * lane + 3 < ne[u]) {
-        if (gz) zv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4r*>(z + base));
-        if (gz_in) gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4r*>(gz_in + base));
-        if (gjac) jv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4r*>(jac + base));
+        if (gz) zv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(z + base));
+        if (gz_in) gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(gz_in + base));
+        if (gjac) jv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(jac + base));
       } else {
 #pragma unroll
         for (int c = 0; c < 4; ++c)
@@ -604,7 +603,7 @@ __global__ __launch_bounds__(kBlock) void nll_rows_bwd_flat_k(const float* __res
     for (int u = 0; u < U; ++u) {
       if (ne[u] == 0) continue;
       const int64_t row0 = (sp0 + u) * RW, base = row0 * d + 4 * lane;
-      f32x4r oz, oj;
+      f32x4 oz, oj;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const bool ok = 4 * lane + c < ne[u];
@@ -613,8 +612,8 @@ __global__ __launch_bounds__(kBlock) void nll_rows_bwd_flat_k(const float* __res
         oj[c] = gl / jv[u][c];
       }
       if (4 * lane + 3 < ne[u]) {
-        if (gz) __builtin_nontemporal_store(oz, reinterpret_cast<f32x4r*>(gz + base));
-        if (gjac) __builtin_nontemporal_store(oj, reinterpret_cast<f32x4r*>(gjac + base));
+        if (gz) __builtin_nontemporal_store(oz, reinterpret_cast<f32x4*>(gz + base));
+        if (gjac) __builtin_nontemporal_store(oj, reinterpret_cast<f32x4*>(gjac + base));
       } else {
 #pragma unroll
         for (int c = 0; c < 4; ++c)
@@ -630,7 +629,6 @@ __global__ __launch_bounds__(kBlock) void nll_rows_bwd_flat_k(const float* __res
 // global_load_dwordx4 at any dword address; rows of 63 floats are only dword aligned) and the row sum is four DPP adds
 // inside the hardware's 16-lane row: quad_perm xor 1, xor 2, row_half_mirror, row_mirror -- VALU only, no LDS crossbar.
 // A wavefront covers 4 rows per load instruction and keeps U of them in flight.
-typedef float f32x4ru __attribute__((ext_vector_type(4), aligned(4)));
 __device__ __forceinline__ float row16_sum(float v) {
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, true));   // quad_perm [2,3,0,1]
@@ -647,19 +645,19 @@ __global__ __launch_bounds__(kBlock) void nll_rows_g16_k(const float* __restrict
   const int64_t gw = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * (kBlock / 64);
   const int nel = d - 4 * g;                           // elements of the row this lane holds: min(4, nel), <= 0: none
   for (int64_t r0 = gw * (4 * U); r0 < B; r0 += nw * (4 * U)) {
-    f32x4ru zv[U], jv[U];
+    f32x4u zv[U], jv[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int64_t row = r0 + 4 * u + grp;
       const int64_t base = row * d + 4 * g;
-      zv[u] = f32x4ru{0.f, 0.f, 0.f, 0.f};
-      jv[u] = f32x4ru{1.f, 1.f, 1.f, 1.f};
+      zv[u] = f32x4u{0.f, 0.f, 0.f, 0.f};
+      jv[u] = f32x4u{1.f, 1.f, 1.f, 1.f};
       // the last lanes of the LAST row must not read past the array; everywhere else the float4 may run into the next row
       // (masked below), which keeps every lane's load a single dwordx4
       const bool full = row < B && nel > 0 && (nel >= 4 || row + 1 < B);
       if (full) {
-        if (logn) zv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4ru*>(z + base));
-        if (jac) jv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4ru*>(jac + base));
+        if (logn) zv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4u*>(z + base));
+        if (jac) jv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4u*>(jac + base));
       } else if (row < B && nel > 0) {
 #pragma unroll
         for (int c = 0; c < 4; ++c)
@@ -693,18 +691,18 @@ __global__ __launch_bounds__(kBlock) void affine_fwd_g16_k(const float* __restri
   const int64_t gw = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * (kBlock / 64);
   const int nel = d - 4 * g;
   for (int64_t r0 = gw * (4 * U); r0 < B; r0 += nw * (4 * U)) {
-    f32x4ru xv[U], ha[U], hb[U];
+    f32x4u xv[U], ha[U], hb[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int64_t row = r0 + 4 * u + grp;
       const int64_t base = row * d + 4 * g;
-      xv[u] = f32x4ru{0.f, 0.f, 0.f, 0.f};
+      xv[u] = f32x4u{0.f, 0.f, 0.f, 0.f};
       ha[u] = xv[u]; hb[u] = xv[u];
       const bool full = row < B && nel > 0 && (nel >= 4 || row + 1 < B);
       if (full) {
-        xv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4ru*>(x + base));
-        ha[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4ru*>(h + 2 * base));
-        hb[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4ru*>(h + 2 * base + 4));
+        xv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4u*>(x + base));
+        ha[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4u*>(h + 2 * base));
+        hb[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4u*>(h + 2 * base + 4));
       } else if (row < B && nel > 0) {
 #pragma unroll
         for (int c = 0; c < 4; ++c)
@@ -720,7 +718,7 @@ __global__ __launch_bounds__(kBlock) void affine_fwd_g16_k(const float* __restri
       const int64_t row = r0 + 4 * u + grp;
       const int64_t base = row * d + 4 * g;
       const float h0[4] = {ha[u][0], ha[u][2], hb[u][0], hb[u][2]}, h1[4] = {ha[u][1], ha[u][3], hb[u][1], hb[u][3]};
-      f32x4ru zv, jv;
+      f32x4u zv, jv;
       float sl = 0.f, sn = 0.f;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
@@ -731,8 +729,8 @@ __global__ __launch_bounds__(kBlock) void affine_fwd_g16_k(const float* __restri
         if (c < nel) { sl += ls; sn += kLog2Pi + zv[c] * zv[c]; }
       }
       if (row < B && nel >= 4) {
-        __builtin_nontemporal_store(zv, reinterpret_cast<f32x4ru*>(z + base));
-        if (jac) __builtin_nontemporal_store(jv, reinterpret_cast<f32x4ru*>(jac + base));
+        __builtin_nontemporal_store(zv, reinterpret_cast<f32x4u*>(z + base));
+        if (jac) __builtin_nontemporal_store(jv, reinterpret_cast<f32x4u*>(jac + base));
       } else if (row < B) {
 #pragma unroll
         for (int c = 0; c < 4; ++c)
@@ -756,23 +754,23 @@ __global__ __launch_bounds__(kBlock) void affine_bwd_g16_k(const float* __restri
   const int64_t gw = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * (kBlock / 64);
   const int nel = d - 4 * g;
   for (int64_t r0 = gw * (4 * U); r0 < B; r0 += nw * (4 * U)) {
-    f32x4ru xv[U], ha[U], hb[U], gv[U], jv[U];
+    f32x4u xv[U], ha[U], hb[U], gv[U], jv[U];
     float gl[U], gn[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int64_t row = r0 + 4 * u + grp;
       const int64_t base = row * d + 4 * g;
-      xv[u] = f32x4ru{0.f, 0.f, 0.f, 0.f};
+      xv[u] = f32x4u{0.f, 0.f, 0.f, 0.f};
       ha[u] = xv[u]; hb[u] = xv[u]; gv[u] = xv[u]; jv[u] = xv[u];
       gl[u] = (glogdet && row < B) ? glogdet[row] : 0.f;
       gn[u] = (glogn && row < B) ? glogn[row] : 0.f;
       const bool full = row < B && nel > 0 && (nel >= 4 || row + 1 < B);
       if (full) {
-        xv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4ru*>(x + base));
-        ha[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4ru*>(h + 2 * base));
-        hb[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4ru*>(h + 2 * base + 4));
-        if (gz) gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4ru*>(gz + base));
-        if (gjac) jv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4ru*>(gjac + base));
+        xv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4u*>(x + base));
+        ha[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4u*>(h + 2 * base));
+        hb[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4u*>(h + 2 * base + 4));
+        if (gz) gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4u*>(gz + base));
+        if (gjac) jv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4u*>(gjac + base));
       } else if (row < B && nel > 0) {
 #pragma unroll
         for (int c = 0; c < 4; ++c)
@@ -791,7 +789,7 @@ __global__ __launch_bounds__(kBlock) void affine_bwd_g16_k(const float* __restri
       if (row >= B || nel <= 0) continue;
       const int64_t base = row * d + 4 * g;
       const float h0[4] = {ha[u][0], ha[u][2], hb[u][0], hb[u][2]}, h1[4] = {ha[u][1], ha[u][3], hb[u][1], hb[u][3]};
-      f32x4ru ox, oa, ob;
+      f32x4u ox, oa, ob;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         // torch clamp backward passes the gradient where min <= v <= max (boundaries included)
@@ -804,9 +802,9 @@ __global__ __launch_bounds__(kBlock) void affine_bwd_g16_k(const float* __restri
         if (c < 2) { oa[2 * c] = o0; oa[2 * c + 1] = o1; } else { ob[2 * c - 4] = o0; ob[2 * c - 3] = o1; }
       }
       if (nel >= 4) {
-        if (gx) __builtin_nontemporal_store(ox, reinterpret_cast<f32x4ru*>(gx + base));
-        __builtin_nontemporal_store(oa, reinterpret_cast<f32x4ru*>(gh + 2 * base));
-        __builtin_nontemporal_store(ob, reinterpret_cast<f32x4ru*>(gh + 2 * base + 4));
+        if (gx) __builtin_nontemporal_store(ox, reinterpret_cast<f32x4u*>(gx + base));
+        __builtin_nontemporal_store(oa, reinterpret_cast<f32x4u*>(gh + 2 * base));
+        __builtin_nontemporal_store(ob, reinterpret_cast<f32x4u*>(gh + 2 * base + 4));
       } else {
 #pragma unroll
         for (int c = 0; c < 4; ++c)

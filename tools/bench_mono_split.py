@@ -5,6 +5,9 @@
 import ctypes, os, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, ROOT + '/graphical-normalizing-flows_amd']
+if os.environ.get('GNF_AB_LIB'):                      # A/B against another build of the library (tools/*.bin)
+    from gnf_hip import abi as _abi
+    _abi.LIB_PATH = os.path.join(ROOT, os.environ['GNF_AB_LIB'])
 from gnf_hip import abi, ops
 from gnf_hip.abi import call, ptr, stream
 from _warm import warm_gpu
