@@ -5,7 +5,7 @@ MLP.py:44-47.   python tests/fuzz_linear.py [n_cases] [seed]"""
 import os, sys, random
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "graphical-normalizing-flows_amd")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "graphical-normalizing-flows_amd"), os.path.join(ROOT, "tests")]
 from gnf_hip import ops       # noqa: E402
 DEV = "cuda:0"
 WIDTHS = [1, 2, 3, 12, 16, 30, 31, 32, 33, 50, 60, 63, 64, 65, 96, 100, 128, 129, 160, 255, 256, 630, 784, 1024, 1568, 2304]
@@ -54,29 +54,36 @@ def one(case, rng, only=None):
                 degs.append((do.to(DEV), dprev.to(DEV), strict))
             masks.append(m)
             dprev = do
+    # Rows with a hidden pre-activation within the fp32 chain's error bound of zero are REDRAWN from the same generator until none
+    # is left (rows are independent): there an fp32 chain and the fp64 one may gate differently, and ONE flipped gate moves that
+    # row's gradient by several per cent (at 60 000 rows x 256 units a walk meets a handful of such rows per case).  The bound of a
+    # layer = 16 fp32 ulps of its own terms' magnitude + the bound INHERITED from its inputs through |W|: behind a narrow
+    # bottleneck (walk 703, case 113: 255 -> 1 -> 198) the single input carries the roundoff of a 255-term sum, which is far more
+    # than 16 ulps of its own small value
+    def tied_rows(x_):
+        a = x_.double()
+        knife = torch.zeros(M, dtype=torch.bool)
+        aerr = torch.zeros(M, dims[0], dtype=torch.float64)      # bound on the fp32 chain's absolute error of the layer inputs
+        for l, (W, b) in enumerate(layers[:-1]):
+            Wm = (W * masks[l] if masks else W).double()
+            pre = torch.nn.functional.linear(a, Wm, b.double())
+            mag = a.abs() @ Wm.abs().t() + b.double().abs()
+            aerr = 16 * 2. ** -23 * mag + aerr @ Wm.abs().t()
+            knife |= ((pre.abs() < aerr) & (pre != 0)).any(1)
+            a = torch.relu(pre)
+        return knife
+    from knife_units import resample_off_ties
+    knife = tied_rows(x)
+    (x,), _ = resample_off_ties(lambda: (torch.randn(M, dims[0], generator=g),), tied_rows, first=(x,))
     gy = torch.randn(M, dims[-1], generator=g)
-    # fp64 reference.  Rows with a hidden pre-activation within the fp32 chain's error bound of zero get a zero cotangent: there an
-    # fp32 chain and the fp64 one may gate differently, and ONE flipped gate moves that row's gradient by several per cent (at
-    # 60 000 rows x 256 units a walk meets a handful of such rows per case).  The bound of a layer = 16 fp32 ulps of its own terms'
-    # magnitude + the bound INHERITED from its inputs through |W|: behind a narrow bottleneck (walk 703, case 113: 255 -> 1 -> 198)
-    # the single input carries the roundoff of a 255-term sum, which is far more than 16 ulps of its own small value
+    # fp64 reference
     xr = x.double().requires_grad_(need_x)
     ps = [(W.double().requires_grad_(True), b.double().requires_grad_(True)) for W, b in layers]
     a = xr
-    knife = torch.zeros(M, dtype=torch.bool)
-    aerr = torch.zeros(M, dims[0], dtype=torch.float64)          # bound on the fp32 chain's absolute error of the layer inputs
     for l, (W, b) in enumerate(ps):
         Wm = W * masks[l].double() if masks else W
         pre = torch.nn.functional.linear(a, Wm, b)
-        if l < nl - 1:
-            with torch.no_grad():
-                mag = a.detach().abs() @ Wm.detach().abs().t() + b.detach().abs()
-                aerr = 16 * 2. ** -23 * mag + aerr @ Wm.detach().abs().t()
-                knife |= ((pre.detach().abs() < aerr) & (pre.detach() != 0)).any(1)
-            a = torch.relu(pre)
-        else:
-            a = pre
-    gy = gy * (~knife).float()[:, None]
+        a = torch.relu(pre) if l < nl - 1 else pre
     (a * gy.double()).sum().backward()
     # product
     xg = x.to(DEV).requires_grad_(need_x)
@@ -93,7 +100,7 @@ def one(case, rng, only=None):
             bad.append("gW%d non-zero under the mask" % l)
     # fp32 chains against fp64: 1e-5 on outputs of O(1), 1e-4 on gradients (sums over up to 60 000 rows)
     bad += [k for k, v in errs.items() if not v < (2e-5 if k == "y" else 1e-4)]
-    desc = "M %5d dims %-28s mask %-10s x.grad %d knife rows %d" % (M, dims, mask_kind, need_x, int(knife.sum()))
+    desc = "M %5d dims %-28s mask %-10s x.grad %d redrawn rows %d" % (M, dims, mask_kind, need_x, int(knife.sum()))
     return desc, errs, bad
 
 

@@ -41,6 +41,15 @@ def run_case(case, hidden, c, S, B, d):
     x = torch.randn(B, d) * 1.5
     h = torch.randn(B, d, c)
     ps = [p.detach().clone() for p in norm.integrand_net.flat_params()]
+    # knife edges: a hidden ReLU pre-activation within a few fp32 ulps of zero (fp64 evaluation, tests/conftest.py) flips a gate in
+    # one of the two fp32 computations and moves a gradient by that element's whole share.  Such elements are redrawn (same
+    # generator, same scale) before the comparison, so every element carries a live cotangent and a failure is a failure; the
+    # tied elements of raw draws are judged by tests/test_gpu_knife.py
+    from conftest import integrand_knife_elements
+    from knife_units import resample_off_ties
+    frozen = [(ps[i], ps[i + 1]) for i in range(0, len(ps), 2)]
+    (x, h), _ = resample_off_ties(lambda: (torch.randn(B, d) * 1.5, torch.randn(B, d, c)),
+                                  lambda x_, h_: integrand_knife_elements(x_, h_, frozen, S), first=(x, h))
     layers = [(ps[i].requires_grad_(True), ps[i + 1].requires_grad_(True)) for i in range(0, len(ps), 2)]
     xr, hr = x.clone().requires_grad_(True), h.clone().requires_grad_(True)
     z0, j0 = O.monotonic_forward(xr, hr, layers, S)
@@ -62,30 +71,6 @@ def run_case(case, hidden, c, S, B, d):
     errs[kl] = min(errs[kl], float((norm.integrand_net.flat_params()[-1].grad.cpu().double() - layers[-1][1].grad.double()).abs().max())
                    / max(bound, 1e-30) * 10.)
     bad = [k for k, v in errs.items() if not (v < (TOL if k in ("z", "jac") else GTOL))]
-    if bad:
-        # knife edges: a hidden ReLU pre-activation within a few fp32 ulps of zero (fp64 evaluation, tests/conftest.py) flips a
-        # gate in one of the two fp32 computations and moves a gradient by that element's whole share.  Such elements get a zero
-        # cotangent and both sides are evaluated again -- what still differs is a defect.
-        from conftest import integrand_knife_elements
-        knife = integrand_knife_elements(x, h, [(W.detach(), b_.detach()) for W, b_ in layers], S)
-        nk = int(knife.sum())
-        if nk:
-            gz2, gj2 = gz.masked_fill(knife, 0.), gj.masked_fill(knife, 0.)
-            for t in [xr, hr] + [p for pair in layers for p in pair]:
-                t.grad = None
-            z0, j0 = O.monotonic_forward(xr, hr, layers, S)
-            ((z0 * gz2).sum() + (torch.log(j0) * gj2).sum()).backward()
-            for t in [xg, hg] + list(norm.integrand_net.flat_params()):
-                t.grad = None
-            z, jac = norm(xg, hg)
-            ((z * gz2.to(DEV)).sum() + (torch.log(jac) * gj2.to(DEV)).sum()).backward()
-            errs2 = {"dx": rel(xg.grad.cpu(), xr.grad), "dh": rel(hg.grad.cpu(), hr.grad)}
-            for k, ((W, b_), pw, pb) in enumerate(zip(layers, norm.integrand_net.flat_params()[0::2],
-                                                      norm.integrand_net.flat_params()[1::2])):
-                errs2["dW%d" % k] = rel(pw.grad.cpu(), W.grad)
-                errs2["db%d" % k] = rel(pb.grad.cpu(), b_.grad)
-            bad = ["%s %.1e (%d knife elements zeroed)" % (k, v, nk) for k, v in errs2.items() if not v < GTOL]
-            bad += [k for k in ("z", "jac") if not errs[k] < TOL]
     # inverse: round trip through the kernel's own forward, and the scattered form == the plain one
     with torch.no_grad():
         zt = z.detach()

@@ -1,5 +1,5 @@
 """A short fixed-seed walk over random Monotonic-normalizer shapes (tests/fuzz_mono.py): forward, every gradient, the inverse
-and its scattered form against the oracle, knife-edge elements arbitrated in fp64.  The parametrised tests pin the shapes the
+and its scattered form against the oracle, knife-edge elements (fp64 evaluation) redrawn before the comparison.  The parametrised tests pin the shapes the
 reference uses; this one walks between them (hidden widths 1..208, 1-4 layers, c 1..40, S 1..40) -- the weight pack's unit order
 and the kernels' launch conditions are functions of exactly these numbers."""
 import pytest
@@ -27,7 +27,7 @@ def test_gemm_random_shapes():
 
 def test_linear_random_chains():
     """Linear + ReLU chains of random depth / widths / batch sizes / mask kinds through the gnf_linear_* entry points against
-    an fp64 autograd (tests/fuzz_linear.py); rows on a ReLU knife edge get a zero cotangent"""
+    an fp64 autograd (tests/fuzz_linear.py); rows on a ReLU knife edge are redrawn, every row has a live cotangent"""
     import fuzz_linear
     res = fuzz_linear.walk(60, 3)
     bad = [(case, desc, why) for case, desc, errs, why in res if why]
