@@ -53,7 +53,23 @@ struct CnnArgs {
   const float* gp; const unsigned char* argin; float* ge; float* part;   // backward
   int64_t n;
   const int32_t* plan; float* gec; int dplan;                             // backward, column plan (gnf_hip.h) or NULL
+  float* a1save;                                                          // forward: conv1 activations out (NULL: not kept)
+  const float* a1in;                                                      // backward, saved-a1 kernel: what the forward kept
 };
+
+// The conv1 + ReLU activations of an image as the Winograd forward can keep them for the backward: the byte image of the
+// backward's LDS buffer, [16 channels][SAVE_CH] with rows of pitch IMG; columns 26, 27 of every row and the entries 728,
+// 729 behind every channel are zeros (the backward's de gather reads them, see gnf_mnistcnn.hip).
+constexpr int SAVE_CH = C1 * IMG + 2, SAVE_IMG = NCH * SAVE_CH;
+static_assert((SAVE_IMG * 4) % 1024 != 0 && (SAVE_IMG * 4) % 16 == 0 && SAVE_IMG * 4 >= 1024, "whole 16-byte chunks");
+constexpr int SAVE_PIECES = (SAVE_IMG * 4 + 1023) / 1024;              // 1 KiB per wavefront instruction
+// Piece p (wave-uniform) of a saved image straight into LDS: global -> LDS without a VGPR destination, lane l lands at
+// lds + 16 l.  rs = descriptor of the image (zero records behind the last image: nothing is loaded).  The last piece is
+// moved back to end with the image: it rewrites the tail of the piece before it with the same bytes.
+__device__ __forceinline__ void a1_piece_to_lds(rsrc_t rs, float* a1_lds, int p, int lane16) {
+  const int b = p * 1024 < SAVE_IMG * 4 - 1024 ? p * 1024 : SAVE_IMG * 4 - 1024;     // bytes; scalar
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(a1_lds + b / 4), 16, lane16, b, 0, 0);
+}
 
 // conv1 + ReLU of NU units starting at unit u0, on v_mfma_f32_16x16x1_4b_f32 (four independent 16 x 16 x 1 products per
 // instruction): block b = the 16-position tile 4 u + b, ONE tap per instruction -- 9 instructions per 64 positions where

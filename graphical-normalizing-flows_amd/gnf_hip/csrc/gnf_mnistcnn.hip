@@ -146,8 +146,30 @@ __device__ __forceinline__ void dw2_phase(const float* av, const float* dz, f32x
 // "structural zeros of the gate backward"): the de gather shrinks to one half wavefront and a dword store per column, and
 // a da1 group whose 16 tiles no such column reaches (bit of the per-row group mask gmt[i], built once per kernel in LDS)
 // skips its T planes -- 16 of its 80 MFMAs and the stores.
+//
+// SV: a1 is not recomputed but LOADED -- the Winograd forward kept every image's conv1 activations (a.a1in, the byte image
+// of one a1 buffer here: SAVE_CH == CHB, pads zero).  Every conv1_run becomes SAVE_PIECES (46) global -> LDS loads of 1 KiB
+// without a VGPR destination, dealt over the wavefronts by DMAU, issued where conv1 ran (top of Xb: the buffer holds the
+// previous image's T planes until the de of Xa is behind the barrier) and complete at the barrier that ends Xb.  The copy
+// rewrites the pad entries of the buffer on every image: the forward stores zeros there.  No conv1 code, no W1 table and no
+// b1 in this variant; the a1 stream rides on a memory system the kernel leaves idle instead of the ALU that bounds it.
+// The prefetches the next scatter / staging consume are issued in Xa, AHEAD of the copy (vmcnt retires in order).
 constexpr int KC = GNF_DAG_PLAN_KC;
-template <bool SP>
+static_assert(SAVE_CH == CHB && SAVE_IMG == A1B, "the saved image is the byte image of an a1 buffer");
+// Pieces of the next image per wavefront.  With conv1 gone Xb is the da1 groups, 2/2/2/1/1/1/1/1 over the wavefronts = 3/3/3/2
+// per SIMD: SIMD 3 (wavefronts 3, 7) has a group's time to spare and issues the whole copy (an issue costs its wavefront
+// 60-185 cycles next to MFMAs).  Plan body at cfg4, tools/bench_cnn.py on one box, recompute 2.70-2.71 ms: evenly
+// {6,6,6,6,6,6,5,5} 2.82; the deals in between ({4,4,4,8,5,5,5,11}, {2,2,2,14,4,4,4,14}) 2.65-2.72 with a run-to-run
+// spread of 0.07 ms that leaves them unranked; this deal 2.535-2.564 in eleven runs -- the whole of what removing conv1 can
+// give (2.541-2.545 with conv1 compiled out and nothing in its place).  Judged by the kernel's time, not by barrier waits.
+#ifndef GNF_BWD_DMAU
+#define GNF_BWD_DMAU {0, 0, 0, 23, 0, 0, 0, 23}
+#endif
+__device__ constexpr int DMAU[8] = GNF_BWD_DMAU;
+__device__ constexpr int DMAPRO[8] = {6, 6, 6, 6, 6, 6, 5, 5};  // the first image: dealt evenly
+static_assert(c1sum(DMAU) == SAVE_PIECES && c1sum(DMAPRO) == SAVE_PIECES, "copy pieces");
+
+template <bool SP, bool SV>
 __device__ __forceinline__ void cnn_bwd_body(const CnnArgs& a, float* smem) {
 #ifdef GNF_CNN_TIMING
   long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -165,11 +187,13 @@ __device__ __forceinline__ void cnn_bwd_body(const CnnArgs& a, float* smem) {
   constexpr int NW = BWD_WAVES, NT = 64 * BWD_WAVES;
   static_assert(((2 * ESZB) % 4 == 0) && ((2 * A1B) % 4 == 0) && (DSZW % 4 == 0), "d_s / u_s must be 16-B aligned");
 
-  if (tid < 9 * NCH) w1_s[tid] = a.W1[(tid & 15) * 9 + (tid >> 4)];   // (nine registers per lane otherwise: the kernel is at 256)
+  if (!SV && tid < 9 * NCH) w1_s[tid] = a.W1[(tid & 15) * 9 + (tid >> 4)];   // (nine registers per lane otherwise: the kernel is at 256)
   const float* w1a = w1_s + j;               // W1 as A operand of conv1: row = channel j (every block), tap t at w1a[16 t]
-  f32x4 b1v;
+  f32x4 b1v = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (!SV) {
 #pragma unroll
-  for (int r = 0; r < 4; ++r) b1v[r] = a.b1[4 * q + r];
+    for (int r = 0; r < 4; ++r) b1v[r] = a.b1[4 * q + r];
+  }
   float w1t[4];                              // W1^T as A operand of the per-tap planes: row = tap j, K slot q, step r
 #pragma unroll
   for (int r = 0; r < 4; ++r) w1t[r] = j < 9 ? a.W1[(4 * q + r) * 9 + j] : 0.f;
@@ -265,6 +289,11 @@ __device__ __forceinline__ void cnn_bwd_body(const CnnArgs& a, float* smem) {
       const int i = tid + k * NT;
       if (i < IMG * IMG) dst[i] = epre[k];
     }
+  };
+  // SV: this wavefront's pieces of image im into an a1 buffer (pieces p0 .. p0 + np - 1, wave-uniform)
+  auto load_a1 = [&](int64_t im, float* dst, int p0, int np) {
+    const rsrc_t rs = rsrc_of(a.a1in, im, SAVE_IMG * 4);
+    for (int k = 0; k < np; ++k) a1_piece_to_lds(rs, dst, p0 + k, lane * 16);   // a scalar loop
   };
   // this thread's pool windows (channel tid/32, window (tid&31) + 32k): fixed LDS offsets
   float* const dwin = d_s + dslot(tid >> 5) * DCS + 4 * (tid & 31);
@@ -367,9 +396,15 @@ __device__ __forceinline__ void cnn_bwd_body(const CnnArgs& a, float* smem) {
   __syncthreads();                                               // e(0) staged, U' and the dY2 zeros written
   if (img0 < a.n) {
     int u0 = 0;
+    if (SV) {
 #pragma unroll
-    for (int w = 0; w < NW; ++w) u0 += w < wave ? C1PRO[w] : 0;
-    conv1_run(e_s, a1_s, u0, C1PRO[wave], w1a, b1v, q, j, lane);
+      for (int w = 0; w < NW; ++w) u0 += w < wave ? DMAPRO[w] : 0;
+      load_a1(img0, a1_s, u0, DMAPRO[wave]);
+    } else {
+#pragma unroll
+      for (int w = 0; w < NW; ++w) u0 += w < wave ? C1PRO[w] : 0;
+      conv1_run(e_s, a1_s, u0, C1PRO[wave], w1a, b1v, q, j, lane);
+    }
   }
 
   // ---- dY2 = pool-backward scatter of g_pooled: every window holds ONE non-zero, so the previous image's entry is
@@ -399,6 +434,7 @@ __device__ __forceinline__ void cnn_bwd_body(const CnnArgs& a, float* smem) {
     const float* e_rd = e_s + par * ESZB;
     float* e_nx = e_s + (par ^ 1) * ESZB;
     rd_target += NW;
+    if (SV) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wavefront's pieces of a1p have landed
     __syncthreads();                                             // a1p (conv1), dY2 (scatter) of this image and the previous
     TSTAMP(0);                                                   // image's T planes complete; its input buffer is free
     // ---- Xa: stage the next image (requested one image ago), request what the image after needs, dW2 (9 K-steps per
@@ -427,12 +463,13 @@ __device__ __forceinline__ void cnn_bwd_body(const CnnArgs& a, float* smem) {
     const bool has_next = img + gstride < a.n;
     int c1t0 = 0;
 #pragma unroll
-    for (int w = 0; w < NW; ++w) c1t0 += w < wave ? C1U[w] : 0;
+    for (int w = 0; w < NW; ++w) c1t0 += w < wave ? (SV ? DMAU[w] : C1U[w]) : 0;
+    if (SV && has_next) load_a1(img + gstride, a1n, c1t0, DMAU[wave]);
     const bool c1_first = wave != 7;                             // SIMD 3 holds two conv1-heavy wavefronts: one starts with conv1,
 #ifdef GNF_CNN_EXP_NOCONV1
     const bool c1_on = false;
 #else
-    const bool c1_on = has_next;
+    const bool c1_on = has_next && !SV;
 #endif
     if (c1_on && c1_first) {                                     // the other with its da1 group
       conv1_run(e_nx, a1n, c1t0, C1U[wave], w1a, b1v, q, j, lane);
@@ -634,10 +671,19 @@ __device__ __forceinline__ void cnn_bwd_body(const CnnArgs& a, float* smem) {
 __global__ __launch_bounds__(64 * BWD_WAVES) void cnn_bwd_wino_k(CnnArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   if (a.plan && a.plan[a.dplan + (a.dplan * KC + 1) / 2] == 0) {   // the plan's overflow word (gnf_hip.h)
-    cnn_bwd_body<true>(a, smem);
+    cnn_bwd_body<true, false>(a, smem);
     return;
   }
-  cnn_bwd_body<false>(a, smem);
+  cnn_bwd_body<false, false>(a, smem);
+}
+// the same over the a1 images the forward kept (a.a1in)
+__global__ __launch_bounds__(64 * BWD_WAVES) void cnn_bwd_wino_saved_k(CnnArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  if (a.plan && a.plan[a.dplan + (a.dplan * KC + 1) / 2] == 0) {
+    cnn_bwd_body<true, true>(a, smem);
+    return;
+  }
+  cnn_bwd_body<false, true>(a, smem);
 }
 
 // the workgroups' partial rows summed in row order (64 columns per workgroup, wavefront w of 16 takes rows w, w + 16, ...,
@@ -675,6 +721,11 @@ static_assert((size_t)BWD_WAVES * PROW * sizeof(float) <= kBwdWinoLds, "the part
 // one 8-wave workgroup per CU: at its 256 VGPRs a second one is not admitted
 constexpr unsigned kBwdGrid = 256;
 
+int conv_bwd_launch(const float* e, const float* a1saved, const float* W1, const float* b1, const float* W2,
+                    const float* g_pooled, const unsigned char* argmax, float* ge, const int32_t* plan, int64_t d_plan,
+                    float* ge_cols, float* gW1, float* gb1, float* gW2, float* gb2, void* ws, int64_t ws_bytes,
+                    int64_t n_img, gnf_stream_t stream);
+
 }  // namespace
 
 extern "C" {
@@ -695,6 +746,35 @@ int gnf_mnistcnn_conv_bwd_cols(const float* e, const float* W1, const float* b1,
                                const unsigned char* argmax, float* ge, const int32_t* plan, int64_t d_plan,
                                float* ge_cols, float* gW1, float* gb1, float* gW2, float* gb2, void* ws,
                                int64_t ws_bytes, int64_t n_img, gnf_stream_t stream) {
+  return conv_bwd_launch(e, nullptr, W1, b1, W2, g_pooled, argmax, ge, plan, d_plan, ge_cols, gW1, gb1, gW2, gb2, ws, ws_bytes,
+                         n_img, stream);
+}
+
+int gnf_mnistcnn_conv_bwd_a1(const float* e, const float* a1saved, const float* W1, const float* b1, const float* W2,
+                             const float* g_pooled, const unsigned char* argmax, float* ge, float* gW1, float* gb1,
+                             float* gW2, float* gb2, void* ws, int64_t ws_bytes, int64_t n_img, gnf_stream_t stream) {
+  return gnf_mnistcnn_conv_bwd_cols_a1(e, a1saved, W1, b1, W2, g_pooled, argmax, ge, nullptr, 0, nullptr, gW1, gb1, gW2, gb2,
+                                       ws, ws_bytes, n_img, stream);
+}
+
+int gnf_mnistcnn_conv_bwd_cols_a1(const float* e, const float* a1saved, const float* W1, const float* b1, const float* W2,
+                                  const float* g_pooled, const unsigned char* argmax, float* ge, const int32_t* plan,
+                                  int64_t d_plan, float* ge_cols, float* gW1, float* gb1, float* gW2, float* gb2, void* ws,
+                                  int64_t ws_bytes, int64_t n_img, gnf_stream_t stream) {
+  if ((!a1saved && n_img > 0) || ((uintptr_t)a1saved & 15)) return GNF_EINVAL;   // 16-byte pieces
+  return conv_bwd_launch(e, a1saved, W1, b1, W2, g_pooled, argmax, ge, plan, d_plan, ge_cols, gW1, gb1, gW2,
+                         gb2, ws, ws_bytes, n_img, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+// a1saved: NULL = recompute conv1 (cnn_bwd_wino_k), else the images the forward kept (cnn_bwd_wino_saved_k)
+int conv_bwd_launch(const float* e, const float* a1saved, const float* W1, const float* b1, const float* W2,
+                    const float* g_pooled, const unsigned char* argmax, float* ge, const int32_t* plan, int64_t d_plan,
+                    float* ge_cols, float* gW1, float* gb1, float* gW2, float* gb2, void* ws, int64_t ws_bytes,
+                    int64_t n_img, gnf_stream_t stream) {
   if (((!e || !g_pooled || !argmax || !ge) && n_img > 0) || !W1 || !b1 || !W2 || !gW1 || !gb1 || !gW2 || !gb2 || !ws ||
       n_img < 0)
     return GNF_EINVAL;                       // empty batch: zero weight gradients through the same kernels
@@ -705,8 +785,10 @@ int gnf_mnistcnn_conv_bwd_cols(const float* e, const float* W1, const float* b1,
   a.e = e; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.gp = g_pooled; a.argin = argmax; a.ge = ge; a.part = (float*)ws;
   a.n = n_img;
   a.plan = plan; a.gec = ge_cols; a.dplan = (int)d_plan;
+  a.a1in = a1saved;
   // fixed grid: every workgroup (also one without images) writes its partial rows
-  if (hipError_t e = gnf_launch_lds(cnn_bwd_wino_k, dim3(kBwdGrid), dim3(64 * BWD_WAVES), kBwdWinoLds, (hipStream_t)stream, a))
+  if (hipError_t e = gnf_launch_lds(a1saved ? cnn_bwd_wino_saved_k : cnn_bwd_wino_k, dim3(kBwdGrid), dim3(64 * BWD_WAVES),
+                                    kBwdWinoLds, (hipStream_t)stream, a))
     return (int)e;
   // one partial row per workgroup -> the four gradients, one launch
   hipLaunchKernelGGL(cnn_reduce_unpack_k, dim3((PROW + 63) / 64), dim3(1024), 0, (hipStream_t)stream, (const float*)ws,
@@ -715,4 +797,4 @@ int gnf_mnistcnn_conv_bwd_cols(const float* e, const float* W1, const float* b1,
   return 0;
 }
 
-}  // extern "C"
+}  // namespace

@@ -11,9 +11,10 @@
 //   is gathered from the LDS image with per-K-step immediate offsets.  Row / channel strides
 //   (40 and == 16 mod 32 dwords) make the 64-lane gather bank-conflict free:
 //   lane (q, j) -> channel 4g+q (bank +16q), row j>>3 (bank +8), column j&7.
-// Backward recomputes conv1 (3 % of the flops) instead of storing 43 KB of activations per
-// image, takes the pool argmax saved by the forward (1 byte per pooled value), and keeps the
-// weight-gradient accumulators in registers across all images of a workgroup.
+// Backward recomputes conv1 (3 % of the flops) or, when the Winograd forward was asked to keep them
+// (a1save: 46 KB of activations per image, see save_a1), loads them; it takes the pool argmax saved
+// by the forward (1 byte per pooled value), and keeps the weight-gradient accumulators in registers
+// across all images of a workgroup.
 //
 // This file: the FORWARD kernels (Winograd, and the direct tie-exact one).  Both conv units are built with
 // -fno-slp-vectorize (gnf_hip/build.py): the SLP vectoriser packs the scalar adds of the output transform into v_pk_add_f32
@@ -187,8 +188,17 @@ static_assert(fsum(F1U) == 11 && fsum(F1PRO) == 11, "conv1 units");
 constexpr int fmax8(const int (&v)[8]) { int t = 0; for (int i = 0; i < 8; ++i) t = v[i] > t ? v[i] : t; return t; }
 static_assert(fmax8(F1U) <= 3 && fmax8(F1PRO) <= 3, "at most three units per wavefront (conv1_do, the packed offsets)");
 
-__global__ __launch_bounds__(64 * FWD_WAVES) void cnn_fwd_wino_k(CnnArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
+// Of a thread's 6 saved-a1 chunks, those stored at the top of the interval; the rest leave behind its Winograd item.  All
+// six at the top (46 KB per workgroup in one burst behind the barrier) cost the forward 0.30 ms at cfg4, 3 + 3 0.13-0.15;
+// none at the top, or one chunk per channel step inside the item, are no better (profiles/conv_saved_a1_ab.txt).
+#ifndef GNF_FWD_SAVE_TOP
+#define GNF_FWD_SAVE_TOP 3
+#endif
+#ifndef GNF_FWD_SAVE_AUX
+#define GNF_FWD_SAVE_AUX 2         // cache policy of the saved-a1 stores: 2 = non-temporal (0, the default policy: the same time)
+#endif
+template <bool SAVE>                       // SAVE: every a1 image also goes to a.a1save (see save_a1)
+__device__ __forceinline__ void cnn_fwd_wino_body(const CnnArgs& a, float* smem) {
   float* e_s = smem;                       // [2][28 x 28]
   float* a1_s = smem + 2 * WESZ;           // [2][16][26][WROW]
   float* xch = a1_s + 2 * A1SZ;            // [2 images][2 halves][16][64]: partial output transforms of the split item
@@ -198,6 +208,8 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void cnn_fwd_wino_k(CnnArgs a) {
   constexpr int NW = FWD_WAVES, NT = 64 * FWD_WAVES;
 
   if (tid < 9 * NCH) w1_s[tid] = a.W1[(tid & 15) * 9 + (tid >> 4)];
+  if (SAVE)                                            // the pad columns of the saved images (see save_a1): zero for good
+    for (int i = tid; i < 2 * A1SZ; i += NT) a1_s[i] = 0.f;
   f32x4 b1v, b2v;
 #pragma unroll
   for (int r = 0; r < 4; ++r) { b1v[r] = a.b1[4 * q + r]; b2v[r] = a.b2[4 * q + r]; }
@@ -263,6 +275,62 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void cnn_fwd_wino_k(CnnArgs a) {
     if (nu == 3) conv1_units<3, WCH>(e_rd, a1_wr, u0, w1_s + j, b1v, q, j, lane);
     else if (nu == 2) conv1_units<2, WCH>(e_rd, a1_wr, u0, w1_s + j, b1v, q, j, lane);
     else if (nu == 1) conv1_units<1, WCH>(e_rd, a1_wr, u0, w1_s + j, b1v, q, j, lane);
+  };
+  // ---- a1save: every finished a1 image also goes to HBM for the backward, in the layout of ITS LDS buffer ([16][SAVE_CH],
+  //      gnf_mnistcnn.h).  The work is cut by DESTINATION: thread t stores the 16-byte chunks t, t + 512, ... of the
+  //      2 920, so a wavefront instruction writes 1 KiB of whole, aligned 128-byte lines (cut by channel, odd channels start
+  //      8 (mod 16) bytes into the image and every instruction leaves two partial lines).  A chunk is two float pairs;
+  //      pair h of the image is (channel h / 365, offset 2 (h % 365)): both images have the row pitch 28, so it sits at
+  //      c * WCH + r here -- or, for r = 728 (the two entries behind a channel, which take conv1's off-grid dummy stores
+  //      here), at a pair of pad columns.  The pad columns 26, 27 of every row are written by nobody, so zeroing the two
+  //      buffers once at kernel start makes them the zeros the backward wants.  LDS byte offsets of the two pairs packed
+  //      once, 16 bits each.  Non-temporal: the image is read again after the whole rest of the step has run, and it is
+  //      larger than every cache.
+  constexpr int SPAIRS = SAVE_CH / 2, SCHUNKS = SAVE_IMG / 4, SPT = (SCHUNKS + NT - 1) / NT, SZERO = C1 * 4;
+  static_assert(SPAIRS * 2 == SAVE_CH && SCHUNKS * 4 == SAVE_IMG && WCH * NCH * 4 < 65536, "saved-image chunks, 16-bit offsets");
+  unsigned spo[SPT];
+  if (SAVE) {
+#pragma unroll
+    for (int k = 0; k < SPT; ++k) {
+      unsigned o[2];
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        const int h = 2 * (tid + k * NT) + hf, c = h / SPAIRS, r2 = h - c * SPAIRS;
+        o[hf] = (unsigned)(c < NCH && r2 < SPAIRS - 1 ? (c * WCH + 2 * r2) * 4 : SZERO);   // (chunks past the image: dropped)
+      }
+      spo[k] = o[0] | (o[1] << 16);
+    }
+  }
+  auto save_rsrc = [&](int64_t im) {
+    // The two timing builds behind block 2 (e) of profiles/conv_saved_a1_ab.txt.  WRONG RESULTS, never in the product:
+#ifdef GNF_FWD_SAVE_DROP
+    im = a.n;                                          // zero records: every store dropped
+#endif
+#ifdef GNF_FWD_SAVE_L2ONLY
+    im = blockIdx.x;                                   // a workgroup rewrites ONE slot (the lines stay in L2)
+#endif
+    return rsrc_of(a.a1save, im, SAVE_IMG * 4);
+  };
+  auto save_read = [&](const float* a1, int k) {       // a1: complete and stable for the whole interval
+    const char* src = reinterpret_cast<const char*>(a1);
+    const f32x2 lo = *reinterpret_cast<const f32x2*>(src + (spo[k] & 0xffffu)), hi = *reinterpret_cast<const f32x2*>(src + (spo[k] >> 16));
+    return f32x4{lo.x, lo.y, hi.x, hi.y};
+  };
+  auto save_store = [&](rsrc_t rs, int k, const f32x4& v) {      // chunk tid + k NT; past the image: out of range, dropped
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, tid * 16, k * NT * 16, GNF_FWD_SAVE_AUX);
+  };
+  auto save_a1 = [&](const float* a1, int64_t im, int kb, int ke) {    // chunks [kb, ke) of this thread
+    const rsrc_t rs = save_rsrc(im);
+#pragma unroll
+    for (int k0 = kb; k0 < ke; k0 += 3) {              // three chunks read (12 registers), then their stores
+      f32x4 v[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        if (k0 + k < ke) v[k] = save_read(a1, k0 + k);
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        if (k0 + k < ke) save_store(rs, k0 + k, v[k]);
+    }
   };
   // one whole item: group grp of 16 tiles of the image in a1
   auto whole_item = [&](const float* a1, int grp, int64_t im) {
@@ -418,10 +486,12 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void cnn_fwd_wino_k(CnnArgs a) {
     stage(e_s + par * WESZ);                           // image i+2 (requested one interval ago)
     fetch(img + 3 * gs);
     if (wave == GNF_FWD_SPLIT_WAVE && prev >= 0) finish_split(xch + (par ^ 1) * 2 * 16 * 64, prev);
+    if (SAVE) save_a1(a1p, img, 0, GNF_FWD_SAVE_TOP);
     FSTAMP(1);
     if (has_next && units_first) conv1_steady(e_s + (par ^ 1) * WESZ, a1n);
     FSTAMP(2);
     whole_item(a1p, wave, img);
+    if (SAVE) save_a1(a1p, img, GNF_FWD_SAVE_TOP, SPT);
     FSTAMP(3);
     if (wave < 2) half_item(a1p, wave, xch + par * 2 * 16 * 64);
     FSTAMP(4);
@@ -438,6 +508,15 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void cnn_fwd_wino_k(CnnArgs a) {
 #undef FSTAMP
 }
 
+__global__ __launch_bounds__(64 * FWD_WAVES) void cnn_fwd_wino_k(CnnArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  cnn_fwd_wino_body<false>(a, smem);
+}
+__global__ __launch_bounds__(64 * FWD_WAVES) void cnn_fwd_wino_save_k(CnnArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  cnn_fwd_wino_body<true>(a, smem);
+}
+
 constexpr size_t kFwdLds = (size_t)(ESZ + NCH * CH) * sizeof(float);
 constexpr size_t kWinoLds = (size_t)(2 * WESZ + 2 * A1SZ + 2 * 2 * 16 * 64 + 9 * NCH) * sizeof(float);   // + the split items' exchange, the W1 table
 static_assert(kWinoLds <= 160 * 1024, "one workgroup per CU");
@@ -448,19 +527,30 @@ constexpr unsigned kFwdGrid = 512;                   // direct kernel: 512 measu
 
 extern "C" {
 
+int64_t gnf_mnistcnn_conv_a1_bytes(int64_t n_img) { return n_img < 0 ? 0 : n_img * SAVE_IMG * (int64_t)sizeof(float); }
+
 int gnf_mnistcnn_conv_fwd(const float* e, const float* W1, const float* b1, const float* W2, const float* b2,
                           float* pooled, unsigned char* argmax, int64_t n_img, int exact_ties, gnf_stream_t stream) {
+  return gnf_mnistcnn_conv_fwd_save(e, W1, b1, W2, b2, pooled, argmax, nullptr, n_img, exact_ties, stream);
+}
+
+int gnf_mnistcnn_conv_fwd_save(const float* e, const float* W1, const float* b1, const float* W2, const float* b2,
+                               float* pooled, unsigned char* argmax, float* a1save, int64_t n_img, int exact_ties,
+                               gnf_stream_t stream) {
   if (!W1 || !b1 || !W2 || !b2 || n_img < 0) return GNF_EINVAL;
+  if (exact_ties && a1save) return GNF_EINVAL;      // the direct kernel keeps nothing: its callers recompute
+  if (a1save && ((uintptr_t)a1save & 15)) return GNF_EINVAL;
   if (n_img == 0) return 0;                // image-sized arrays may be NULL for an empty batch
   if (!e || !pooled || !argmax) return GNF_EINVAL;
   CnnArgs a{};
   a.e = e; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.pooled = pooled; a.arg = argmax; a.n = n_img;
+  a.a1save = a1save;
   if (exact_ties) {                                 // direct implicit GEMM: bit-equal outputs for equal patches
     const unsigned grid = n_img < kFwdGrid ? (unsigned)n_img : kFwdGrid;
     return (int)gnf_launch_lds(cnn_fwd_k, dim3(grid), dim3(64 * FWD_WAVES), kFwdLds, (hipStream_t)stream, a);
   }
   const unsigned grid = n_img < kWinoGrid ? (unsigned)n_img : kWinoGrid;
-  return (int)gnf_launch_lds(cnn_fwd_wino_k, dim3(grid), dim3(64 * FWD_WAVES), kWinoLds, (hipStream_t)stream, a);
+  return (int)gnf_launch_lds(a1save ? cnn_fwd_wino_save_k : cnn_fwd_wino_k, dim3(grid), dim3(64 * FWD_WAVES), kWinoLds, (hipStream_t)stream, a);
 }
 
 }  // extern "C"

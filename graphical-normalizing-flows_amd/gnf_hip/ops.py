@@ -405,22 +405,52 @@ def mlp(x, layers, masks=None, relu_in=False, degs=None):
 
 
 # ----------------------------------------------------------------------------- MNISTCNN conv front
+A1_SAVE_CAP_DEFAULT = 8 << 30      # bytes; policy, not a measurement: B <= 219 at d = 784 (46 720 B per image)
+
+
+def _a1_buffer(n, like, will_backward, exact_ties):
+    """Buffer for the conv1 activations of n images that the Winograd forward keeps for the backward (which then loads
+    them instead of recomputing conv1 on the ALU that bounds it), or None: no backward will come, exact_ties (the direct
+    forward keeps nothing), GNF_CONV_SAVE_A1=0 (the A/B switch), or more bytes than the cap GNF_CONV_SAVE_A1_MAX_BYTES
+    (default 8 GiB).  None selects the recompute entry points.  The buffer lives and dies with the autograd node.
+    will_backward must come from OUTSIDE the Function: inside `forward` grad mode is always off and
+    `ctx.needs_input_grad` follows `requires_grad` of the inputs alone, also under `no_grad`."""
+    if not will_backward or exact_ties or n <= 0 or os.environ.get("GNF_CONV_SAVE_A1", "1") == "0":
+        return None
+    nbytes = int(abi.load().gnf_mnistcnn_conv_a1_bytes(n))
+    if nbytes > int(os.environ.get("GNF_CONV_SAVE_A1_MAX_BYTES", A1_SAVE_CAP_DEFAULT)):
+        return None
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=like.device)
+
+
+def _conv_fwd(e, W1c, b1c, W2c, b2c, pooled, arg, a1, n, exact_ties):
+    if a1 is None:
+        call("gnf_mnistcnn_conv_fwd", ptr(e), ptr(W1c), ptr(b1c), ptr(W2c), ptr(b2c), ptr(pooled), abi.rawptr(arg), n,
+             int(bool(exact_ties)), stream())
+    else:
+        call("gnf_mnistcnn_conv_fwd_save", ptr(e), ptr(W1c), ptr(b1c), ptr(W2c), ptr(b2c), ptr(pooled), abi.rawptr(arg),
+             ptr(a1), n, int(bool(exact_ties)), stream(), profile_as="gnf_mnistcnn_conv_fwd")
+
+
 class MnistConvFn(torch.autograd.Function):
     """flatten(max_pool2d(conv2(relu(conv1(e))), 2)) for 28x28 single-channel images
-    (models/MLP.py:36-43), fused in LDS; backward recomputes conv1 in-kernel."""
+    (models/MLP.py:36-43), fused in LDS; the backward loads the conv1 activations the forward kept (_a1_buffer) or
+    recomputes conv1 in-kernel."""
 
     @staticmethod
-    def forward(ctx, e, W1, b1, W2, b2, exact_ties=False):
+    def forward(ctx, e, W1, b1, W2, b2, exact_ties=False, grad_mode=None):
         """exact_ties: direct-convolution forward whose pool argmax follows torch's first-maximum rule on exactly tied
-        windows (include/gnf_hip.h); the Winograd forward otherwise"""
+        windows (include/gnf_hip.h); the Winograd forward otherwise.  grad_mode: torch.is_grad_enabled() at the call
+        (mnist_conv hands it in); a bare .apply without it keeps nothing and recomputes"""
         e = e.contiguous()
         n = e.shape[0]
         W1c, b1c, W2c, b2c = W1.contiguous(), b1.contiguous(), W2.contiguous(), b2.contiguous()
         pooled = _empty((n, 2304), e)
         arg = torch.empty((n, 2304), dtype=torch.uint8, device=e.device)
-        call("gnf_mnistcnn_conv_fwd", ptr(e), ptr(W1c), ptr(b1c), ptr(W2c), ptr(b2c), ptr(pooled), abi.rawptr(arg), n,
-             int(bool(exact_ties)), stream())
+        a1 = _a1_buffer(n, e, bool(grad_mode) and any(ctx.needs_input_grad), exact_ties)
+        _conv_fwd(e, W1c, b1c, W2c, b2c, pooled, arg, a1, n, exact_ties)
         ctx.save_for_backward(e, W1c, b1c, W2c, b2c, arg)
+        ctx.a1 = a1                        # an intermediate, not an output: freed with the node
         return pooled
 
     @staticmethod
@@ -432,9 +462,18 @@ class MnistConvFn(torch.autograd.Function):
         gW1, gb1, gW2, gb2 = grad_out(W1), grad_out(b1), grad_out(W2), grad_out(b2)
         nws = abi.load().gnf_mnistcnn_conv_bwd_ws_bytes(n)
         ws = _ws(nws, e)
-        call("gnf_mnistcnn_conv_bwd", ptr(e), ptr(W1), ptr(b1), ptr(W2), ptr(gp), abi.rawptr(arg), ptr(ge), ptr(gW1),
-             ptr(gb1), ptr(gW2), ptr(gb2), abi.rawptr(ws), nws, n, stream())
-        return ge, gW1, gb1, gW2, gb2, None
+        if ctx.a1 is None:
+            call("gnf_mnistcnn_conv_bwd", ptr(e), ptr(W1), ptr(b1), ptr(W2), ptr(gp), abi.rawptr(arg), ptr(ge), ptr(gW1),
+                 ptr(gb1), ptr(gW2), ptr(gb2), abi.rawptr(ws), nws, n, stream())
+        else:
+            call("gnf_mnistcnn_conv_bwd_a1", ptr(e), ptr(ctx.a1), ptr(W1), ptr(b1), ptr(W2), ptr(gp), abi.rawptr(arg),
+                 ptr(ge), ptr(gW1), ptr(gb1), ptr(gW2), ptr(gb2), abi.rawptr(ws), nws, n, stream(),
+                 profile_as="gnf_mnistcnn_conv_bwd")
+        return ge, gW1, gb1, gW2, gb2, None, None
+
+
+def mnist_conv(e, W1, b1, W2, b2, exact_ties=False):
+    return MnistConvFn.apply(e, W1, b1, W2, b2, exact_ties, torch.is_grad_enabled())
 
 
 def crop_origin(p):
@@ -685,10 +724,10 @@ class DagConvFrontFn(torch.autograd.Function):
         W1c, b1c, W2c, b2c = W1.contiguous(), b1.contiguous(), W2.contiguous(), b2.contiguous()
         pooled = _empty((n, 2304), x)
         arg = torch.empty((n, 2304), dtype=torch.uint8, device=x.device)
-        call("gnf_mnistcnn_conv_fwd", ptr(e), ptr(W1c), ptr(b1c), ptr(W2c), ptr(b2c), ptr(pooled), abi.rawptr(arg), n,
-             int(bool(exact_ties)), stream())
+        a1 = _a1_buffer(n, x, bool(grad_mode) and any(ctx.needs_input_grad), exact_ties)
+        _conv_fwd(e, W1c, b1c, W2c, b2c, pooled, arg, a1, n, exact_ties)
         ctx.save_for_backward(x, A, u1, u2, e, W1c, b1c, W2c, b2c, arg)
-        ctx.tab, ctx.plan = (tab if B > 0 else None), plan
+        ctx.tab, ctx.plan, ctx.a1 = (tab if B > 0 else None), plan, a1
         ctx.cfg = (imp_mode, gate_mode, float(h_thresh), float(temperature), seed, offset)
         return pooled
 
@@ -706,9 +745,15 @@ class DagConvFrontFn(torch.autograd.Function):
         ws = _ws(nws, x)
         plan = ctx.plan
         gec = _empty((n, abi.DAG_PLAN_KC), x) if plan is not None else None
-        call("gnf_mnistcnn_conv_bwd_cols", ptr(e), ptr(W1), ptr(b1), ptr(W2), ptr(gp), abi.rawptr(arg), ptr(ge),
-             abi.rawptr(plan) if plan is not None else None, d, ptr(gec), ptr(gW1), ptr(gb1), ptr(gW2), ptr(gb2),
-             abi.rawptr(ws), nws, n, stream())
+        if ctx.a1 is None:
+            call("gnf_mnistcnn_conv_bwd_cols", ptr(e), ptr(W1), ptr(b1), ptr(W2), ptr(gp), abi.rawptr(arg), ptr(ge),
+                 abi.rawptr(plan) if plan is not None else None, d, ptr(gec), ptr(gW1), ptr(gb1), ptr(gW2), ptr(gb2),
+                 abi.rawptr(ws), nws, n, stream())
+        else:
+            call("gnf_mnistcnn_conv_bwd_cols_a1", ptr(e), ptr(ctx.a1), ptr(W1), ptr(b1), ptr(W2), ptr(gp),
+                 abi.rawptr(arg), ptr(ge), abi.rawptr(plan) if plan is not None else None, d, ptr(gec), ptr(gW1),
+                 ptr(gb1), ptr(gW2), ptr(gb2), abi.rawptr(ws), nws, n, stream(),
+                 profile_as="gnf_mnistcnn_conv_bwd_cols")
         gA, finish, acc = (grad_out_shared(A, accumulate_ok=plan is not None) if ctx.needs_input_grad[1]
                            else (None, None, False))
         gx = _empty((B, d), x) if ctx.needs_input_grad[0] else None

@@ -138,8 +138,8 @@ class MNISTCNN(nn.Module):
     def forward(self, x, context=None):
         rows = x.shape[0]
         if self._fused_front(x):
-            feat = ops.MnistConvFn.apply(x.view(-1, 784), self.conv1.weight, self.conv1.bias, self.conv2.weight,
-                                         self.conv2.bias, self.exact_pool_ties)
+            feat = ops.mnist_conv(x.view(-1, 784), self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias,
+                                  self.exact_pool_ties)
         elif self._embeddable(x):
             # the 14x14 / 7x7 scales of the multi-scale factory: the image sits in the top-left corner of a zero 28x28
             # one.  Valid convolutions never look across the corner's edge for the output positions that exist in the
@@ -147,8 +147,8 @@ class MNISTCNN(nn.Module):
             # necessary area, still several times cheaper than an im2col round trip through HBM)
             _, h, w = self.size_img
             big = F.pad(x.view(-1, 1, h, w), (0, 28 - w, 0, 28 - h)).view(-1, 784)
-            pooled = ops.MnistConvFn.apply(big, self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias,
-                                           self.exact_pool_ties)
+            pooled = ops.mnist_conv(big, self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias,
+                                    self.exact_pool_ties)
             feat = pooled.view(-1, 16, 12, 12)[:, :, :(h - 4) // 2, :(w - 4) // 2].reshape(rows, -1)
         else:
             # any other geometry: batched im2col + MFMA GEMM (no MIOpen: its find step costs minutes on this stack)

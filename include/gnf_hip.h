@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GNF_ABI_VERSION 8
+#define GNF_ABI_VERSION 9
 #define GNF_EINVAL (-1)   /* bad argument (null pointer, negative size, ...)          */
 #define GNF_ESHAPE (-2)   /* shape not supported by any compiled kernel instantiation */
 #define GNF_EWS    (-3)   /* workspace too small                                      */
@@ -350,6 +350,26 @@ int gnf_mnistcnn_conv_bwd_cols(const float* e, const float* W1, const float* b1,
                                float* ge, const int32_t* plan, int64_t d_plan, float* ge_cols,
                                float* gW1, float* gb1, float* gW2, float* gb2,
                                void* ws, int64_t ws_bytes, int64_t n_img, gnf_stream_t stream);
+/* The Winograd pair with the conv1 + ReLU activations kept by the forward instead of recomputed by the backward: the
+ * recompute sits on the fp32 ALU that bounds the backward, the stream on a memory system both kernels leave idle.
+ * a1save / a1saved: gnf_mnistcnn_conv_a1_bytes(n_img) bytes, 16-byte aligned -- per image [16 channels][730] floats, rows of
+ * pitch 28 (the backward's LDS image); columns 26, 27 of every row and the entries 728, 729 of every channel are written as
+ * zeros and the backward RELIES on that.  gnf_mnistcnn_conv_fwd_save with a1save == NULL is gnf_mnistcnn_conv_fwd; with
+ * exact_ties = 1 (the direct kernel keeps nothing) a1save must be NULL.  The _a1 backwards take the arguments of their
+ * namesakes plus a1saved and return the same bits. */
+int64_t gnf_mnistcnn_conv_a1_bytes(int64_t n_img);
+int gnf_mnistcnn_conv_fwd_save(const float* e, const float* W1, const float* b1, const float* W2, const float* b2,
+                               float* pooled, unsigned char* argmax, float* a1save, int64_t n_img, int exact_ties,
+                               gnf_stream_t stream);
+int gnf_mnistcnn_conv_bwd_a1(const float* e, const float* a1saved, const float* W1, const float* b1, const float* W2,
+                             const float* g_pooled, const unsigned char* argmax,
+                             float* ge, float* gW1, float* gb1, float* gW2, float* gb2,
+                             void* ws, int64_t ws_bytes, int64_t n_img, gnf_stream_t stream);
+int gnf_mnistcnn_conv_bwd_cols_a1(const float* e, const float* a1saved, const float* W1, const float* b1, const float* W2,
+                                  const float* g_pooled, const unsigned char* argmax,
+                                  float* ge, const int32_t* plan, int64_t d_plan, float* ge_cols,
+                                  float* gW1, float* gb1, float* gW2, float* gb2,
+                                  void* ws, int64_t ws_bytes, int64_t n_img, gnf_stream_t stream);
 
 /* ---- sparse masked-image front for a DETERMINISTIC DAG gate ---------------
  * Replaces, for evaluation / sampling, the chain  e = x * P[i]  (DAGConditioner.py:142-153, deterministic branches)

@@ -1,26 +1,39 @@
 """A/B timing of the dense conv kernels: builds gnf_mnistcnn.hip (+ gnf_rowwise.hip) with the given extra hipcc flags
 into a scratch library and times the forward / backward entry points at the cfg4 size (78 400 images) with HIP events.
-    python tools/bench_cnn.py [-DFOO ...] [--label NAME]"""
+    python tools/bench_cnn.py [-DFOO ...] [--label NAME] [--saved-a1] [--build-only PATH | --lib PATH]
+--saved-a1 also times the pair that streams the conv1 activations through HBM (forward with a1save, backward with a1saved).
+--build-only PATH compiles the scratch library to PATH and exits (no GPU needed); --lib PATH times a library built that way."""
 import ctypes, subprocess, sys, os
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = ROOT + '/graphical-normalizing-flows_amd/gnf_hip/csrc/'
-flags = [a for a in sys.argv[1:] if a.startswith('-') and a != '--label']
-label = sys.argv[sys.argv.index('--label') + 1] if '--label' in sys.argv else ' '.join(flags) or 'default'
-so = '/tmp/libgnf_cnn_ab_%d.so' % os.getpid()
+OPTS = ('--label', '--saved-a1', '--build-only', '--lib')
+flags = [a for a in sys.argv[1:] if a.startswith('-') and a not in OPTS]
+
+
+def opt(name):
+    return sys.argv[sys.argv.index(name) + 1] if name in sys.argv else None
+
+
+label = opt('--label') or ' '.join(flags) or 'default'
+prebuilt, build_only = opt('--lib'), opt('--build-only')
+so = prebuilt or build_only or '/tmp/libgnf_cnn_ab_%d.so' % os.getpid()
 sys.path.insert(0, ROOT + '/graphical-normalizing-flows_amd')
 from gnf_hip.build import EXTRA_FLAGS   # the product's per-file flags apply here too
 from _warm import warm_gpu  # noqa: E402
 objs = []
-for f in (os.environ.get('GNF_CNN_FWD_SRC', 'gnf_mnistcnn_fwd.hip'), os.environ.get('GNF_CNN_BWD_SRC', 'gnf_mnistcnn.hip'),
+for f in () if prebuilt else (os.environ.get('GNF_CNN_FWD_SRC', 'gnf_mnistcnn_fwd.hip'), os.environ.get('GNF_CNN_BWD_SRC', 'gnf_mnistcnn.hip'),
           'gnf_rowwise.hip'):                                       # A/B against other sources in csrc/
     o = '/tmp/cnn_ab_%d_%s.o' % (os.getpid(), f)
     subprocess.run(['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value'] + EXTRA_FLAGS.get(f, EXTRA_FLAGS.get('gnf_mnistcnn_fwd.hip' if 'fwd' in f else 'gnf_mnistcnn.hip', []) if 'mnistcnn' in f else []) + flags +
                    ['-I' + ROOT + '/include', '-I' + src, '-c', src + f, '-o', o], check=True)
     objs.append(o)
-subprocess.run(['hipcc', '--offload-arch=gfx950', '-shared', '-fPIC', '-o', so] + objs, check=True)
+if not prebuilt:
+    subprocess.run(['hipcc', '--offload-arch=gfx950', '-shared', '-fPIC', '-o', so] + objs, check=True)
 for o in objs:
     os.remove(o)
+if build_only:
+    sys.exit(0)
 lib = ctypes.CDLL(so)
 n = 78400
 dev = 'cuda:0'
@@ -73,6 +86,34 @@ def bwd_cols():
                                           ctypes.c_int64(n), st)
 
 
+# the saved-a1 pair: the forward keeps the conv1 activations (46 720 B per image), the backward loads them
+SAVED = '--saved-a1' in sys.argv
+if SAVED:
+    lib.gnf_mnistcnn_conv_a1_bytes.restype = ctypes.c_int64
+    a1 = torch.empty(lib.gnf_mnistcnn_conv_a1_bytes(ctypes.c_int64(n)) // 4, device=dev)
+
+
+def fwd_save():
+    return lib.gnf_mnistcnn_conv_fwd_save(P(e.data_ptr()), P(W1.data_ptr()), P(b1.data_ptr()), P(W2.data_ptr()), P(b2.data_ptr()),
+                                          P(pooled.data_ptr()), P(arg.data_ptr()), P(a1.data_ptr()), ctypes.c_int64(n),
+                                          ctypes.c_int(0), st)
+
+
+def bwd_a1():
+    return lib.gnf_mnistcnn_conv_bwd_a1(P(e.data_ptr()), P(a1.data_ptr()), P(W1.data_ptr()), P(b1.data_ptr()), P(W2.data_ptr()),
+                                        P(gp.data_ptr()), P(arg.data_ptr()), P(ge.data_ptr()), P(g[0].data_ptr()),
+                                        P(g[1].data_ptr()), P(g[2].data_ptr()), P(g[3].data_ptr()), P(ws.data_ptr()),
+                                        ctypes.c_int64(nws), ctypes.c_int64(n), st)
+
+
+def bwd_cols_a1():
+    return lib.gnf_mnistcnn_conv_bwd_cols_a1(P(e.data_ptr()), P(a1.data_ptr()), P(W1.data_ptr()), P(b1.data_ptr()),
+                                             P(W2.data_ptr()), P(gp.data_ptr()), P(arg.data_ptr()), P(ge.data_ptr()),
+                                             P(plan.data_ptr()), ctypes.c_int64(784), P(gec.data_ptr()), P(g[0].data_ptr()),
+                                             P(g[1].data_ptr()), P(g[2].data_ptr()), P(g[3].data_ptr()), P(ws.data_ptr()),
+                                             ctypes.c_int64(nws), ctypes.c_int64(n), st)
+
+
 def timeit(fn, reps=15):
     warm_gpu()
     for _ in range(3):
@@ -100,4 +141,18 @@ if HAS_COLS:
         bad += int((gec[on, k] != ge[on.nonzero().flatten(), cd[rows, k][on]]).sum())
     print("[%s] conv bwd, compact de (MNIST window plan) %.4f ms   mismatching ge_cols entries %d   gW2 equal %s gW1 equal %s"
           % (label, tc, bad, bool(torch.equal(g2d, g[2])), bool(torch.equal(g0d, g[0]))))
-os.remove(so)
+if SAVED and not HAS_COLS:
+    raise SystemExit("--saved-a1 compares against gnf_mnistcnn_conv_bwd_cols, which this library does not have")
+if SAVED:
+    gec_r, g_r = gec.clone(), [t.clone() for t in g]      # (g, gec: of the last call above, the plan form)
+    assert bwd() == 0
+    ge_r = ge.clone()
+    tfs, tbs = timeit(fwd_save), timeit(bwd_a1)
+    same_d = torch.equal(ge, ge_r)
+    tcs = timeit(bwd_cols_a1)
+    on = cd[rows] >= 0
+    same_c = torch.equal(gec[on], gec_r[on]) and all(torch.equal(x, y) for x, y in zip(g, g_r))
+    print("[%s] saved a1: conv fwd %.4f ms (%+.4f)   conv bwd %.4f ms (%+.4f)   compact de %.4f ms (%+.4f)   bit-equal to the "
+          "recompute: dense ge %s, plan %s" % (label, tfs, tfs - tf, tbs, tbs - tb, tcs, tcs - tc, same_d, same_c))
+if not prebuilt:
+    os.remove(so)
