@@ -20,14 +20,24 @@ c_u64 = ctypes.c_uint64
 c_stream = ctypes.c_void_p
 
 MONO_MAX_LAYERS = 8
+MADE_MAX_HIDDEN = 8       # GNF_MADE_MAX_HIDDEN
+MADE_NORM_NONE, MADE_NORM_AFFINE = 0, 1
 DAG_PLAN_KC = 32          # GNF_DAG_PLAN_KC
-ABI_VERSION = 9           # GNF_ABI_VERSION of include/gnf_hip.h this binding was written against
+ABI_VERSION = 10          # GNF_ABI_VERSION of include/gnf_hip.h this binding was written against
 
 
 class MonoNet(ctypes.Structure):
     """gnf_mono_net (include/gnf_hip.h)."""
     _fields_ = [("nl", c_int), ("dims", c_int * (MONO_MAX_LAYERS + 1)),
                 ("W", ctypes.c_void_p * MONO_MAX_LAYERS), ("b", ctypes.c_void_p * MONO_MAX_LAYERS)]
+
+
+class MadeNet(ctypes.Structure):
+    """gnf_made_net (include/gnf_hip.h)."""
+    _fields_ = [("nh", c_int), ("d", c_int), ("out", c_int), ("max_new", c_int), ("width", c_int * MADE_MAX_HIDDEN),
+                ("W", ctypes.c_void_p * (MADE_MAX_HIDDEN + 1)), ("b", ctypes.c_void_p * (MADE_MAX_HIDDEN + 1)),
+                ("order", ctypes.c_void_p * MADE_MAX_HIDDEN), ("off", ctypes.c_void_p * MADE_MAX_HIDDEN),
+                ("var_of_step", ctypes.c_void_p)]
 
 
 # name -> (restype, argtypes); must list every symbol include/gnf_hip.h declares
@@ -98,6 +108,11 @@ SIGNATURES = {
                                       c_f, c_f, c_f, c_i64, c_i64, c_i64, ctypes.POINTER(ctypes.c_void_p),
                                       ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, c_i64, c_i64, c_i64, c_stream]),
     "gnf_monotonic_bwd_kernel": (ctypes.c_char_p, []),
+    "gnf_made_prefix_pack_floats": (c_i64, [ctypes.POINTER(MadeNet)]),
+    "gnf_made_prefix_pack": (c_int, [ctypes.POINTER(MadeNet), c_f, c_stream]),
+    "gnf_made_prefix_ws_bytes": (c_i64, [ctypes.POINTER(MadeNet), c_i64]),
+    "gnf_made_prefix": (c_int, [ctypes.POINTER(MadeNet), c_f, c_f, c_f, c_f, c_int, c_int, c_int, c_i64, ctypes.c_void_p,
+                                c_i64, c_stream]),
     "gnf_dag_loss_prep": (c_int, [c_f, c_f, c_float, c_f, c_i64, c_stream]),
     "gnf_dag_loss_value": (c_int, [c_f, c_f, c_f, c_f, c_float, c_f, c_f, c_f, c_f, c_int, c_f, c_f, c_i64, c_stream]),
     "gnf_dag_loss_bwd": (c_int, [c_f, c_f, c_f, c_f, c_f, c_i64, c_stream]),

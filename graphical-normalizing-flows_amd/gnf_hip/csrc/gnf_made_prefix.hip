@@ -1,0 +1,317 @@
+// Prefix evaluation of a MADE (models/Conditionners/AutoregressiveConditioner.py): the conditioner side of inverting an
+// autoregressive flow step column by column instead of by d fixed-point passes (reference NormalizingFlow.py:98-107).
+//
+// A hidden unit of degree m reads inputs of degree <= m only, so it is FINAL once the variables of degree 0..m are known.
+// Step t (the variable of degree t is inverted in it) therefore computes, layer by layer, just the hidden units of degree
+// t-1 from the already-final units below them, then the `out` outputs of that one variable.  Units and inputs are kept in
+// DEGREE order (the plan's stable sort), which makes "every unit of degree < t" a contiguous K range [0, off[t]) of the
+// activation row and of the packed weight rows: no mask is read, the prefix length IS the mask.
+//
+// One workgroup owns TB batch rows and walks the steps [t0, t1) for them; rows never interact, so nothing is synchronised
+// across workgroups.  The rows' activations live in LDS when one launch runs the whole inversion (Affine normalizer:
+// x[b, v] = (z - mu) / sigma is formed right here and is the next step's input), otherwise in the caller's workspace,
+// which carries them from one single-step launch to the next (any other normalizer inverts the column in between).
+//
+// Two inner products, chosen per (layer, step) by the number of new units n:
+//   n >= 8 (and TB = 16): v_mfma_f32_16x16x4_f32, batch rows on M, the new units padded to 16 on N, K split over the four
+//           wavefronts in chunks of 16 and reduced through LDS in a fixed order;
+//   n <  8: plain dot products, 256 / TB lanes per batch row over K, reduced inside the lane group.
+// fp32 throughout, fp32 accumulation, a fixed summation order for a given (net, B).
+#include "gnf_common.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxH = GNF_MADE_MAX_HIDDEN;
+constexpr int kLdsBytes = 160 * 1024;
+constexpr int kRedFloats = 4 * 256;          // the four wavefronts' partial 16 x 16 tiles
+
+__host__ __device__ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// what host and device agree on: the activation row and the packed parameter image
+struct MadeLayout {
+  int nh, d, out;
+  int A;                        // floats per activation row: [x in degree order | hidden layer 0 | ... ], made odd
+  int width[kMaxH];
+  int act_off[kMaxH];           // first column of hidden layer l in the activation row (the inputs start at 0)
+  int K[kMaxH + 1];             // in_features of layer l (l = nh: the output layer)
+  int ldw[kMaxH + 1];           // K rounded up to 16: row pitch of the packed weights, the tail zero-filled
+  int rows[kMaxH + 1];          // out_features
+  int64_t w_off[kMaxH + 1];     // float offsets into the pack
+  int64_t b_off[kMaxH + 1];
+  int64_t pack_floats;
+};
+
+int make_layout(const gnf_made_net* net, MadeLayout* lay) {
+  if (!net || net->nh < 0 || net->nh > kMaxH || net->d <= 0 || net->out <= 0) return GNF_EINVAL;
+  lay->nh = net->nh; lay->d = net->d; lay->out = net->out;
+  int64_t A = net->d, off = 0;
+  for (int l = 0; l <= net->nh; ++l) {
+    if (l < net->nh) {
+      if (net->width[l] <= 0) return GNF_EINVAL;
+      lay->width[l] = net->width[l];
+      lay->act_off[l] = (int)A;
+      A += net->width[l];
+    }
+    lay->K[l] = l == 0 ? net->d : net->width[l - 1];
+    lay->rows[l] = l < net->nh ? net->width[l] : net->d * net->out;
+    if ((int64_t)net->d * net->out > (1 << 30) || A > (1 << 30)) return GNF_ESHAPE;
+    lay->ldw[l] = round_up(lay->K[l], 16);
+    lay->w_off[l] = off;
+    off += (int64_t)lay->rows[l] * lay->ldw[l];
+    lay->b_off[l] = off;
+    off += round_up(lay->rows[l], 4);
+  }
+  lay->A = (int)A | 1;          // an odd pitch spreads the 16 rows of an MFMA operand read over the LDS banks
+  lay->pack_floats = off;
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ the weight image
+struct PackArgs {
+  MadeLayout lay;
+  const float* W[kMaxH + 1];
+  const float* b[kMaxH + 1];
+  const int32_t* order[kMaxH];
+  const int32_t* var_of_step;
+};
+
+// hidden layer l: Wp[u'][k'] = W[order_l[u']][order_{l-1}[k']] (order_{-1} = var_of_step); output layer: row t * out + c is
+// output neuron c * d + var_of_step[t].  Columns K .. ldw-1 are zeros.
+__global__ void made_prefix_pack_k(PackArgs a, float* __restrict__ pack) {
+  const MadeLayout& L = a.lay;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < L.pack_floats; e += (int64_t)gridDim.x * blockDim.x) {
+    int l = 0;
+    while (l < L.nh && e >= L.w_off[l + 1]) ++l;
+    const int32_t* in_order = l == 0 ? a.var_of_step : a.order[l - 1];
+    float v = 0.f;
+    if (e < L.b_off[l]) {
+      const int64_t i = e - L.w_off[l];
+      const int r = (int)(i / L.ldw[l]), k = (int)(i - (int64_t)r * L.ldw[l]);
+      const int src = l < L.nh ? a.order[l][r] : (r % L.out) * L.d + a.var_of_step[r / L.out];
+      if (k < L.K[l]) v = a.W[l][(int64_t)src * L.K[l] + in_order[k]];
+    } else {
+      const int r = (int)(e - L.b_off[l]);
+      if (r < L.rows[l]) v = a.b[l][l < L.nh ? a.order[l][r] : (r % L.out) * L.d + a.var_of_step[r / L.out]];
+    }
+    pack[e] = v;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ the step kernel
+struct StepArgs {
+  MadeLayout lay;
+  const int32_t* off[kMaxH];
+  const int32_t* var_of_step;
+};
+
+__device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f : v; }
+
+// dst[r][u] = act(bias[u] + sum_{k < K} W[u][k] in[r][k]) for the n units u of this step and the tile's rows r < nrows.
+// W points at the first of those units' packed rows (rows_avail of them follow in the image).  Ends in a barrier.
+template <int TB>
+__device__ __forceinline__ void layer_step(const float* __restrict__ W, int ldw, int rows_avail,
+                                           const float* __restrict__ bias, int n, int K, const float* in, int A,
+                                           float* dst, int dstride, bool relu, int nrows, float* red) {
+  const int tid = threadIdx.x;
+  if (TB == 16 && n >= 8) {
+    const int wave = tid >> 6, lane = tid & 63, m = lane & 15, q = lane >> 4;
+    const float* a = in + (size_t)(m < nrows ? m : nrows - 1) * A;
+    const int nchunks = (K + 15) >> 4;
+    for (int nt = 0; nt * 16 < n; ++nt) {
+      // B operand: lane (m, q) holds column m of the tile = unit nt * 16 + m (a padding column reads a row that exists)
+      const int urow = nt * 16 + m < rows_avail ? nt * 16 + m : rows_avail - 1;
+      const float* w = W + (size_t)urow * ldw + 4 * q;
+      f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+      for (int ch = wave; ch < nchunks; ch += 4) {
+        // MFMA i of a chunk contracts k = 16 ch + 4 q + i over q = 0..3: both operands use that same order
+        const int kb = ch * 16 + 4 * q;
+        const f32x4 wv = ld4(w + ch * 16);
+        const float a0 = kb < K ? a[kb] : 0.f;
+        const float a1 = kb + 1 < K ? a[kb + 1] : 0.f;
+        const float a2 = kb + 2 < K ? a[kb + 2] : 0.f;
+        const float a3 = kb + 3 < K ? a[kb + 3] : 0.f;
+        c0 = mfma(a0, wv[0], c0);
+        c1 = mfma(a1, wv[1], c1);
+        c0 = mfma(a2, wv[2], c0);
+        c1 = mfma(a3, wv[3], c1);
+      }
+      c0 += c1;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[wave * 256 + (q * 4 + r) * 16 + m] = c0[r];     // D: row 4 q + r, column m
+      __syncthreads();
+      {
+        const int rm = tid >> 4, u = nt * 16 + (tid & 15);
+        if (u < n && rm < nrows) {
+          const float v = ((red[tid] + red[256 + tid]) + red[512 + tid]) + red[768 + tid] + bias[u];
+          dst[(size_t)rm * dstride + u] = relu ? relu_keep_nan(v) : v;
+        }
+      }
+      __syncthreads();
+    }
+    return;
+  }
+  constexpr int G = kThreads / TB;             // lanes per batch row: 16 / 32 / 64, an aligned part of one wavefront
+  const int r = tid / G, j = tid % G;
+  const float* a = in + (size_t)(r < nrows ? r : nrows - 1) * A;
+  for (int u = 0; u < n; ++u) {
+    const float* w = W + (size_t)u * ldw;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int k = j;
+    for (; k + 3 * G < K; k += 4 * G) {          // four weight loads in flight: the row comes from L2, the step is latency
+      const float w0 = w[k], w1 = w[k + G], w2 = w[k + 2 * G], w3 = w[k + 3 * G];
+      s0 = fmaf(w0, a[k], s0);
+      s1 = fmaf(w1, a[k + G], s1);
+      s2 = fmaf(w2, a[k + 2 * G], s2);
+      s3 = fmaf(w3, a[k + 3 * G], s3);
+    }
+    for (; k < K; k += G) s0 = fmaf(w[k], a[k], s0);
+    const float v = group_sum<G>((s0 + s1) + (s2 + s3)) + bias[u];
+    if (j == 0 && r < nrows) dst[(size_t)r * dstride + u] = relu ? relu_keep_nan(v) : v;
+  }
+  __syncthreads();
+}
+
+template <int TB, bool kLds>
+__global__ __launch_bounds__(kThreads) void made_prefix_k(StepArgs s, const float* __restrict__ pack,
+                                                          const float* __restrict__ z, float* x, float* __restrict__ h_out,
+                                                          int t0, int t1, int mode, float* ws, int64_t B) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const MadeLayout& L = s.lay;
+  float* red = smem;
+  float* hbuf = smem + kRedFloats;                                   // [TB][out]: the step's conditioner outputs
+  const int tid = threadIdx.x;
+  const int64_t row0 = (int64_t)blockIdx.x * TB;
+  const int nrows = (int)(B - row0 < TB ? B - row0 : TB);
+  const int A = L.A, d = L.d, out = L.out, nh = L.nh;
+  float* act = kLds ? hbuf + round_up(TB * out, 4) : ws + (size_t)row0 * A;
+
+  if (!kLds && t0 >= 1) {
+    // the column the caller inverted since the previous launch: the newest input of this one
+    if (tid < nrows) act[(size_t)tid * A + t0 - 1] = x[(row0 + tid) * d + s.var_of_step[t0 - 1]];
+    __syncthreads();
+  }
+  for (int t = t0; t < t1; ++t) {
+    const int v = s.var_of_step[t];
+    // the step's z is asked for before the layers, which hide its latency
+    const float zv = mode == GNF_MADE_NORM_AFFINE && tid < nrows ? z[(row0 + tid) * d + v] : 0.f;
+    if (t >= 1)
+      for (int l = 0; l < nh; ++l) {
+        const int n0 = s.off[l][t - 1], n1 = s.off[l][t];             // the units of degree t - 1
+        const int K = l == 0 ? t : s.off[l - 1][t];                    // inputs / units below of degree <= t - 1
+        layer_step<TB>(pack + L.w_off[l] + (size_t)n0 * L.ldw[l], L.ldw[l], L.rows[l] - n0, pack + L.b_off[l] + n0,
+                       n1 - n0, K, act + (l == 0 ? 0 : L.act_off[l - 1]), A, act + L.act_off[l] + n0, A, true, nrows, red);
+      }
+    {
+      const int K = nh == 0 ? t : s.off[nh - 1][t];                    // strict rule: degree < t
+      const int n0 = t * out;
+      layer_step<TB>(pack + L.w_off[nh] + (size_t)n0 * L.ldw[nh], L.ldw[nh], L.rows[nh] - n0, pack + L.b_off[nh] + n0,
+                     out, K, act + (nh == 0 ? 0 : L.act_off[nh - 1]), A, hbuf, out, false, nrows, red);
+    }
+    if (mode == GNF_MADE_NORM_NONE) {
+      for (int i = tid; i < nrows * out; i += kThreads) h_out[row0 * out + i] = hbuf[i];
+    } else if (tid < nrows) {
+      // AffineNormalizer.py:14-17, the arithmetic of gnf_affine_inv
+      const float mu = fminf(fmaxf(hbuf[tid * out], -5.f), 5.f);
+      const float sg = expf(fminf(fmaxf(hbuf[tid * out + 1], -5.f), 2.f));
+      const float xv = (zv - mu) / sg;
+      x[(row0 + tid) * d + v] = xv;
+      act[(size_t)tid * A + t] = xv;
+    }
+    __syncthreads();
+  }
+}
+
+int tile_rows(const gnf_made_net* net, int64_t B) {
+  if (net->max_new >= 8 || net->out >= 8) return 16;                  // the MFMA tile
+  if ((B + 3) / 4 <= 1024) return 4;                                  // few rows: short steps on many CUs
+  if ((B + 7) / 8 <= 1024) return 8;
+  return 16;
+}
+
+int64_t lds_bytes(const MadeLayout& lay, int TB, bool with_act) {
+  return 4 * ((int64_t)kRedFloats + round_up(TB * lay.out, 4) + (with_act ? (int64_t)TB * lay.A : 0));
+}
+
+template <int TB>
+int launch(const StepArgs& s, bool lds, size_t smem, int64_t grid, hipStream_t st, const float* pack, const float* z,
+           float* x, float* h_out, int t0, int t1, int mode, float* ws, int64_t B) {
+  hipError_t e = lds ? gnf_launch_lds(made_prefix_k<TB, true>, dim3((unsigned)grid), dim3(kThreads), smem, st, s, pack, z, x,
+                                      h_out, t0, t1, mode, ws, B)
+                     : gnf_launch_lds(made_prefix_k<TB, false>, dim3((unsigned)grid), dim3(kThreads), smem, st, s, pack, z, x,
+                                      h_out, t0, t1, mode, ws, B);
+  return e == hipSuccess ? 0 : (int)e;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t gnf_made_prefix_pack_floats(const gnf_made_net* net) {
+  MadeLayout lay;
+  const int rc = make_layout(net, &lay);
+  return rc ? rc : lay.pack_floats;
+}
+
+int gnf_made_prefix_pack(const gnf_made_net* net, float* pack, gnf_stream_t stream) {
+  PackArgs a;
+  const int rc = make_layout(net, &a.lay);
+  if (rc) return rc;
+  if (!pack || !net->var_of_step) return GNF_EINVAL;
+  for (int l = 0; l <= net->nh; ++l) {
+    if (!net->W[l] || !net->b[l] || (l < net->nh && !net->order[l])) return GNF_EINVAL;
+    a.W[l] = net->W[l];
+    a.b[l] = net->b[l];
+    if (l < net->nh) a.order[l] = net->order[l];
+  }
+  a.var_of_step = net->var_of_step;
+  const int64_t blocks = (a.lay.pack_floats + 255) / 256;
+  hipLaunchKernelGGL(made_prefix_pack_k, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream,
+                     a, pack);
+  GNF_LAUNCH_CHECK();
+  return 0;
+}
+
+int64_t gnf_made_prefix_ws_bytes(const gnf_made_net* net, int64_t B) {
+  MadeLayout lay;
+  const int rc = make_layout(net, &lay);
+  if (rc) return rc;
+  if (B < 0) return GNF_EINVAL;
+  return 4 * B * lay.A;
+}
+
+int gnf_made_prefix(const gnf_made_net* net, const float* pack, const float* z, float* x, float* h_out, int t0, int t1,
+                    int normalizer_mode, int64_t B, void* ws, int64_t ws_bytes, gnf_stream_t stream) {
+  StepArgs s;
+  const int rc = make_layout(net, &s.lay);
+  if (rc) return rc;
+  if (B < 0 || t0 < 0 || t1 < t0 || t1 > net->d) return GNF_EINVAL;
+  if (normalizer_mode != GNF_MADE_NORM_NONE && normalizer_mode != GNF_MADE_NORM_AFFINE) return GNF_EINVAL;
+  if (normalizer_mode == GNF_MADE_NORM_NONE && t1 > t0 + 1) return GNF_EINVAL;
+  if (normalizer_mode == GNF_MADE_NORM_AFFINE && net->out < 2) return GNF_ESHAPE;
+  if (B == 0 || t1 == t0) return 0;
+  if (!pack || !x || !net->var_of_step) return GNF_EINVAL;
+  if (normalizer_mode == GNF_MADE_NORM_NONE ? !h_out : !z) return GNF_EINVAL;
+  for (int l = 0; l < net->nh; ++l) {
+    if (!net->off[l]) return GNF_EINVAL;
+    s.off[l] = net->off[l];
+  }
+  s.var_of_step = net->var_of_step;
+  const int TB = tile_rows(net, B);
+  const int64_t grid = (B + TB - 1) / TB;
+  if (grid > 0x7fffffff) return GNF_ESHAPE;
+  // the whole inversion in one launch keeps the tile's activations in LDS; step launches hand them on through ws
+  const bool lds = t0 == 0 && t1 == net->d && lds_bytes(s.lay, TB, true) <= kLdsBytes;
+  if (lds_bytes(s.lay, TB, false) > kLdsBytes) return GNF_ESHAPE;
+  if (!lds && (!ws || ws_bytes < 4 * B * s.lay.A)) return GNF_EWS;
+  const size_t smem = (size_t)lds_bytes(s.lay, TB, lds);
+  hipStream_t st = (hipStream_t)stream;
+  switch (TB) {
+    case 4: return launch<4>(s, lds, smem, grid, st, pack, z, x, h_out, t0, t1, normalizer_mode, (float*)ws, B);
+    case 8: return launch<8>(s, lds, smem, grid, st, pack, z, x, h_out, t0, t1, normalizer_mode, (float*)ws, B);
+    default: return launch<16>(s, lds, smem, grid, st, pack, z, x, h_out, t0, t1, normalizer_mode, (float*)ws, B);
+  }
+}
+
+}  // extern "C"

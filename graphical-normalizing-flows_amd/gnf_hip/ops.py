@@ -159,6 +159,90 @@ def affine_inverse(z, h):
     return x
 
 
+# ----------------------------------------------------------------------------- MADE prefix evaluation
+MADE_NORM_NONE, MADE_NORM_AFFINE = abi.MADE_NORM_NONE, abi.MADE_NORM_AFFINE
+
+
+def _made_net(params, plan):
+    """params: [W0, b0, ..., W_out, b_out] (nn.Linear layout) of a MADE; plan: MADE.prefix_plan() -> gnf_made_net.  The
+    returned struct holds raw pointers: the caller keeps params and plan alive while it is in use."""
+    nh = len(plan["widths"])
+    if len(params) != 2 * (nh + 1) or nh > abi.MADE_MAX_HIDDEN:
+        raise abi.GnfError("MADE prefix kernel: 0..%d hidden layers, one (weight, bias) pair per layer"
+                           % abi.MADE_MAX_HIDDEN)
+    net = abi.MadeNet()
+    net.nh, net.d, net.out, net.max_new = nh, plan["d"], plan["out"], plan["max_new"]
+    fan_in = plan["d"]
+    for l in range(nh + 1):
+        W, b = params[2 * l], params[2 * l + 1]
+        rows = plan["widths"][l] if l < nh else plan["d"] * plan["out"]
+        if tuple(W.shape) != (rows, fan_in) or tuple(b.shape) != (rows,) or not (W.is_contiguous() and b.is_contiguous()):
+            raise abi.GnfError("MADE prefix kernel: layer %d is not a contiguous [%d, %d] Linear" % (l, rows, fan_in))
+        net.W[l], net.b[l] = ptr(W).value, ptr(b).value
+        if l < nh:
+            net.width[l] = rows
+            net.order[l] = abi.rawptr(plan["order"][l]).value
+            net.off[l] = abi.rawptr(plan["off"][l]).value
+            fan_in = rows
+    net.var_of_step = abi.rawptr(plan["var_of_step"]).value
+    return net
+
+
+@torch.no_grad()
+def made_prefix_pack(params, plan):
+    """the prefix kernel's weight image (weights and biases in degree order): parameter-only, one launch; a caller that
+    steps through an inversion builds it once (AutoregressiveConditioner.hold_prefix_pack)"""
+    params = [p.detach() for p in params]
+    net = _made_net(params, plan)
+    nfl = abi.load().gnf_made_prefix_pack_floats(ctypes.byref(net))
+    if nfl < 0:
+        abi.check(int(nfl), "gnf_made_prefix_pack_floats")
+    pack = _empty((int(nfl),), params[0])
+    call("gnf_made_prefix_pack", ctypes.byref(net), ptr(pack), stream())
+    return pack
+
+
+@torch.no_grad()
+def made_prefix_workspace(params, plan, batch):
+    """the activation workspace that carries an inversion of `batch` rows from one made_prefix_steps call to the next"""
+    params = [p.detach() for p in params]
+    net = _made_net(params, plan)
+    nbytes = abi.load().gnf_made_prefix_ws_bytes(ctypes.byref(net), int(batch))
+    if nbytes < 0:
+        abi.check(int(nbytes), "gnf_made_prefix_ws_bytes")
+    return _ws(nbytes, params[0])
+
+
+@torch.no_grad()
+def made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=None, ws=None):
+    """Steps t0 <= t < t1 of the column-by-column inversion of a MADE step (gnf_made_prefix): z, x [B, d] fp32 contiguous.
+    MADE_NORM_AFFINE writes column var_of_step[t] of x per step ((0, d): the whole inversion, one launch);
+    MADE_NORM_NONE (t1 == t0 + 1) writes the conditioner outputs of that variable to h_out [B, out] and leaves the column
+    to the caller.  ws (made_prefix_workspace): the same buffer for every call of one inversion; allocated here when a call
+    that needs one comes without."""
+    params = [p.detach() for p in params]
+    net = _made_net(params, plan)
+    B, d = x.shape
+    if d != plan["d"] or not x.is_contiguous() or (z is not None and (tuple(z.shape) != (B, d) or not z.is_contiguous())):
+        raise abi.GnfError("made_prefix_steps: z and x must be contiguous [B, %d]" % plan["d"])
+    if h_out is not None and (tuple(h_out.shape) != (B, plan["out"]) or not h_out.is_contiguous()):
+        raise abi.GnfError("made_prefix_steps: h_out must be contiguous [B, %d]" % plan["out"])
+    if ws is None and not (t0 == 0 and t1 == d):
+        ws = made_prefix_workspace(params, plan, B)
+    args = lambda w: (ctypes.byref(net), ptr(pack), ptr(z), ptr(x), ptr(h_out), int(t0), int(t1), int(mode), B,
+                      None if w is None else ctypes.c_void_p(w.data_ptr()), 0 if w is None else w.numel() * 4, stream())
+    if ws is None:
+        # a whole inversion whose tile of activations fits in LDS needs no workspace; the library says when it does not
+        rc = getattr(abi.load(), "gnf_made_prefix")(*args(None))
+        if rc == 0:
+            return x
+        if rc != -3:
+            abi.check(rc, "gnf_made_prefix")
+        ws = made_prefix_workspace(params, plan, B)
+    call("gnf_made_prefix", *args(ws))
+    return x
+
+
 # ----------------------------------------------------------------------------- row reductions
 class LogSumRowsFn(torch.autograd.Function):
     """torch.log(jac).sum(1)   (models/NormalizingFlow.py:70)."""

@@ -60,6 +60,34 @@ def made_degrees(nin, hidden_sizes, random=False, natural_ordering=False, rng=No
     return m
 
 
+def made_prefix_plan(m, nin, nout):
+    """Tables for evaluating a MADE with degrees `m` (MADE.m: {-1: inputs, l: hidden layer l}) prefix by prefix, in the order
+    in which an inversion learns the variables: step t inverts the variable of degree t, and by the degree rule a hidden
+    unit of degree g is final once the variables of degree <= g are known.  Pure numpy:
+        order[l]     the units of hidden layer l in a stable sort by degree
+        off[l][t]    (t = 0..nin) number of units of degree < t: those units are order[l][:off[l][t]]
+        var_of_step  var_of_step[t] = the variable of degree t
+        out          outputs per variable (output neuron of component c of variable v: c * nin + v)
+        max_new      the largest number of units of one degree < nin - 1 in a layer (what one step computes)
+    Step t >= 1 computes the units of degree t - 1 of every layer, order[l][off[l][t-1]:off[l][t]]: layer 0 from the inputs
+    of degree <= t - 1 (var_of_step[:t]), layer l from order[l-1][:off[l-1][t]]; the outputs of var_of_step[t] read the last
+    hidden layer's units of degree < t, order[-1][:off[-1][t]] (the inputs of degree < t when there is no hidden layer)."""
+    L = len(m) - 1
+    deg_in = np.asarray(m[-1]).astype(np.int64)
+    if not np.array_equal(np.sort(deg_in), np.arange(nin)):
+        raise ValueError("the input degrees must be a permutation of 0..nin-1")
+    order, off, widths, max_new = [], [], [], 0
+    for l in range(L):
+        deg = np.asarray(m[l]).astype(np.int64)
+        order.append(np.argsort(deg, kind="stable").astype(np.int32))
+        off.append(np.searchsorted(np.sort(deg), np.arange(nin + 1), side="left").astype(np.int32))
+        widths.append(int(deg.size))
+        if nin > 1:
+            max_new = max(max_new, int(np.diff(off[-1][:nin]).max()))
+    return {"d": int(nin), "out": int(nout // nin), "widths": widths, "order": order, "off": off,
+            "var_of_step": np.argsort(deg_in, kind="stable").astype(np.int32), "max_new": max_new}
+
+
 class MADE(nn.Module):
     """Masked autoencoder, reference AutoregressiveConditioner.py:28-109: natural ordering (`random=False`, what the
     conditioner builds) or sampled orderings (`random=True`), cycling through `num_masks` seeds on update_masks().  Every
@@ -110,6 +138,37 @@ class MADE(nn.Module):
     def masked_layers(self):
         return [l for l in self.net if isinstance(l, MaskedLinear)]
 
+    _prefix_cache = None                 # (key, plan): plain attributes, nothing enters the state_dict
+
+    def prefix_plan(self):
+        """made_prefix_plan(self.m) with its tables on the weights' device, or None when the masks in force are not the
+        degree rule of self.m (a loaded checkpoint, a hand-set mask) or the net is conditioned on a context.  Cached;
+        rebuilt when update_masks() installs another ordering or a mask buffer changes."""
+        if getattr(self, "cond_in", 0) != 0:
+            return None
+        layers = self.masked_layers()
+        specs = [l.degree_spec() for l in layers]
+        if any(s is None for s in specs):
+            return None
+        key = (tuple(l._deg_checked for l in layers), layers[0].weight.device)
+        cache = self._prefix_cache
+        if cache is None or cache[0] is not self.m or cache[1] != key:
+            L, dev = len(self.hidden_sizes), layers[0].weight.device
+            reps = self.nout // self.nin
+            want = [(self.m[l], self.m[l - 1], False) for l in range(L)] + [(np.tile(self.m[-1], reps), self.m[L - 1], True)]
+            same = all(strict == ws and np.array_equal(do.cpu().numpy(), np.asarray(wo, dtype=np.float32))
+                       and np.array_equal(di.cpu().numpy(), np.asarray(wi, dtype=np.float32))
+                       for (do, di, strict), (wo, wi, ws) in zip(specs, want))
+            plan = None
+            if same:
+                plan = made_prefix_plan(self.m, self.nin, self.nout)
+                plan["var_host"] = [int(v) for v in plan["var_of_step"]]
+                for k in ("order", "off"):
+                    plan[k] = [torch.from_numpy(a).to(dev) for a in plan[k]]
+                plan["var_of_step"] = torch.from_numpy(plan["var_of_step"]).to(dev)
+            cache = self._prefix_cache = (self.m, key, plan)
+        return cache[2]
+
     def forward(self, x):
         ls = self.masked_layers()
         y = ops.mlp(x, [(l.weight, l.bias) for l in ls], [l.mask for l in ls], degs=[l.degree_spec() for l in ls])
@@ -146,3 +205,38 @@ class AutoregressiveConditioner(Conditioner):
 
     def depth(self):
         return self.in_size - 1
+
+    # -- column-by-column inversion (NormalizingFlowStep._invert_by_columns) ---------------------------------------------
+    def prefix_plan(self):
+        get = getattr(self.masked_autoregressive_net, "prefix_plan", None)
+        return get() if get is not None else None
+
+    _held_prefix = None
+
+    def _prefix_params(self):
+        return [p for l in self.masked_autoregressive_net.masked_layers() for p in (l.weight, l.bias)]
+
+    def hold_prefix_pack(self):
+        """context manager: the degree-ordered weight image of the prefix kernel, built once for the step calls inside"""
+        import contextlib
+
+        @contextlib.contextmanager
+        def hold():
+            prev = self._held_prefix
+            plan = self.prefix_plan()
+            if prev is None and plan is not None:
+                self._held_prefix = ops.made_prefix_pack(self._prefix_params(), plan)
+            try:
+                yield
+            finally:
+                self._held_prefix = prev
+        return hold()
+
+    def prefix_workspace(self, batch):
+        return ops.made_prefix_workspace(self._prefix_params(), self.prefix_plan(), batch)
+
+    def prefix_steps(self, z, x, t0, t1, mode, h_out=None, ws=None):
+        """steps t0 <= t < t1 of the plan on the HIP prefix kernel (gnf_hip.ops.made_prefix_steps)"""
+        plan, params = self.prefix_plan(), self._prefix_params()
+        pack = self._held_prefix if self._held_prefix is not None else ops.made_prefix_pack(params, plan)
+        return ops.made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=h_out, ws=ws)

@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from gnf_hip import ops
 from .Conditionners import Conditioner, DAGConditioner
-from .Normalizers import Normalizer
+from .Normalizers import Normalizer, AffineNormalizer
 
 
 # captured inversion graphs per NormalizingFlowStep, kept OUTSIDE the modules: a hipGraph is neither copyable nor
@@ -77,6 +77,7 @@ class NormalizingFlowStep(NormalizingFlow):
         self.normalizer = normalizer
         self.level_schedule = True       # invert(): topological level schedule for DAG conditioners
         self.graph_invert = True         # ... replayed as a hipGraph from the second pass of a shape on (frozen A, GPU)
+        self.column_schedule = True      # invert(): one column per step for MADE conditioners, every hidden unit once
 
     def getConditioners(self):
         return [self.conditioner]
@@ -240,6 +241,42 @@ class NormalizingFlowStep(NormalizingFlow):
         graph.replay()
         return xbuf.clone()
 
+    def _invert_by_columns(self, z, context):
+        """MADE conditioner: the variables are inverted in degree order, one per step, and a step evaluates only the hidden
+        units that became final with the previous column (AutoregressiveConditioner.prefix_plan) -- about half of ONE masked
+        forward and ONE normalizer inverse in total, where the passes below spend depth() + 1 = d of each.  The same function
+        in another fp32 summation order.  Returns None when not applicable."""
+        cond = self.conditioner
+        get_plan = getattr(cond, "prefix_plan", None)
+        if not (self.column_schedule and context is None and get_plan is not None and z.is_cuda and z.dim() == 2
+                and z.dtype == torch.float32):
+            return None
+        if z.shape[0] == 0:
+            # no rows, no launch: the empty result (the passes would stop at the MADE's `.view(0, -1, d)` as the reference's do)
+            return torch.zeros_like(z)
+        plan = get_plan()
+        if plan is None or plan["d"] != z.shape[1]:
+            return None
+        z = z.contiguous()
+        x = torch.zeros_like(z)
+        B, d, out = z.shape[0], plan["d"], plan["out"]
+        with cond.hold_prefix_pack():
+            if type(self.normalizer) is AffineNormalizer:
+                cond.prefix_steps(z, x, 0, d, ops.MADE_NORM_AFFINE)          # the whole inversion, one launch
+                return x
+            h = torch.empty(B, out, dtype=torch.float32, device=z.device)
+            ws = cond.prefix_workspace(B)
+            zt = z.t().contiguous()                                          # a column of z as a one-row [1, B] problem
+            cols = torch.arange(d, dtype=torch.int32, device=z.device)
+            into = getattr(self.normalizer, "inverse_transform_into", None)
+            for t in range(d):
+                v = plan["var_host"][t]
+                cond.prefix_steps(z, x, t, t + 1, ops.MADE_NORM_NONE, h_out=h, ws=ws)
+                # the normalizer's own inverse of that one column; the fused Monotonic kernel writes x[:, v] itself
+                if into is None or not into(zt[v:v + 1], h.view(1, B, out), x, cols[v:v + 1]):
+                    x[:, v:v + 1] = self.normalizer.inverse_transform(z[:, v:v + 1], h.view(B, 1, out), context)
+        return x
+
     def invert(self, z, context=None):
         """Reference :98-107: fixed point of x <- normalizer^-1(z, conditioner(x)) from x = 0, depth()+1 passes, early
         exit once a pass changes nothing (its progress print is dropped)."""
@@ -248,6 +285,8 @@ class NormalizingFlowStep(NormalizingFlow):
             for _, _, make in self._holders():
                 stack.enter_context(make())
             x = self._invert_by_levels(z, context)
+            if x is None:
+                x = self._invert_by_columns(z, context)
             if x is not None:
                 return x
             x = torch.zeros_like(z)

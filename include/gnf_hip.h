@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GNF_ABI_VERSION 9
+#define GNF_ABI_VERSION 10
 #define GNF_EINVAL (-1)   /* bad argument (null pointer, negative size, ...)          */
 #define GNF_ESHAPE (-2)   /* shape not supported by any compiled kernel instantiation */
 #define GNF_EWS    (-3)   /* workspace too small                                      */
@@ -319,6 +319,47 @@ int gnf_monotonic_bwd_f32(const float* pack, const gnf_mono_net* net,
                           float* const* gW, float* const* gb,
                           void* ws, int64_t ws_bytes, int64_t B, int64_t d, gnf_stream_t stream);
 const char* gnf_monotonic_bwd_kernel(void);
+
+/* ---- MADE prefix evaluation: inverting an autoregressive step column by column (round 7) -------------------------------
+ * NormalizingFlowStep.invert (reference NormalizingFlow.py:98-107) runs d fixed-point passes, each a full MADE forward
+ * (AutoregressiveConditioner.py:28-109) and a full normalizer inverse, for ONE new column per pass.  By the MADE's degree
+ * rule a hidden unit of degree m is final once the variables of degree 0..m are known, so step t needs only the hidden
+ * units of degree t-1 (from the final units below them) and the `out` outputs of the variable of degree t.
+ *   net: nh hidden layers of width[l]; W[l] / b[l], l = 0..nh, in nn.Linear layout (W[nh]: [out*d, .], output neuron of
+ *     component c of variable v at c*d + v); the plan tables (device, int32): order[l] [width[l]] = the units of layer l in
+ *     a stable sort by degree, off[l] [d+1] with off[l][t] = number of units of degree < t, var_of_step [d] = the variable
+ *     of degree t; max_new (host) = the largest number of units of one degree in a layer.  The masks are NOT read: the
+ *     caller guarantees that they are the degree rule (<= between layers, < into the output layer).
+ *   pack: >= gnf_made_prefix_pack_floats(net) floats, written by gnf_made_prefix_pack (weights and biases in degree order;
+ *     parameter-only, valid until a parameter or the ordering changes).
+ *   gnf_made_prefix runs steps t0 <= t < t1 for B rows:
+ *     GNF_MADE_NORM_NONE   (t1 == t0 + 1): h_out[b, c] (B x out, contiguous) = the outputs of variable var_of_step[t0]; the
+ *       caller inverts that column, writes x[:, var_of_step[t0]] and calls again with t0 + 1;
+ *     GNF_MADE_NORM_AFFINE (out >= 2): x[b, v] = (z[b, v] - clamp(h0, -5, 5)) / exp(clamp(h1, -5, 2)) per step, as
+ *       gnf_affine_inv computes it; (t0, t1) = (0, d) is the whole inversion of an Affine + MADE step in one launch.
+ *   z, x: [B, d] contiguous; columns of x of degree < t0 are read, the others written (AFFINE) or left alone (NONE).
+ *   ws: >= gnf_made_prefix_ws_bytes(net, B) bytes carrying the activations from one call to the next (the SAME buffer for
+ *     every call of one inversion, steps in ascending order from 0); may be NULL for (0, d) calls whose tile fits in LDS,
+ *     GNF_EWS tells otherwise.  Values are those of the passes up to fp32 summation order. */
+#define GNF_MADE_MAX_HIDDEN 8
+#define GNF_MADE_NORM_NONE 0
+#define GNF_MADE_NORM_AFFINE 1
+typedef struct {
+  int nh;                                   /* number of hidden layers (0..GNF_MADE_MAX_HIDDEN) */
+  int d, out;                               /* variables; conditioner outputs per variable */
+  int max_new;
+  int width[GNF_MADE_MAX_HIDDEN];
+  const float* W[GNF_MADE_MAX_HIDDEN + 1];
+  const float* b[GNF_MADE_MAX_HIDDEN + 1];
+  const int32_t* order[GNF_MADE_MAX_HIDDEN];
+  const int32_t* off[GNF_MADE_MAX_HIDDEN];
+  const int32_t* var_of_step;
+} gnf_made_net;
+int64_t gnf_made_prefix_pack_floats(const gnf_made_net* net);
+int gnf_made_prefix_pack(const gnf_made_net* net, float* pack, gnf_stream_t stream);
+int64_t gnf_made_prefix_ws_bytes(const gnf_made_net* net, int64_t B);
+int gnf_made_prefix(const gnf_made_net* net, const float* pack, const float* z, float* x, float* h_out, int t0, int t1,
+                    int normalizer_mode, int64_t B, void* ws, int64_t ws_bytes, gnf_stream_t stream);
 
 /* ---- MNISTCNN convolutional front: models/MLP.py:36-41 as the DAG embedding net --------
  * (ImageExperiments / NormalizingFlowFactories.py:83-86: size_img = [1,28,28]).
