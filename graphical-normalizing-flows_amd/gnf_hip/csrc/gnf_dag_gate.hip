@@ -357,7 +357,8 @@ __global__ void dag_gate_bwd_dA_k(const float* __restrict__ tab, const float* __
                                   float* __restrict__ gA, int64_t dd) {
   const int64_t i4 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i4 >= dd) return;
-  if (i4 + 3 < dd && (dd & 3) == 0) {
+  const bool al16 = ((reinterpret_cast<uintptr_t>(part) | reinterpret_cast<uintptr_t>(tab) | reinterpret_cast<uintptr_t>(gA)) & 15) == 0;
+  if (i4 + 3 < dd && (dd & 3) == 0 && al16) {     // (gA may be a slot of a flat gradient buffer: any dword address)
     float4 s = *reinterpret_cast<const float4*>(part + i4);
     for (int c = 1; c < nc; ++c) {
       const float4 v = *reinterpret_cast<const float4*>(part + (int64_t)c * dd + i4);

@@ -797,10 +797,11 @@ int gnf_gemm_launch(GemmArgs g, int splits, hipStream_t s) {
 }
 
 int gnf_gemm_grouped_launch(GemmArgs g, int ngroups, hipStream_t s) {
-  auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
   const bool akf = g.sak == 1 && g.sam % 4 == 0, amf = g.sam == 1 && g.sak % 4 == 0;
   const bool bkf = g.sbk == 1 && g.sbn % 4 == 0, bnf = g.sbn == 1 && g.sbk % 4 == 0;
-  if (!g.grp || ngroups < 1 || ngroups > 65535 || !(akf || amf) || !(bkf || bnf) || !al16(g.A) || !al16(g.B) ||
+  // (no condition on the base pointers: gemm_vec_k's global side assumes dword alignment only -- the cotangent the sparse
+  // front's backward passes as A / B is a caller's array)
+  if (!g.grp || ngroups < 1 || ngroups > 65535 || !(akf || amf) || !(bkf || bnf) ||
       g.b_grp_stride % 4 || g.Bmask || g.Cmask || g.gate)
     return GNF_ESHAPE;
   if (g.grp_k) {

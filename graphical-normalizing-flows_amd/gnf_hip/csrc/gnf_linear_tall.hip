@@ -468,13 +468,14 @@ int64_t gnf_linear_tall_ws_floats(int64_t M, int64_t N, int64_t K) { return (int
 namespace {
 template <int NT, int KC>
 void launch_tall_fwd(dim3 g, hipStream_t s, const float* x, const float* W, const float* b, int relu, float* y, int M, int N, int K) {
-  if (K == 16 * KC) hipLaunchKernelGGL((lin_fwd_tall_k<NT, KC, true>), g, dim3(256), 0, s, x, W, b, relu, y, M, N, K);
+  // the exact-K instantiation reads x rows as 16-byte aligned quads: only for an x that is; the descriptor one takes any dword
+  if (K == 16 * KC && ((uintptr_t)x & 15) == 0) hipLaunchKernelGGL((lin_fwd_tall_k<NT, KC, true>), g, dim3(256), 0, s, x, W, b, relu, y, M, N, K);
   else hipLaunchKernelGGL((lin_fwd_tall_k<NT, KC, false>), g, dim3(256), 0, s, x, W, b, relu, y, M, N, K);
 }
 template <int NT, int KC>
 void launch_tall_bwd(dim3 g, hipStream_t s, const float* gr, const float* W, const float* a, int gated, float* gx, float* part,
                      int M, int N, int K, int want_xsum) {
-  if (K == 16 * KC) hipLaunchKernelGGL((lin_bwd_tall_k<NT, KC, true>), g, dim3(512), 0, s, gr, W, a, gated, gx, part, M, N, K, want_xsum);
+  if (K == 16 * KC && ((uintptr_t)a & 15) == 0) hipLaunchKernelGGL((lin_bwd_tall_k<NT, KC, true>), g, dim3(512), 0, s, gr, W, a, gated, gx, part, M, N, K, want_xsum);
   else hipLaunchKernelGGL((lin_bwd_tall_k<NT, KC, false>), g, dim3(512), 0, s, gr, W, a, gated, gx, part, M, N, K, want_xsum);
 }
 // instantiation (out tiles NT in {2, 4}) x (k chunks KC in {1, 4, 8})

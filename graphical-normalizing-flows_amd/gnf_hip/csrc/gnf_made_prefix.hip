@@ -259,6 +259,7 @@ int gnf_made_prefix_pack(const gnf_made_net* net, float* pack, gnf_stream_t stre
   const int rc = make_layout(net, &a.lay);
   if (rc) return rc;
   if (!pack || !net->var_of_step) return GNF_EINVAL;
+  if ((uintptr_t)pack & 15) return GNF_EINVAL;          // the step kernel reads the image's rows as 16-byte quads
   for (int l = 0; l <= net->nh; ++l) {
     if (!net->W[l] || !net->b[l] || (l < net->nh && !net->order[l])) return GNF_EINVAL;
     a.W[l] = net->W[l];
@@ -292,6 +293,7 @@ int gnf_made_prefix(const gnf_made_net* net, const float* pack, const float* z, 
   if (normalizer_mode == GNF_MADE_NORM_AFFINE && net->out < 2) return GNF_ESHAPE;
   if (B == 0 || t1 == t0) return 0;
   if (!pack || !x || !net->var_of_step) return GNF_EINVAL;
+  if ((uintptr_t)pack & 15) return GNF_EINVAL;          // rows of the weight image are read as 16-byte quads (ld4)
   if (normalizer_mode == GNF_MADE_NORM_NONE ? !h_out : !z) return GNF_EINVAL;
   for (int l = 0; l < net->nh; ++l) {
     if (!net->off[l]) return GNF_EINVAL;

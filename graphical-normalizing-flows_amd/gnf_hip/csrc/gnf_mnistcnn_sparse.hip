@@ -735,7 +735,7 @@ __global__ __launch_bounds__(64 * FC_WAVES) void sparse_fc12_k(FcArgs a) {
   if (wave < 2) {
     const float* w2p = a.W2 + (int64_t)(n2 < a.out_d ? n2 : a.out_d - 1) * FC_F + 4 * q;
 #pragma unroll
-    for (int T = 0; T < FC_F / 16; ++T) wv[T] = *reinterpret_cast<const f32x4*>(w2p + 16 * T);
+    for (int T = 0; T < FC_F / 16; ++T) wv[T] = *reinterpret_cast<const f32x4u*>(w2p + 16 * T);   // (the caller's fc2 weight: any dword)
   }
   const float* bp = a.Wg + ((int64_t)g * KD + kq * (FC_KSTEPS * 4) + q) * FC_F + 64 * ch + 4 * j;
   f32x4 bv[FC_KSTEPS];
@@ -941,6 +941,7 @@ int gnf_mnistcnn_sparse_fwd_prepared_fc2(const float* x, int64_t B, const float*
   if (!x || !P || !pix || !groups || !h2) return GNF_EINVAL;
   if (!ws || ws_bytes < items * KD * (int64_t)sizeof(float) || max_group_rows <= 0 || max_group_rows > items)
     return GNF_EINVAL;
+  if (((uintptr_t)ws | (uintptr_t)prep) & 15) return GNF_EINVAL;   // workspace and tables are read in 16-byte pieces
   hipStream_t s = (hipStream_t)stream;
   const float* Wg = (const float*)prep;
   const float* bg = Wg + (int64_t)NORIG * KD * F;

@@ -2612,7 +2612,7 @@ int64_t gnf_monotonic_pack_floats(const gnf_mono_net* net) {
 int gnf_monotonic_pack(const gnf_mono_net* net, float* pack, gnf_stream_t stream) {
   const int HT = pick_ht(net);
   if (HT < 0) return GNF_ESHAPE;
-  if (!pack) return GNF_EINVAL;
+  if (!pack || ((uintptr_t)pack & 15)) return GNF_EINVAL;   // the consumers read it in 16-byte pieces, some straight to LDS
   PackArgs a;
   a.net = *net;
   a.L = net_layout(net, HT);
@@ -2644,6 +2644,7 @@ static int mono_fwd_any(const float* pack, const gnf_mono_net* net, const float*
   const int HT = pick_ht(net);
   if (HT < 0) return GNF_ESHAPE;
   if (!pack || !cc_w || !cc_t || S < 1 || B < 0 || d <= 0) return GNF_EINVAL;
+  if ((uintptr_t)pack & 15) return GNF_EINVAL;          // 16-byte pieces, some global -> LDS directly (glds16)
   if (B == 0) return 0;                    // batch-sized arrays may be NULL for an empty batch
   if (!x || !h || !z || !jac) return GNF_EINVAL;
   MonoArgs a{};
@@ -2662,6 +2663,7 @@ int gnf_monotonic_inv_scatter(const float* pack, const gnf_mono_net* net, const 
   const int HT = pick_ht(net);
   if (HT < 0) return GNF_ESHAPE;
   if (!pack || !cc_w || !cc_t || S < 1 || B < 0 || d <= 0) return GNF_EINVAL;
+  if ((uintptr_t)pack & 15) return GNF_EINVAL;
   if (B == 0) return 0;
   if (!z || !h || !x) return GNF_EINVAL;
   MonoArgs a{};
@@ -2716,6 +2718,7 @@ int gnf_monotonic_bwd(const float* pack, const gnf_mono_net* net, const float* x
   const int HT = pick_ht(net);
   if (HT < 0) return GNF_ESHAPE;
   if (!pack || !cc_w || !cc_t || !gW || !gb || S < 1 || B < 0 || d <= 0) return GNF_EINVAL;
+  if (((uintptr_t)pack | (uintptr_t)ws) & 15) return GNF_EINVAL;   // the weight image and the staging arrays: 16-byte pieces
   const int NH = net->nl - 1;
   if (NH > 4) return GNF_ESHAPE;
   if (B == 0) {                              // empty batch: zero parameter gradients, nothing else to write

@@ -65,6 +65,7 @@ extern "C" int64_t gnf_probe_mfma_f32(float* out, int iters, int blocks, gnf_str
 
 extern "C" int gnf_probe_copy(float* dst, const float* src, int64_t n, gnf_stream_t stream) {
   if (!dst || !src || n < 0 || (n & 3)) return GNF_EINVAL;
+  if (((uintptr_t)dst | (uintptr_t)src) & 15) return GNF_EINVAL;   // a float4 copy by definition: 16-byte aligned arrays only
   if (n == 0) return 0;
   hipLaunchKernelGGL(probe_copy_k, dim3(256 * 16), dim3(256), 0, (hipStream_t)stream, (f32x4*)dst, (const f32x4*)src,
                      n / 4);

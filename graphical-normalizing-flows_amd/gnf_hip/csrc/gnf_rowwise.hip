@@ -61,7 +61,7 @@ __device__ __forceinline__ void affine_fwd_body(const float* __restrict__ x, flo
                              int64_t d) {
   const int64_t row0 = ((int64_t)blockIdx.x * (kBlock / G) + threadIdx.x / G) * R;
   const int g = threadIdx.x % G;
-  const bool pair = (h_sc == 1 && h_sd == 2 && (h_sb & 1) == 0);
+  const bool pair = (h_sc == 1 && h_sd == 2 && (h_sb & 1) == 0 && (reinterpret_cast<uintptr_t>(h) & 7) == 0);
   float ld[R], ln[R];
 #pragma unroll
   for (int k = 0; k < R; ++k) { ld[k] = 0.f; ln[k] = 0.f; }
@@ -128,8 +128,8 @@ __global__ void affine_bwd_k(const float* __restrict__ x, const float* __restric
                              int64_t B, int64_t d) {
   const int64_t row0 = ((int64_t)blockIdx.x * (kBlock / G) + threadIdx.x / G) * R;
   const int g = threadIdx.x % G;
-  const bool pair = (h_sc == 1 && h_sd == 2 && (h_sb & 1) == 0);
-  const bool gpair = (g_sc == 1 && g_sd == 2 && (g_sb & 1) == 0);
+  const bool pair = (h_sc == 1 && h_sd == 2 && (h_sb & 1) == 0 && (reinterpret_cast<uintptr_t>(h) & 7) == 0);
+  const bool gpair = (g_sc == 1 && g_sd == 2 && (g_sb & 1) == 0 && (reinterpret_cast<uintptr_t>(gh) & 7) == 0);
 #pragma unroll 4
   for (int64_t i = g; i < d; i += G) {
     float h0[R], h1[R], xv[R], gzv[R], gjv[R];

@@ -20,7 +20,10 @@ class FlatState:
 
     def __init__(self, module):
         self.params = [p for p in module.parameters() if p.requires_grad]
-        pad4 = lambda k: (k + 3) // 4 * 4          # every parameter starts 16-B aligned (vector loads)
+        # every parameter starts 16-B aligned.  A performance choice, not a requirement: the kernels take an fp32 array at any
+        # 4-byte-aligned address (include/gnf_hip.h) and 16-byte alignment selects their vector forms (Adam's float4 loop, the
+        # exact-K tall-layer kernels, the dedicated GEMM families)
+        pad4 = lambda k: (k + 3) // 4 * 4
         n = sum(pad4(p.numel()) for p in self.params)
         dev = self.params[0].device
         self.flat = torch.zeros(n, device=dev)

@@ -14,6 +14,18 @@
  *   - the caller owns and sizes every buffer, including workspaces (gnf_*_ws_bytes);
  *   - no global mutable state: safe for one process per GPU and for several streams;
  *   - strides are in ELEMENTS, not bytes;
+ *   - ALIGNMENT: every fp32 array -- inputs, outputs, parameters, cotangents, gradient arrays -- may sit at any
+ *     4-byte-aligned address (a slice of a [n, 21] data set, a view into a flat parameter or gradient buffer); 16-byte
+ *     alignment only selects faster kernels (the float4 forms of the row-wise and Adam kernels, the exact-K tall-layer
+ *     kernels, the dedicated GEMM families) and never changes what is computed beyond the rounding of another summation
+ *     order.  The exceptions, all of them buffers the library itself fills and that are read in 16-byte pieces -- they must
+ *     be 16-byte aligned, and the entry points refuse another address with GNF_EINVAL before any launch:
+ *       the saved conv1 activations a1save / a1saved (gnf_mnistcnn_conv_fwd_save, *_a1),
+ *       the weight images `pack` of gnf_monotonic_pack and gnf_made_prefix_pack and of every entry point that reads them,
+ *       the byte workspaces `ws` of gnf_monotonic_bwd and `ws` / `prep` of gnf_mnistcnn_sparse_fwd_prepared_fc2.
+ *     and the measurement probe gnf_probe_copy, a float4 stream copy by definition, refuses a dst / src that is not.
+ *     (Every other `void*` workspace should be 16-byte aligned as well; any allocator's result is.)
+ *     tests/test_gpu_alignment.py runs every entry point at the offsets 4, 8 and 12;
  *   - an EMPTY batch (B, n_img, M or the row count = 0) is a valid call, as it is in the
  *     reference (torch ops on [0, d] tensors): arrays sized by the batch may then be NULL
  *     (torch hands out a null data_ptr for them), nothing is launched over them, and the

@@ -19,16 +19,30 @@ def dim(rng, big):
     return rng.randint(1, big)
 
 
-def operand(rows, cols, layout, pad, gen):
-    """[rows, cols] view with the given memory order ('r' row-major, 'c' column-major) and `pad` extra leading elements"""
+def displaced(t, off):
+    """a copy of the device tensor `t` whose storage starts `off` floats past an allocation (allocations are 16-byte aligned:
+    off = 1, 2, 3 gives a base pointer at dword-only alignment)"""
+    if not off:
+        return t
+    buf = torch.empty(t.numel() + off, device=t.device)
+    out = buf[off:].view(t.shape)
+    out.copy_(t)
+    return out
+
+
+def operand(rows, cols, layout, pad, gen, off=0):
+    """[rows, cols] view with the given memory order ('r' row-major, 'c' column-major), `pad` extra leading elements and the
+    base pointer `off` floats past a 16-byte boundary"""
     if layout == "r":
-        base = torch.randn(rows, cols + pad, generator=gen).to(DEV)
+        base = displaced(torch.randn(rows, cols + pad, generator=gen).to(DEV), off)
         return base[:, :cols]
-    base = torch.randn(cols, rows + pad, generator=gen).to(DEV)
+    base = displaced(torch.randn(cols, rows + pad, generator=gen).to(DEV), off)
     return base[:, :rows].t()
 
 
-def one(case, rng):
+def one(case, rng, rng_off=None):
+    """rng_off: a second random.Random that draws the base offsets (in floats) of the operands; None: every base aligned.  It is
+    a generator of its own so that the shapes, layouts and values of a walk are the same with and without offsets."""
     shape_kind = rng.random()
     forced = None
     if shape_kind < .12:     # gemm_tall_k's domain and its edges: both operands k-contiguous, 96 < N <= 128, K % 32 == 0, K >= 256
@@ -60,21 +74,25 @@ def one(case, rng):
         la, lb, lc = rng.choice([("r", "c", "r"), ("r", "r", "r"), ("c", "r", "r")])
         pa, pb, pc = rng.choice([0, 4]), rng.choice([0, 4]), 0
     gen = torch.Generator().manual_seed(case)
-    A = operand(M, K, la, pa, gen)
-    B = operand(K, N, lb, pb, gen)
-    C = operand(M, N, lc, pc, gen)
+    oa, ob, oc, obias, om, ocm, og = [rng_off.choice([0, 1, 2, 3]) for _ in range(7)] if rng_off is not None else [0] * 7
+    A = operand(M, K, la, pa, gen, oa)
+    B = operand(K, N, lb, pb, gen, ob)
+    C = operand(M, N, lc, pc, gen, oc)
     use_bias, use_relu = rng.random() < .4, rng.random() < .3
     use_bmask, use_cmask, use_gate = rng.random() < .15, rng.random() < .1, rng.random() < .1
     if forced is not None and rng.random() < .8:    # (the dedicated kernels take bias / ReLU at most)
         use_bmask = use_cmask = use_gate = False
         if forced[0] != "r" or forced[1] != "c":    # wide and k-major: no epilogue at all
             use_bias = use_relu = False
-    bias = torch.randn(N, generator=gen).to(DEV) if use_bias else None
+    bias = displaced(torch.randn(N, generator=gen).to(DEV), obias) if use_bias else None
     Bmask = (operand(K, N, lb, pb, gen) > -.5).float() if use_bmask else None   # (shares B's strides: same order, same pad)
     if use_bmask:
         Bmask = torch.empty_strided(B.shape, B.stride(), device=DEV).copy_(Bmask) if Bmask.stride() != B.stride() else Bmask
-    Cmask = (torch.rand(M, N, generator=gen) < .7).float().to(DEV) if use_cmask else None
-    gate = torch.randn(M, N, generator=gen).to(DEV) if use_gate else None
+        if om:                                                                  # the same view over a displaced base
+            flat = torch.empty(Bmask.untyped_storage().nbytes() // 4 + om, device=DEV)
+            Bmask = flat[om:].as_strided(Bmask.shape, Bmask.stride(), om).copy_(Bmask)
+    Cmask = displaced((torch.rand(M, N, generator=gen) < .7).float().to(DEV), ocm) if use_cmask else None
+    gate = displaced(torch.randn(M, N, generator=gen).to(DEV), og) if use_gate else None
     ops.gemm(A, A.stride(), B, B.stride(), C, C.stride(), M, N, K,
              Bmask=Bmask, bias=bias, Cmask=Cmask, cm_strides=Cmask.stride() if use_cmask else (0, 0),
              gate=gate, g_strides=gate.stride() if use_gate else (0, 0), relu=use_relu)
@@ -92,17 +110,20 @@ def one(case, rng):
     err = (C.double() - ref).abs()
     tol = 2e-6 * mag + 1e-30             # ~sqrt(K) ulps would do; K ulps of the term magnitudes is the safe bound for fp32 chains
     worst = float((err / tol).max())
-    desc = "M %6d N %5d K %6d  A%s%d B%s%d C%s%d %s%s%s%s%s %-22s" % (M, N, K, la, pa, lb, pb, lc, pc, "b" if use_bias else "-",
-                                                                 "r" if use_relu else "-", "m" if use_bmask else "-",
-                                                                 "c" if use_cmask else "-", "g" if use_gate else "-", kern)
+    offs = "" if rng_off is None else " +%d%d%d%d%d%d%d" % (oa, ob, oc, obias, om, ocm, og)
+    desc = "M %6d N %5d K %6d  A%s%d B%s%d C%s%d %s%s%s%s%s%s %-22s" % (M, N, K, la, pa, lb, pb, lc, pc, "b" if use_bias else "-",
+                                                                   "r" if use_relu else "-", "m" if use_bmask else "-",
+                                                                   "c" if use_cmask else "-", "g" if use_gate else "-", offs, kern)
     return desc, worst, worst > 1.
 
 
-def walk(n, seed):
+def walk(n, seed, offset_seed=None):
+    """offset_seed: draw a base offset of 0..3 floats for every operand from random.Random(offset_seed)"""
     rng = random.Random(seed)
+    rng_off = random.Random(offset_seed) if offset_seed is not None else None
     out = []
     for case in range(n):
-        desc, worst, bad = one(case, rng)
+        desc, worst, bad = one(case, rng, rng_off)
         out.append((case, desc, worst, bad))
     return out
 

@@ -32,6 +32,36 @@ def params(rng):
     return M, nl, dims, mask_kind, rng.random() < .7
 
 
+# Rows with a hidden pre-activation within the fp32 chain's error bound of zero are REDRAWN from the same generator until none
+# is left (rows are independent): there an fp32 chain and the fp64 one may gate differently, and ONE flipped gate moves that
+# row's gradient by several per cent (at 60 000 rows x 256 units a walk meets a handful of such rows per case).  The bound of a
+# layer = 16 fp32 ulps of its own terms' magnitude + the bound INHERITED from its inputs through |W|: behind a narrow
+# bottleneck (walk 703, case 113: 255 -> 1 -> 198) the single input carries the roundoff of a 255-term sum, which is far more
+# than 16 ulps of its own small value
+def tied_rows(x_, layers, masks):
+    """[M] bool: the rows of x_ with such a pre-activation in the chain `layers` ([(W, b)], CPU) under `masks` ([] or one per layer)"""
+    a = x_.double()
+    knife = torch.zeros(a.shape[0], dtype=torch.bool)
+    aerr = torch.zeros(a.shape[0], a.shape[1], dtype=torch.float64)  # bound on the fp32 chain's absolute error of the layer inputs
+    for l, (W, b) in enumerate(layers[:-1]):
+        Wm = (W * masks[l] if masks else W).double()
+        pre = torch.nn.functional.linear(a, Wm, b.double())
+        mag = a.abs() @ Wm.abs().t() + b.double().abs()
+        aerr = 16 * 2. ** -23 * mag + aerr @ Wm.abs().t()
+        knife |= ((pre.abs() < aerr) & (pre != 0)).any(1)
+        a = torch.relu(pre)
+    return knife
+
+
+def redraw_off_ties(x, layers, masks, g):
+    """x with its tied rows redrawn from the generator g until none is left -> (x, tied rows of the first draw)"""
+    from knife_units import resample_off_ties
+    is_tied = lambda x_: tied_rows(x_, layers, masks)          # noqa: E731
+    knife = is_tied(x)
+    (x,), _ = resample_off_ties(lambda: (torch.randn(x.shape, generator=g),), is_tied, first=(x,))
+    return x, knife
+
+
 def one(case, rng, only=None):
     M, nl, dims, mask_kind, need_x = params(rng)
     if only is not None and case != only:
@@ -54,27 +84,7 @@ def one(case, rng, only=None):
                 degs.append((do.to(DEV), dprev.to(DEV), strict))
             masks.append(m)
             dprev = do
-    # Rows with a hidden pre-activation within the fp32 chain's error bound of zero are REDRAWN from the same generator until none
-    # is left (rows are independent): there an fp32 chain and the fp64 one may gate differently, and ONE flipped gate moves that
-    # row's gradient by several per cent (at 60 000 rows x 256 units a walk meets a handful of such rows per case).  The bound of a
-    # layer = 16 fp32 ulps of its own terms' magnitude + the bound INHERITED from its inputs through |W|: behind a narrow
-    # bottleneck (walk 703, case 113: 255 -> 1 -> 198) the single input carries the roundoff of a 255-term sum, which is far more
-    # than 16 ulps of its own small value
-    def tied_rows(x_):
-        a = x_.double()
-        knife = torch.zeros(M, dtype=torch.bool)
-        aerr = torch.zeros(M, dims[0], dtype=torch.float64)      # bound on the fp32 chain's absolute error of the layer inputs
-        for l, (W, b) in enumerate(layers[:-1]):
-            Wm = (W * masks[l] if masks else W).double()
-            pre = torch.nn.functional.linear(a, Wm, b.double())
-            mag = a.abs() @ Wm.abs().t() + b.double().abs()
-            aerr = 16 * 2. ** -23 * mag + aerr @ Wm.abs().t()
-            knife |= ((pre.abs() < aerr) & (pre != 0)).any(1)
-            a = torch.relu(pre)
-        return knife
-    from knife_units import resample_off_ties
-    knife = tied_rows(x)
-    (x,), _ = resample_off_ties(lambda: (torch.randn(M, dims[0], generator=g),), tied_rows, first=(x,))
+    x, knife = redraw_off_ties(x, layers, masks, g)
     gy = torch.randn(M, dims[-1], generator=g)
     # fp64 reference
     xr = x.double().requires_grad_(need_x)
