@@ -23,7 +23,7 @@ MONO_MAX_LAYERS = 8
 MADE_MAX_HIDDEN = 8       # GNF_MADE_MAX_HIDDEN
 MADE_NORM_NONE, MADE_NORM_AFFINE = 0, 1
 DAG_PLAN_KC = 32          # GNF_DAG_PLAN_KC
-ABI_VERSION = 10          # GNF_ABI_VERSION of include/gnf_hip.h this binding was written against
+ABI_VERSION = 11          # GNF_ABI_VERSION of include/gnf_hip.h this binding was written against
 
 
 class MonoNet(ctypes.Structure):
@@ -128,6 +128,13 @@ SIGNATURES = {
                                          ctypes.c_void_p, c_i64, c_i64, c_stream]),
     "gnf_mnistcnn_conv_bwd_cols_a1": (c_int, [c_f, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p, c_f, ctypes.c_void_p, c_i64,
                                               c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p, c_i64, c_i64, c_stream]),
+    "gnf_lenet_conv_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "gnf_lenet_conv_feat": (c_i64, [c_int, c_int, c_int, c_int]),
+    "gnf_lenet_conv_fwd": (c_int, [c_f, c_i64, c_int, c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p, c_i64,
+                                   c_stream]),
+    "gnf_lenet_conv_bwd_ws_bytes": (c_i64, [c_int, c_int, c_int, c_int, c_i64]),
+    "gnf_lenet_conv_bwd": (c_int, [c_f, c_i64, c_int, c_int, c_int, c_int, c_f, c_f, c_f, c_f, ctypes.c_void_p, c_f, c_f,
+                                   c_i64, c_f, c_f, c_f, c_f, ctypes.c_void_p, c_i64, c_i64, c_stream]),
     "gnf_mnistcnn_sparse_ws_bytes": (c_i64, [c_i64, c_i64]),
     "gnf_mnistcnn_sparse_fwd": (c_int, [c_f, c_i64, c_f, ctypes.c_void_p, c_i64, ctypes.c_void_p, c_i64, c_f, c_f, c_f,
                                         c_f, c_f, c_f, c_i64, c_f, c_f, ctypes.c_void_p, ctypes.c_void_p, c_i64,

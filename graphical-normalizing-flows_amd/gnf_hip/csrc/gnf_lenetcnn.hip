@@ -1,0 +1,598 @@
+// LeNet convolutional front of CIFAR10CNN (models/MLP.py, reference :66-68) as the embedding net of a DAG conditioner:
+//     feat = flatten(pool2(relu(conv_k(6 -> 16)(pool2(relu(conv_k(C -> 6)(e)))))))      on rows e [n, C*H*W]
+// for the four geometries buildCIFAR10NormalizingFlow constructs, (C, H, W, k) = (3,32,32,5), (1,32,32,3), (1,16,16,3),
+// (1,8,8,2): feature widths 400 / 576 / 64 / 16.  Pooling is floor pooling (13 -> 6, 7 -> 3, 5 -> 2 drop the last row and
+// column; those conv outputs are never computed).  Everything between e and feat lives in LDS: no im2col, no map in HBM.
+//
+// gfx950 mapping.  One 256-thread workgroup walks over groups of IPB = 256 / P1^2 images (1 / 1 / 5 / 28): input, pooled
+// conv1 map (and the backward's gradient maps) of a group sit in LDS, 17 KB forward and 56 KB backward at (3,32,32,5), so
+// several workgroups share a CU and hide each other's barriers.
+//   conv1 + ReLU + pool: a thread owns ONE pooled position, its 2 x 2 window for all 6 channels = 24 accumulators, and reads
+//           the (k+1) x (k+1) patch of each input channel row by row from LDS;
+//   conv2 + ReLU + pool: a wavefront owns 4 (8 at (1,32,32,3)) output channels, a lane one ROW of one 2 x 2 pool window
+//           (2 positions), and the two rows of a window meet through one lane exchange;
+//   the weights are read through wave-uniform addresses, i.e. scalar loads into SGPRs: they cost no LDS and no VGPR.
+//
+// Why plain VALU FMAs and not v_mfma_f32_16x16x4_f32.  The fp32 matrix pipe has the rate of the fp32 vector pipe on gfx950
+// (64 FLOP / clk / SIMD, MI355X_MICROARCH), so MFMA can only save ISSUE slots and LDS traffic, not time per FLOP; with
+// N = 6 output channels 10 of the 16 columns of a tile are padding (conv1 would run at 37 % of the pipe), and the im2col
+// operand of a 16 x 16 x 4 step is 64 single LDS dwords per 1024 MACs.  The register-blocked direct form at (3,32,32,5):
+//     conv1: 1800 v_fmac per thread (24 accumulators x 75 taps) against 108 LDS dwords (3 channels x 6 x 6 patch)  = 17 : 1
+//     conv2: 1200 v_fmac per lane (2 positions x 4 channels x 150 taps) against 180 LDS dwords                     =  7 : 1
+// and a CU retires 2 wave-FMAs per clock against one ds_read_b32 per 2 clocks, i.e. it needs >= 4 : 1 to stay on the ALU.
+// 0.59 MMAC per image forward; lane utilisation 196 / 256 (conv1) and 50 / 64 (conv2).
+//
+// Decisions follow torch: the ReLU gate is `pre-activation > 0`, a pool window takes its FIRST maximum in row-major scan
+// order (strict > when a later entry replaces an earlier one), always.
+//
+// Backward.  conv1 is recomputed (its pooled activations are the operand of dW2 and are needed in any case, and the
+// recompute yields pool 1's argmax for free), conv2's pool decision (one byte per feature: 0..3 = window entry that carries
+// the gradient, 4 = gated off) is either read from the plane the forward saved or recomputed when the caller passes NULL.
+// A pooled gradient has ONE non-zero per 2 x 2 window, so the two weight gradients run over (value, offset) lists -- a quarter
+// of the dense work -- while the two data gradients (da1, de) gather from the dense maps, bounds checked.  Weight gradients
+// are accumulated in registers over all images of a workgroup, written once per workgroup to the caller's workspace and
+// summed over workgroups in a fixed order by a second kernel: no float atomics, the same bits on every call.
+#include "gnf_common.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kFwdGridMax = 1024;     // 4 workgroups per CU
+constexpr int kBwdGridMax = 512;      // 2 workgroups per CU (56 KB of LDS each at the largest geometry)
+
+template <int C_, int H_, int K_>
+struct Geo {
+  static constexpr int C = C_, H = H_, W = H_, K = K_;
+  static constexpr int HW = H * W, IMG = C * HW;
+  static constexpr int H1 = H - K + 1;          // conv1 output side
+  static constexpr int P1 = H1 / 2;             // pooled (floor)
+  static constexpr int NP1 = P1 * P1;
+  static constexpr int U1 = 2 * P1;             // conv1 outputs a pool window covers
+  static constexpr int H2 = P1 - K + 1;         // conv2 output side
+  static constexpr int P2 = H2 / 2;
+  static constexpr int NP2 = P2 * P2;
+  static constexpr int U2 = 2 * P2;
+  static constexpr int F = 16 * NP2;            // feature width
+  static constexpr int T1 = C * K * K;          // taps of one conv1 output channel
+  static constexpr int T2 = 6 * K * K;
+  static constexpr int IPB = kThreads / NP1;    // images of one group
+  static constexpr int S2 = IPB * NP2 * 2;      // conv2 lanes: (image, window, window row)
+  static constexpr int WPG = (S2 + 63) / 64;    // wavefronts that share a channel group
+  static constexpr int CG = 4 * WPG;            // channels of a wavefront
+  static constexpr int R2 = (T2 + 63) / 64;     // dW2: rounds of 64 taps
+  static constexpr int J1 = (6 * T1 + kThreads - 1) / kThreads;   // dW1: entries per thread
+  static constexpr int PW = 6 * T1 + 6 + 16 * T2 + 16;            // floats of one workgroup's partial gradients
+  static_assert(IPB >= 1 && (WPG == 1 || WPG == 2) && P2 >= 1, "geometry");
+};
+
+struct float2i { float v; int off; };   // a gradient and the offset of the window entry it belongs to
+
+// The weights reach the FMAs as SGPR operands through scalar loads.  Left alone, instruction selection emits every invariant
+// load of a 3000-FMA block first: several hundred SGPRs, spilled into VGPR lanes and on to scratch.  So the weights are
+// walked in memory order in STAGES of GS groups of KK contiguous floats, double buffered by hand: the loads of stage st + 1
+// are issued, then -- between two scheduling barriers -- stage st is consumed.  body(g, w, z) applies group g's KK weights
+// and ties every accumulator it has updated to `z` with an empty volatile asm (tie()); z is the zero the loads of stage st + 2
+// add to their address, which is what keeps them BEHIND the arithmetic of stage st -- and the arithmetic in its stage.
+__device__ __forceinline__ void tie(int& z, float& a) { asm volatile("" : "+s"(z), "+v"(a)); }
+__device__ __forceinline__ void tie(int& z, float& a, float& b) { asm volatile("" : "+s"(z), "+v"(a), "+v"(b)); }
+__device__ __forceinline__ void tie(int& z, float& a, float& b, float& c, float& d) {
+  asm volatile("" : "+s"(z), "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+}
+
+template <int K>
+struct Stage { static constexpr int GS = K >= 5 ? 1 : (K == 3 ? 3 : 6); };
+
+template <int NG, int KK, int GS_, class Addr, class Body>
+__device__ __forceinline__ void staged_weights(Addr addr, Body body) {
+  constexpr int GS = GS_ < NG ? GS_ : NG;
+  constexpr int NS = (NG + GS - 1) / GS;
+  float w[2][GS * KK];
+  int z = opaque_s(0);
+  auto load = [&](int st, float* dst) {
+#pragma unroll
+    for (int q = 0; q < GS; ++q)
+      if (st * GS + q < NG) {
+        const float* p = addr(st * GS + q) + z;
+#pragma unroll
+        for (int t = 0; t < KK; ++t) dst[q * KK + t] = p[t];
+      }
+  };
+  load(0, w[0]);
+#pragma unroll
+  for (int st = 0; st < NS; ++st) {
+    if (st + 1 < NS) load(st + 1, w[(st + 1) & 1]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int q = 0; q < GS; ++q)
+      if (st * GS + q < NG) {
+        body(st * GS + q, &w[st & 1][q * KK], z);
+      }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------- forward phases
+// conv1 + bias + ReLU + pool of the group's images in xs -> a1s [IPB][6][P1][P1]; arg1s (LDS, may be null): 0..3 = the window
+// entry that carries the gradient, 4 = the pooled value is 0 (every entry gated off)
+template <class G>
+__device__ __forceinline__ void conv1_phase(const float* xs, float* a1s, unsigned char* arg1s, const float* __restrict__ W1,
+                                            const float* __restrict__ b1, int tid) {
+  const int s = tid / G::NP1, p = tid % G::NP1;
+  if (s >= G::IPB) return;
+  const int py = p / G::P1, px = p % G::P1;
+  const float* xb = xs + s * G::IMG + 2 * py * G::W + 2 * px;
+  float acc[2][2][6];
+#pragma unroll
+  for (int o = 0; o < 6; ++o) acc[0][0][o] = acc[0][1][o] = acc[1][0][o] = acc[1][1][o] = b1[o];
+  float v[G::K + 1][G::K + 1];
+  staged_weights<6 * G::C, G::K * G::K, Stage<G::K>::GS>(
+      [&](int g) { return W1 + ((g % 6) * G::C + g / 6) * G::K * G::K; },     // group g = (c, o), c outer
+      [&](int g, const float* w, int& z) {
+        const int c = g / 6, o = g % 6;
+        if (o == 0) {
+#pragma unroll
+          for (int r = 0; r <= G::K; ++r)
+#pragma unroll
+            for (int j = 0; j <= G::K; ++j) v[r][j] = xb[c * G::HW + r * G::W + j];
+        }
+#pragma unroll
+        for (int ky = 0; ky < G::K; ++ky)
+#pragma unroll
+          for (int kx = 0; kx < G::K; ++kx) {
+            const float wk = w[ky * G::K + kx];
+            acc[0][0][o] = fmaf(v[ky][kx], wk, acc[0][0][o]);
+            acc[0][1][o] = fmaf(v[ky][kx + 1], wk, acc[0][1][o]);
+            acc[1][0][o] = fmaf(v[ky + 1][kx], wk, acc[1][0][o]);
+            acc[1][1][o] = fmaf(v[ky + 1][kx + 1], wk, acc[1][1][o]);
+          }
+        tie(z, acc[0][0][o], acc[0][1][o], acc[1][0][o], acc[1][1][o]);
+      });
+#pragma unroll
+  for (int o = 0; o < 6; ++o) {
+    float m = fmaxf(acc[0][0][o], 0.f);
+    int idx = 0;
+    float t = fmaxf(acc[0][1][o], 0.f);
+    if (t > m) { m = t; idx = 1; }
+    t = fmaxf(acc[1][0][o], 0.f);
+    if (t > m) { m = t; idx = 2; }
+    t = fmaxf(acc[1][1][o], 0.f);
+    if (t > m) { m = t; idx = 3; }
+    a1s[(s * 6 + o) * G::NP1 + p] = m;
+    if (arg1s) arg1s[(s * 6 + o) * G::NP1 + p] = (unsigned char)(m > 0.f ? idx : 4);
+  }
+}
+
+// conv2 + bias + ReLU + pool of a1s; emit(s, channel, window, pooled value, code) once per feature.  No barrier inside;
+// every lane runs the exchange (an idle lane works on slot 0 and emits nothing).
+template <class G, class Emit>
+__device__ __forceinline__ void conv2_phase(const float* a1s, const float* __restrict__ W2, const float* __restrict__ b2,
+                                            int tid, Emit emit) {
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int g = wave / G::WPG;                                   // wave-uniform: the weights go through scalar loads
+  const int q = (wave % G::WPG) * 64 + lane;
+  const bool active = q < G::S2;
+  const int qq = active ? q : 0;
+  const int s = qq / (2 * G::NP2), rem = qq % (2 * G::NP2), cell = rem >> 1, dy = rem & 1;
+  const int cy = cell / G::P2, cx = cell % G::P2;
+  const float* ab = a1s + s * 6 * G::NP1 + (2 * cy + dy) * G::P1 + 2 * cx;
+  const float* wg = W2 + g * G::CG * G::T2;
+  float acc[2][G::CG];
+#pragma unroll
+  for (int j = 0; j < G::CG; ++j) acc[0][j] = acc[1][j] = b2[g * G::CG + j];
+  float v[G::K][G::K + 1];
+  staged_weights<6 * G::CG, G::K * G::K, Stage<G::K>::GS>(
+      [&](int gq) { return wg + ((gq % G::CG) * 6 + gq / G::CG) * G::K * G::K; },   // group = (ci, j), ci outer
+      [&](int gq, const float* w, int& z) {
+        const int ci = gq / G::CG, j = gq % G::CG;
+        if (j == 0) {
+#pragma unroll
+          for (int ky = 0; ky < G::K; ++ky)
+#pragma unroll
+            for (int i = 0; i <= G::K; ++i) v[ky][i] = ab[ci * G::NP1 + ky * G::P1 + i];
+        }
+#pragma unroll
+        for (int ky = 0; ky < G::K; ++ky)
+#pragma unroll
+          for (int kx = 0; kx < G::K; ++kx) {
+            const float wk = w[ky * G::K + kx];
+            acc[0][j] = fmaf(v[ky][kx], wk, acc[0][j]);
+            acc[1][j] = fmaf(v[ky][kx + 1], wk, acc[1][j]);
+          }
+        tie(z, acc[0][j], acc[1][j]);
+      });
+#pragma unroll
+  for (int j = 0; j < G::CG; ++j) {
+    float m = fmaxf(acc[0][j], 0.f);
+    int idx = 2 * dy;
+    const float t = fmaxf(acc[1][j], 0.f);
+    if (t > m) { m = t; idx = 2 * dy + 1; }
+    const float mo = __shfl_xor(m, 1, GNF_WAVE);                 // the window's other row: lanes 2i (row 0) and 2i + 1
+    const int io = __shfl_xor(idx, 1, GNF_WAVE);
+    if (active && dy == 0) {
+      if (mo > m) { m = mo; idx = io; }                          // row 0 keeps a tie: first maximum in scan order
+      emit(s, g * G::CG + j, cell, m, m > 0.f ? idx : 4);
+    }
+  }
+}
+
+// the group's inputs -> xs (zeros for the images past the end)
+template <class G>
+__device__ __forceinline__ void stage_inputs(float* xs, const float* __restrict__ e, int64_t ld_e, int64_t i0, int64_t n,
+                                             int tid) {
+  for (int i = tid; i < G::IPB * G::IMG; i += kThreads) {
+    const int s = i / G::IMG, r = i % G::IMG;
+    const int64_t im = i0 + s;
+    xs[i] = im < n ? e[im * ld_e + r] : 0.f;
+  }
+}
+
+template <class G>
+__global__ __launch_bounds__(kThreads, 4) void lenet_fwd_k(const float* __restrict__ e, int64_t ld_e,
+                                                        const float* __restrict__ W1, const float* __restrict__ b1,
+                                                        const float* __restrict__ W2, const float* __restrict__ b2,
+                                                        float* __restrict__ feat, unsigned char* __restrict__ arg2,
+                                                        int64_t n) {
+  __shared__ float xs[G::IPB * G::IMG];
+  __shared__ float a1s[G::IPB * 6 * G::NP1];
+  const int tid = threadIdx.x;
+  for (int64_t i0 = (int64_t)blockIdx.x * G::IPB; i0 < n; i0 += (int64_t)gridDim.x * G::IPB) {
+    stage_inputs<G>(xs, e, ld_e, i0, n, tid);
+    __syncthreads();
+    conv1_phase<G>(xs, a1s, nullptr, W1, b1, tid);
+    __syncthreads();
+    conv2_phase<G>(a1s, W2, b2, tid, [&](int s, int ch, int cell, float m, int code) {
+      const int64_t im = i0 + s;
+      if (im < n) {
+        feat[im * G::F + ch * G::NP2 + cell] = m;
+        if (arg2) arg2[im * G::F + ch * G::NP2 + cell] = (unsigned char)code;
+      }
+    });
+    __syncthreads();
+  }
+}
+
+// --------------------------------------------------------------------------------------------------------------- backward
+template <class G, bool RECOMPUTE>
+__global__ __launch_bounds__(kThreads, 2) void lenet_bwd_k(const float* __restrict__ e, int64_t ld_e,
+                                                        const float* __restrict__ W1, const float* __restrict__ b1,
+                                                        const float* __restrict__ W2, const float* __restrict__ b2,
+                                                        const unsigned char* __restrict__ arg2,
+                                                        const float* __restrict__ g_feat, float* __restrict__ ge,
+                                                        int64_t ld_ge, float* __restrict__ part, int64_t n) {
+  __shared__ float xs[G::IPB * G::IMG];
+  __shared__ float a1s[G::IPB * 6 * G::NP1];
+  __shared__ float d2[G::IPB * 16 * G::U2 * G::U2];      // dL/d(conv2 pre-activation), dense
+  __shared__ float2i l2[G::IPB * G::F];                  // ... as one (value, a1 offset of the entry) per window
+  __shared__ float d1[G::IPB * 6 * G::U1 * G::U1];       // dL/d(conv1 pre-activation), dense
+  __shared__ float2i l1[G::IPB * 6 * G::NP1];            // ... as one (value, input offset of the entry) per window
+  __shared__ unsigned char arg1s[G::IPB * 6 * G::NP1];
+  __shared__ unsigned char arg2s[RECOMPUTE ? G::IPB * G::F : 1];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+  // dW2 / db2: wavefront `wave` owns the channels 4 wave .. 4 wave + 3, a lane the taps lane + 64 rr
+  float accW2[4][G::R2], accb2[4];
+  int abase[G::R2];
+#pragma unroll
+  for (int rr = 0; rr < G::R2; ++rr) {
+    const int tap = lane + 64 * rr < G::T2 ? lane + 64 * rr : 0;
+    const int ci = tap / (G::K * G::K), kk = tap % (G::K * G::K);
+    abase[rr] = ci * G::NP1 + (kk / G::K) * G::P1 + kk % G::K;
+  }
+#pragma unroll
+  for (int jj = 0; jj < 4; ++jj) {
+    accb2[jj] = 0.f;
+#pragma unroll
+    for (int rr = 0; rr < G::R2; ++rr) accW2[jj][rr] = 0.f;
+  }
+  // dW1 / db1: thread owns the entries tid + 256 j of [6][C][k][k]
+  float accW1[G::J1], accb1[G::J1];
+  int xbase[G::J1], o1[G::J1];
+#pragma unroll
+  for (int j = 0; j < G::J1; ++j) {
+    const int en = tid + kThreads * j < 6 * G::T1 ? tid + kThreads * j : 0;
+    const int tap = en % G::T1, c = tap / (G::K * G::K), kk = tap % (G::K * G::K);
+    o1[j] = en / G::T1;
+    xbase[j] = c * G::HW + (kk / G::K) * G::W + kk % G::K;
+    accW1[j] = accb1[j] = 0.f;
+  }
+
+  for (int64_t i0 = (int64_t)blockIdx.x * G::IPB; i0 < n; i0 += (int64_t)gridDim.x * G::IPB) {
+    stage_inputs<G>(xs, e, ld_e, i0, n, tid);
+    __syncthreads();
+    conv1_phase<G>(xs, a1s, arg1s, W1, b1, tid);
+    __syncthreads();
+    if (RECOMPUTE) {
+      conv2_phase<G>(a1s, W2, b2, tid, [&](int s, int ch, int cell, float, int code) {
+        arg2s[s * G::F + ch * G::NP2 + cell] = (unsigned char)code;
+      });
+      __syncthreads();
+    }
+    // the cotangent of the features through pool 2 and ReLU: dense map and list
+    for (int i = tid; i < G::IPB * G::F; i += kThreads) {
+      const int s = i / G::F, r = i % G::F, ch = r / G::NP2, cell = r % G::NP2;
+      const int cy = cell / G::P2, cx = cell % G::P2;
+      const int64_t im = i0 + s;
+      int code = 4;
+      if (im < n) code = RECOMPUTE ? arg2s[i] : arg2[im * G::F + r];
+      const float g = code < 4 ? g_feat[im * G::F + r] : 0.f;
+      float* dd = d2 + (s * 16 + ch) * G::U2 * G::U2 + 2 * cy * G::U2 + 2 * cx;
+      dd[0] = code == 0 ? g : 0.f;
+      dd[1] = code == 1 ? g : 0.f;
+      dd[G::U2] = code == 2 ? g : 0.f;
+      dd[G::U2 + 1] = code == 3 ? g : 0.f;
+      l2[i] = float2i{g, (2 * cy + ((code >> 1) & 1)) * G::P1 + 2 * cx + (code & 1)};
+    }
+    __syncthreads();
+    // dW2[o][ci][ky][kx] += g * a1[ci][y + ky][x + kx] over the windows' entries
+#pragma unroll 1
+    for (int s = 0; s < G::IPB; ++s)
+#pragma unroll 1
+      for (int cell = 0; cell < G::NP2; ++cell)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          const float2i q = l2[(s * 16 + wave * 4 + jj) * G::NP2 + cell];
+          accb2[jj] += q.v;
+#pragma unroll
+          for (int rr = 0; rr < G::R2; ++rr)
+            accW2[jj][rr] = fmaf(q.v, a1s[s * 6 * G::NP1 + abase[rr] + q.off], accW2[jj][rr]);
+        }
+    // da1[ci][y][x] = sum_{o, ky, kx} dpre2[o][y - ky][x - kx] W2[o][ci][ky][kx], then through pool 1 and ReLU
+    {
+      const int s = tid / G::NP1, p = tid % G::NP1;
+      if (s < G::IPB) {
+        const int py = p / G::P1, px = p % G::P1;
+        float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        const float* db = d2 + s * 16 * G::U2 * G::U2;
+#pragma unroll 1
+        for (int o = 0; o < 16; ++o) {                 // a rolled loop: the 6 k^2 weights of one o are contiguous scalar loads
+          const float* wo = W2 + o * G::T2;
+          const float* dd = db + o * G::U2 * G::U2;
+          float d[G::K * G::K];
+#pragma unroll
+          for (int ky = 0; ky < G::K; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < G::K; ++kx) {
+              const int yy = py - ky, xx = px - kx;
+              const bool valid = (unsigned)yy < (unsigned)G::U2 && (unsigned)xx < (unsigned)G::U2;
+              d[ky * G::K + kx] = valid ? dd[valid ? yy * G::U2 + xx : 0] : 0.f;
+            }
+          staged_weights<6, G::K * G::K, Stage<G::K>::GS>([&](int ci) { return wo + ci * G::K * G::K; },
+                                                          [&](int ci, const float* w, int& z) {
+#pragma unroll
+                                                            for (int t = 0; t < G::K * G::K; ++t)
+                                                              acc[ci] = fmaf(d[t], w[t], acc[ci]);
+                                                            tie(z, acc[ci]);
+                                                          });
+        }
+#pragma unroll
+        for (int ci = 0; ci < 6; ++ci) {
+          const int code = arg1s[(s * 6 + ci) * G::NP1 + p];
+          const float g = code < 4 ? acc[ci] : 0.f;
+          float* dd = d1 + (s * 6 + ci) * G::U1 * G::U1 + 2 * py * G::U1 + 2 * px;
+          dd[0] = code == 0 ? g : 0.f;
+          dd[1] = code == 1 ? g : 0.f;
+          dd[G::U1] = code == 2 ? g : 0.f;
+          dd[G::U1 + 1] = code == 3 ? g : 0.f;
+          l1[(s * 6 + ci) * G::NP1 + p] = float2i{g, (2 * py + ((code >> 1) & 1)) * G::W + 2 * px + (code & 1)};
+        }
+      }
+    }
+    __syncthreads();
+    // dW1[o][c][ky][kx] += g * e[c][y + ky][x + kx] over the windows' entries
+#pragma unroll 1
+    for (int s = 0; s < G::IPB; ++s)
+#pragma unroll 4
+      for (int p = 0; p < G::NP1; ++p)
+#pragma unroll
+        for (int j = 0; j < G::J1; ++j) {
+          const float2i q = l1[(s * 6 + o1[j]) * G::NP1 + p];
+          accb1[j] += q.v;
+          accW1[j] = fmaf(q.v, xs[s * G::IMG + xbase[j] + q.off], accW1[j]);
+        }
+    // de[c][Y][X] = sum_{o, ky, kx} dpre1[o][Y - ky][X - kx] W1[o][c][ky][kx]
+    if (ge) {
+      for (int i = tid; i < G::IPB * G::HW; i += kThreads) {
+        const int s = i / G::HW, r = i % G::HW, Y = r / G::W, X = r % G::W;
+        float acc[G::C];
+#pragma unroll
+        for (int c = 0; c < G::C; ++c) acc[c] = 0.f;
+        const float* db = d1 + s * 6 * G::U1 * G::U1;
+#pragma unroll 1
+        for (int o = 0; o < 6; ++o) {
+          const float* wo = W1 + o * G::T1;
+          const float* dd = db + o * G::U1 * G::U1;
+          float d[G::K * G::K];
+#pragma unroll
+          for (int ky = 0; ky < G::K; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < G::K; ++kx) {
+              const int yy = Y - ky, xx = X - kx;
+              const bool valid = (unsigned)yy < (unsigned)G::U1 && (unsigned)xx < (unsigned)G::U1;
+              d[ky * G::K + kx] = valid ? dd[valid ? yy * G::U1 + xx : 0] : 0.f;
+            }
+          staged_weights<G::C, G::K * G::K, Stage<G::K>::GS>([&](int c) { return wo + c * G::K * G::K; },
+                                                             [&](int c, const float* w, int& z) {
+#pragma unroll
+                                                               for (int t = 0; t < G::K * G::K; ++t)
+                                                                 acc[c] = fmaf(d[t], w[t], acc[c]);
+                                                               tie(z, acc[c]);
+                                                             });
+        }
+        const int64_t im = i0 + s;
+        if (im < n)
+#pragma unroll
+          for (int c = 0; c < G::C; ++c) ge[im * ld_ge + c * G::HW + r] = acc[c];
+      }
+    }
+    __syncthreads();
+  }
+
+  // this workgroup's partial gradients: [dW1 6*T1][db1 6][dW2 16*T2][db2 16]
+  float* prow = part + (int64_t)blockIdx.x * G::PW;
+#pragma unroll
+  for (int j = 0; j < G::J1; ++j) {
+    const int en = tid + kThreads * j;
+    if (en < 6 * G::T1) {
+      prow[en] = accW1[j];
+      if (en % G::T1 == 0) prow[6 * G::T1 + en / G::T1] = accb1[j];
+    }
+  }
+#pragma unroll
+  for (int jj = 0; jj < 4; ++jj) {
+#pragma unroll
+    for (int rr = 0; rr < G::R2; ++rr)
+      if (lane + 64 * rr < G::T2) prow[6 * G::T1 + 6 + (wave * 4 + jj) * G::T2 + lane + 64 * rr] = accW2[jj][rr];
+    if (lane == 0) prow[6 * G::T1 + 6 + 16 * G::T2 + wave * 4 + jj] = accb2[jj];
+  }
+}
+
+// out[en] = sum over the workgroups' partial rows, four interleaved chains in a fixed order (nb = 0: zeros)
+__global__ __launch_bounds__(kThreads) void lenet_reduce_k(const float* __restrict__ part, int nb, int pw, int n1, int n2,
+                                                           float* __restrict__ gW1, float* __restrict__ gb1,
+                                                           float* __restrict__ gW2, float* __restrict__ gb2) {
+  const int en = blockIdx.x * kThreads + threadIdx.x;
+  if (en >= pw) return;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  int b = 0;
+  for (; b + 4 <= nb; b += 4) {
+    s0 += part[(int64_t)b * pw + en];
+    s1 += part[(int64_t)(b + 1) * pw + en];
+    s2 += part[(int64_t)(b + 2) * pw + en];
+    s3 += part[(int64_t)(b + 3) * pw + en];
+  }
+  for (; b < nb; ++b) s0 += part[(int64_t)b * pw + en];
+  const float v = (s0 + s1) + (s2 + s3);
+  if (en < n1) gW1[en] = v;
+  else if (en < n1 + 6) gb1[en - n1] = v;
+  else if (en < n1 + 6 + n2) gW2[en - n1 - 6] = v;
+  else gb2[en - n1 - 6 - n2] = v;
+}
+
+// ------------------------------------------------------------------------------------------------------------------- host
+typedef Geo<3, 32, 5> G0;
+typedef Geo<1, 32, 3> G1;
+typedef Geo<1, 16, 3> G2;
+typedef Geo<1, 8, 2> G3;
+static_assert(G0::F == 400 && G1::F == 576 && G2::F == 64 && G3::F == 16, "feature widths of the factory's geometries");
+
+int geo_index(int C, int H, int W, int k) {
+  if (C == 3 && H == 32 && W == 32 && k == 5) return 0;
+  if (C == 1 && H == 32 && W == 32 && k == 3) return 1;
+  if (C == 1 && H == 16 && W == 16 && k == 3) return 2;
+  if (C == 1 && H == 8 && W == 8 && k == 2) return 3;
+  return -1;
+}
+
+inline bool bad_f32(const void* p) { return ((uintptr_t)p & 3) != 0; }
+
+template <class G>
+int grid_of(int64_t n, int cap) {
+  const int64_t groups = (n + G::IPB - 1) / G::IPB;
+  return (int)(groups < cap ? groups : cap);
+}
+
+template <class G>
+int fwd_launch(const float* e, int64_t ld_e, const float* W1, const float* b1, const float* W2, const float* b2, float* feat,
+               unsigned char* arg2, int64_t n, hipStream_t s) {
+  if (ld_e < G::IMG) return GNF_EINVAL;
+  hipLaunchKernelGGL(lenet_fwd_k<G>, dim3(grid_of<G>(n, kFwdGridMax)), dim3(kThreads), 0, s, e, ld_e, W1, b1, W2, b2, feat,
+                     arg2, n);
+  GNF_LAUNCH_CHECK();
+  return 0;
+}
+
+template <class G>
+int bwd_launch(const float* e, int64_t ld_e, const float* W1, const float* b1, const float* W2, const float* b2,
+               const unsigned char* arg2, const float* g_feat, float* ge, int64_t ld_ge, float* gW1, float* gb1, float* gW2,
+               float* gb2, float* part, int64_t n, hipStream_t s) {
+  if (n > 0 && (ld_e < G::IMG || (ge && ld_ge < G::IMG))) return GNF_EINVAL;
+  const int nb = n > 0 ? grid_of<G>(n, kBwdGridMax) : 0;
+  if (nb > 0) {
+    if (arg2)
+      hipLaunchKernelGGL((lenet_bwd_k<G, false>), dim3(nb), dim3(kThreads), 0, s, e, ld_e, W1, b1, W2, b2, arg2, g_feat, ge,
+                         ld_ge, part, n);
+    else
+      hipLaunchKernelGGL((lenet_bwd_k<G, true>), dim3(nb), dim3(kThreads), 0, s, e, ld_e, W1, b1, W2, b2, arg2, g_feat, ge,
+                         ld_ge, part, n);
+    GNF_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(lenet_reduce_k, dim3((G::PW + kThreads - 1) / kThreads), dim3(kThreads), 0, s, part, nb, G::PW,
+                     6 * G::T1, 16 * G::T2, gW1, gb1, gW2, gb2);
+  GNF_LAUNCH_CHECK();
+  return 0;
+}
+
+template <class G>
+int64_t ws_bytes_of(int64_t n) {
+  const int64_t nb = n > 0 ? grid_of<G>(n, kBwdGridMax) : 1;
+  return nb * G::PW * (int64_t)sizeof(float);
+}
+
+}  // namespace
+
+extern "C" {
+
+int gnf_lenet_conv_supported(int C, int H, int W, int k) { return geo_index(C, H, W, k) >= 0; }
+
+int64_t gnf_lenet_conv_feat(int C, int H, int W, int k) {
+  switch (geo_index(C, H, W, k)) {
+    case 0: return G0::F;
+    case 1: return G1::F;
+    case 2: return G2::F;
+    case 3: return G3::F;
+  }
+  return GNF_ESHAPE;
+}
+
+int gnf_lenet_conv_fwd(const float* e, int64_t ld_e, int C, int H, int W, int k, const float* W1, const float* b1,
+                       const float* W2, const float* b2, float* feat, unsigned char* argmax2, int64_t n_img,
+                       gnf_stream_t stream) {
+  const int gi = geo_index(C, H, W, k);
+  if (gi < 0) return GNF_ESHAPE;
+  if (n_img < 0 || !W1 || !b1 || !W2 || !b2 || ((!e || !feat) && n_img > 0)) return GNF_EINVAL;
+  if (bad_f32(e) || bad_f32(W1) || bad_f32(b1) || bad_f32(W2) || bad_f32(b2) || bad_f32(feat)) return GNF_EINVAL;
+  if (n_img == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  switch (gi) {
+    case 0: return fwd_launch<G0>(e, ld_e, W1, b1, W2, b2, feat, argmax2, n_img, s);
+    case 1: return fwd_launch<G1>(e, ld_e, W1, b1, W2, b2, feat, argmax2, n_img, s);
+    case 2: return fwd_launch<G2>(e, ld_e, W1, b1, W2, b2, feat, argmax2, n_img, s);
+    default: return fwd_launch<G3>(e, ld_e, W1, b1, W2, b2, feat, argmax2, n_img, s);
+  }
+}
+
+int64_t gnf_lenet_conv_bwd_ws_bytes(int C, int H, int W, int k, int64_t n_img) {
+  if (n_img < 0) return GNF_EINVAL;
+  switch (geo_index(C, H, W, k)) {
+    case 0: return ws_bytes_of<G0>(n_img);
+    case 1: return ws_bytes_of<G1>(n_img);
+    case 2: return ws_bytes_of<G2>(n_img);
+    case 3: return ws_bytes_of<G3>(n_img);
+  }
+  return GNF_ESHAPE;
+}
+
+int gnf_lenet_conv_bwd(const float* e, int64_t ld_e, int C, int H, int W, int k, const float* W1, const float* b1,
+                       const float* W2, const float* b2, const unsigned char* argmax2, const float* g_feat, float* ge,
+                       int64_t ld_ge, float* gW1, float* gb1, float* gW2, float* gb2, void* ws, int64_t ws_bytes,
+                       int64_t n_img, gnf_stream_t stream) {
+  const int gi = geo_index(C, H, W, k);
+  if (gi < 0) return GNF_ESHAPE;
+  if (n_img < 0 || !W1 || !b1 || !W2 || !b2 || !gW1 || !gb1 || !gW2 || !gb2 || !ws || ((!e || !g_feat) && n_img > 0))
+    return GNF_EINVAL;
+  if (bad_f32(e) || bad_f32(W1) || bad_f32(b1) || bad_f32(W2) || bad_f32(b2) || bad_f32(g_feat) || bad_f32(ge) ||
+      bad_f32(gW1) || bad_f32(gb1) || bad_f32(gW2) || bad_f32(gb2) || bad_f32(ws))
+    return GNF_EINVAL;
+  if (ws_bytes < gnf_lenet_conv_bwd_ws_bytes(C, H, W, k, n_img)) return GNF_EWS;
+  hipStream_t s = (hipStream_t)stream;
+  float* part = static_cast<float*>(ws);
+  switch (gi) {
+    case 0: return bwd_launch<G0>(e, ld_e, W1, b1, W2, b2, argmax2, g_feat, ge, ld_ge, gW1, gb1, gW2, gb2, part, n_img, s);
+    case 1: return bwd_launch<G1>(e, ld_e, W1, b1, W2, b2, argmax2, g_feat, ge, ld_ge, gW1, gb1, gW2, gb2, part, n_img, s);
+    case 2: return bwd_launch<G2>(e, ld_e, W1, b1, W2, b2, argmax2, g_feat, ge, ld_ge, gW1, gb1, gW2, gb2, part, n_img, s);
+    default: return bwd_launch<G3>(e, ld_e, W1, b1, W2, b2, argmax2, g_feat, ge, ld_ge, gW1, gb1, gW2, gb2, part, n_img, s);
+  }
+}
+
+}  // extern "C"

@@ -560,6 +560,56 @@ def mnist_conv(e, W1, b1, W2, b2, exact_ties=False):
     return MnistConvFn.apply(e, W1, b1, W2, b2, exact_ties, torch.is_grad_enabled())
 
 
+# ----------------------------------------------------------------------------- CIFAR10CNN conv front
+def lenet_conv_supported(size_img, k):
+    """the geometries gnf_lenet_conv_* is instantiated for (the four of buildCIFAR10NormalizingFlow)"""
+    c, h, w = size_img
+    return bool(abi.load().gnf_lenet_conv_supported(int(c), int(h), int(w), int(k)))
+
+
+class LenetConvFn(torch.autograd.Function):
+    """flatten(pool2(relu(conv_k(6->16)(pool2(relu(conv_k(C->6)(e))))))) on rows e [n, C*H*W] (reference models/MLP.py:66-68),
+    fused in LDS (csrc/gnf_lenetcnn.hip).  The forward keeps the second pool's decisions (one byte per feature) when a
+    backward will come; the backward recomputes conv1 and, without that plane, conv2 as well."""
+
+    @staticmethod
+    def forward(ctx, e, W1, b1, W2, b2, size_img, k, grad_mode=None):
+        c, h, w = (int(v) for v in size_img)
+        k = int(k)
+        if e.stride(-1) != 1 or e.stride(0) < c * h * w:
+            e = e.contiguous()
+        n = e.shape[0]
+        W1c, b1c, W2c, b2c = W1.contiguous(), b1.contiguous(), W2.contiguous(), b2.contiguous()
+        F = int(abi.load().gnf_lenet_conv_feat(c, h, w, k))
+        feat = _empty((n, F), e)
+        keep = bool(grad_mode) and any(ctx.needs_input_grad) and os.environ.get("GNF_LENET_SAVE_ARGMAX", "1") != "0"
+        arg = torch.empty((n, F), dtype=torch.uint8, device=e.device) if keep else None
+        call("gnf_lenet_conv_fwd", ptr(e), e.stride(0), c, h, w, k, ptr(W1c), ptr(b1c), ptr(W2c), ptr(b2c), ptr(feat),
+             abi.rawptr(arg) if keep else None, n, stream())
+        ctx.save_for_backward(e, W1c, b1c, W2c, b2c)
+        ctx.arg, ctx.geo = arg, (c, h, w, k)
+        return feat
+
+    @staticmethod
+    def backward(ctx, gf):
+        e, W1, b1, W2, b2 = ctx.saved_tensors
+        c, h, w, k = ctx.geo
+        n = e.shape[0]
+        gf = gf.contiguous()
+        ge = _empty((n, c * h * w), e) if ctx.needs_input_grad[0] else None
+        outs = [grad_out_shared(p) for p in (W1, b1, W2, b2)]
+        nws = abi.load().gnf_lenet_conv_bwd_ws_bytes(c, h, w, k, n)
+        ws = _ws(nws, e)
+        call("gnf_lenet_conv_bwd", ptr(e), e.stride(0), c, h, w, k, ptr(W1), ptr(b1), ptr(W2), ptr(b2),
+             abi.rawptr(ctx.arg) if ctx.arg is not None else None, ptr(gf), ptr(ge), c * h * w,
+             *(ptr(t) for t, _, _ in outs), abi.rawptr(ws), nws, n, stream())
+        return (ge, *(finish(t) for t, finish, _ in outs), None, None, None)
+
+
+def lenet_conv(e, W1, b1, W2, b2, size_img, k):
+    return LenetConvFn.apply(e, W1, b1, W2, b2, size_img, k, torch.is_grad_enabled())
+
+
 def crop_origin(p):
     """cell origin of the 5x5 pooled block that can deviate from the background for a pixel row / column p"""
     return min(max((p - 6) >> 1, 0), 7)

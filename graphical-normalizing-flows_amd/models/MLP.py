@@ -4,7 +4,8 @@ Same class names, constructor arguments, attribute names and therefore `state_di
 `fc1/fc2[/fc3]`).  What differs is how they run: Linear/ReLU chains go through the fused MFMA GEMM chain
 (gnf_hip.ops.mlp); the convolutional front of `MNISTCNN` on 28x28 single-channel images -- the embedding net of the
 MNIST DAG flow, evaluated on B*d masked images per step -- is one LDS-resident Winograd/MFMA kernel pair
-(gnf_hip.ops.MnistConvFn, csrc/gnf_mnistcnn.hip)."""
+(gnf_hip.ops.MnistConvFn, csrc/gnf_mnistcnn.hip); the LeNet front of `CIFAR10CNN`, the embedding net of the CIFAR-10 DAG
+flows, is a direct-convolution kernel pair (gnf_hip.ops.LenetConvFn, csrc/gnf_lenetcnn.hip)."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -159,8 +160,10 @@ class MNISTCNN(nn.Module):
 
 
 class CIFAR10CNN(nn.Module):
-    """LeNet-style CIFAR embedding net of the reference (:51-72).  Not on any measured configuration: convolutions stay
-    on torch, the fc chain on the MFMA GEMM."""
+    """LeNet-style CIFAR embedding net of the reference (:51-72): pool2(relu(conv_k(C->6))) pool2(relu(conv_k(6->16))) flatten
+    fc1 ReLU fc2 ReLU fc3.  The convolutional front of the four geometries buildCIFAR10NormalizingFlow constructs is one
+    LDS-resident kernel pair (gnf_hip.ops.LenetConvFn, csrc/gnf_lenetcnn.hip); any other geometry, a CPU tensor, or
+    `fused_front = False` takes the torch convolutions.  The fc chain is on the MFMA GEMM either way."""
 
     def __init__(self, out_d=10, fc_l=[400, 128, 84], size_img=[3, 32, 32], k_size=5):
         super().__init__()
@@ -171,12 +174,24 @@ class CIFAR10CNN(nn.Module):
         self.fc1 = nn.Linear(fc_l[0], fc_l[1])
         self.fc2 = nn.Linear(fc_l[1], fc_l[2])
         self.fc3 = nn.Linear(fc_l[2], out_d)
+        self.fused_front = True          # False: the torch conv / pool chain
+
+    def _fused_front(self, x):
+        c, h, w = self.size_img
+        k = self.conv1.weight.shape[-1]
+        return (self.fused_front and x.is_cuda and x.dtype == torch.float32 and x.shape[-1] == c * h * w
+                and self.conv1.weight.shape == (6, c, k, k) and self.conv2.weight.shape == (16, 6, k, k)
+                and ops.lenet_conv_supported(self.size_img, k))
 
     def forward(self, x, context=None):
         rows = x.shape[0]
-        feat = x.view(-1, *self.size_img)
-        for conv in (self.conv1, self.conv2):
-            feat = self.pool(F.relu(conv(feat)))
+        if self._fused_front(x):
+            feat = ops.lenet_conv(x.reshape(-1, x.shape[-1]), self.conv1.weight, self.conv1.bias, self.conv2.weight,
+                                  self.conv2.bias, self.size_img, self.conv1.weight.shape[-1])
+        else:
+            feat = x.view(-1, *self.size_img)
+            for conv in (self.conv1, self.conv2):
+                feat = self.pool(F.relu(conv(feat)))
         return ops.mlp(feat.reshape(rows, -1), _linears([self.fc1, self.fc2, self.fc3])).view(rows, -1)
 
 

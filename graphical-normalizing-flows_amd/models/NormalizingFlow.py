@@ -388,17 +388,24 @@ class CNNormalizingFlow(FCNormalizingFlow):
         return torch.cat(latents, 1), logdet
 
     def invert(self, z, context=None):
+        """Exact inverse of forward.  Only the flows forward's zip reaches take part (the CIFAR-10 factory builds four
+        flows for three dropping factors), and when the last of them still drops elements, the tail of z is the block
+        forward kept (`latents.append(x)`): the coarse-to-fine pass starts from it.  The reference (:209-226) pairs the
+        reversed lists from their ends -- the wrong flow with each factor when the lengths differ, an IndexError for four
+        and three -- and starts from `0.`, which it then views (divergence table)."""
         batch = z.shape[0]
+        active = min(len(self.steps), len(self.dropping_factors))
+        steps, drops = list(self.steps)[:active], list(self.dropping_factors)[:active]
         # slice z back into the per-scale latent blocks, in emission order
         parts, start = [], 0
-        for flow, drop in zip(self.steps, self.dropping_factors):
+        for flow, drop in zip(steps, drops):
             full = flow.img_sizes[0] * flow.img_sizes[1] * flow.img_sizes[2]
             c, h, w = self._kept_shape(flow.img_sizes, drop)
             width = full - c * h * w if full != c * h * w else full
             parts.append(z[:, start:start + width])
             start += width
-        x = None
-        for flow, drop, zk in zip(reversed(self.steps), reversed(self.dropping_factors), reversed(parts)):
+        x = z[:, start:].contiguous() if start < z.shape[1] else None   # the block the last active scale kept, if any
+        for flow, drop, zk in zip(reversed(steps), reversed(drops), reversed(parts)):
             c, h, w = self._kept_shape(flow.img_sizes, drop)
             if c * h * w != flow.img_sizes[0] * flow.img_sizes[1] * flow.img_sizes[2]:
                 # re-interleave the element kept for the coarser scale with the dropped ones of each block

@@ -1,7 +1,8 @@
 """Flow factories of the reference (models/NormalizingFlowFactories.py), building the MI355X-backed classes.
 
-`NormalLogDensity`, `buildFCNormalizingFlow`, `MNIST_A_prior` and `buildMNISTNormalizingFlow` keep the reference's
-names, arguments and the `state_dict` layout of what they build (`z_log_density.pi`, `steps.N....`)."""
+`NormalLogDensity`, `buildFCNormalizingFlow`, `MNIST_A_prior`, `buildMNISTNormalizingFlow` and
+`buildCIFAR10NormalizingFlow` keep the reference's names, arguments and the `state_dict` layout of what they build
+(`z_log_density.pi`, `steps.N....`)."""
 import math
 
 import torch
@@ -96,4 +97,44 @@ def buildMNISTNormalizingFlow(nb_inner_steps, normalizer_type, normalizer_args, 
             flow.img_sizes = img_size
             scales.append(flow)
         return CNNormalizingFlow(scales, NormalLogDensity(), [drop for _, drop, _ in _MNIST_SCALES])
+    return None
+
+
+# the scales of the CIFAR-10 factory: (image size, CIFAR10CNN fc sizes, kernel size) and the blocks dropped after the
+# first three -- FOUR flows and THREE dropping factors, as in the reference: CNNormalizingFlow.forward zips the two lists,
+# so the fourth flow holds parameters that are never used
+_CIFAR_SCALES = (([3, 32, 32], [400, 128, 84], 5),
+                 ([1, 32, 32], [576, 128, 32], 3),
+                 ([1, 16, 16], [64, 32, 32], 3),
+                 ([1, 8, 8], [16, 32, 32], 2))
+_CIFAR_DROPS = [[3, 1, 1], [1, 2, 2], [1, 2, 2]]
+
+
+def _cifar_dag_steps(n_steps, img_size, fc, k_size, normalizer_type, normalizer_args, l1, nb_epoch_update):
+    """`n_steps` DAG-conditioner steps on one image scale, each with its own CIFAR10CNN embedding net; the normalizer is
+    built from `normalizer_args` alone (a Monotonic caller passes `cond_size` itself, as with the reference)"""
+    pixels = img_size[0] * img_size[1] * img_size[2]
+    emb_size = 2 if normalizer_type is AffineNormalizer else 30
+    out = []
+    for _ in range(n_steps):
+        net = CIFAR10CNN(out_d=emb_size, fc_l=fc, size_img=img_size, k_size=k_size)
+        cond = DAGConditioner(pixels, net, emb_size, l1=l1, nb_epoch_update=nb_epoch_update)
+        out.append(NormalizingFlowStep(cond, normalizer_type(**normalizer_args)))
+    return out
+
+
+def buildCIFAR10NormalizingFlow(nb_inner_steps, normalizer_type, normalizer_args, l1=0., nb_epoch_update=5):
+    """CIFAR-10 DAG flows of the reference (:100-135): `len(nb_inner_steps) == 1` -> one 3x32x32 scale (FCNormalizingFlow),
+    `== 4` -> scales 3x32x32 / 32x32 / 16x16 / 8x8 chained by CNNormalizingFlow, anything else -> None."""
+    common = (normalizer_type, normalizer_args, l1, nb_epoch_update)
+    if len(nb_inner_steps) == 4:
+        scales = []
+        for n_steps, (img_size, fc, k_size) in zip(nb_inner_steps, _CIFAR_SCALES):
+            flow = FCNormalizingFlow(_cifar_dag_steps(n_steps, img_size, fc, k_size, *common), None)
+            flow.img_sizes = img_size
+            scales.append(flow)
+        return CNNormalizingFlow(scales, NormalLogDensity(), [list(d) for d in _CIFAR_DROPS])
+    if len(nb_inner_steps) == 1:
+        img_size, fc, k_size = _CIFAR_SCALES[0]
+        return FCNormalizingFlow(_cifar_dag_steps(nb_inner_steps[0], img_size, fc, k_size, *common), NormalLogDensity())
     return None

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define GNF_ABI_VERSION 10
+#define GNF_ABI_VERSION 11
 #define GNF_EINVAL (-1)   /* bad argument (null pointer, negative size, ...)          */
 #define GNF_ESHAPE (-2)   /* shape not supported by any compiled kernel instantiation */
 #define GNF_EWS    (-3)   /* workspace too small                                      */
@@ -423,6 +423,33 @@ int gnf_mnistcnn_conv_bwd_cols_a1(const float* e, const float* a1saved, const fl
                                   float* ge, const int32_t* plan, int64_t d_plan, float* ge_cols,
                                   float* gW1, float* gb1, float* gW2, float* gb2,
                                   void* ws, int64_t ws_bytes, int64_t n_img, gnf_stream_t stream);
+
+/* ---- CIFAR10CNN convolutional front: models/MLP.py:66-68 as the DAG embedding net ---------
+ * (NormalizingFlowFactories.py:100-135).  feat = flatten(pool2(relu(conv_k(6->16)(pool2(relu(conv_k(C->6)(e)))))))
+ * in torch's (channel, row, column) order, 2 x 2 floor pooling, for the geometries the factory builds:
+ *   (C, H, W, k) = (3,32,32,5), (1,32,32,3), (1,16,16,3), (1,8,8,2)  ->  gnf_lenet_conv_feat = 400, 576, 64, 16;
+ * any other geometry: gnf_lenet_conv_supported = 0 and GNF_ESHAPE from every other call.
+ * e: [n_img, C*H*W] rows of pitch ld_e (elements, >= C*H*W; row offsets are 64-bit); W1 [6,C,k,k], b1 [6], W2 [16,6,k,k],
+ * b2 [16]; feat: [n_img, F] contiguous.  Decisions are torch's: ReLU passes pre-activations > 0, a pool window takes its
+ * FIRST maximum in scan order, always (no exact_ties switch: equal patches give bit-equal sums in this direct form).
+ * argmax2 (may be NULL): [n_img, F] bytes, one per feature: 0..3 = the entry of the second pool's window that carries the
+ * gradient, 4 = none (the pooled value is 0).  n_img == 0: returns 0 without a launch. */
+int gnf_lenet_conv_supported(int C, int H, int W, int k);
+int64_t gnf_lenet_conv_feat(int C, int H, int W, int k);
+int gnf_lenet_conv_fwd(const float* e, int64_t ld_e, int C, int H, int W, int k,
+                       const float* W1, const float* b1, const float* W2, const float* b2,
+                       float* feat, unsigned char* argmax2, int64_t n_img, gnf_stream_t stream);
+/* Backward: g_feat [n_img, F] -> gW1, gb1, gW2, gb2 (written, not accumulated; zeros for n_img == 0) and, when ge is
+ * not NULL, ge [n_img, C*H*W] rows of pitch ld_ge.  conv1 is always recomputed (its pooled activations are an operand of
+ * gW2); the second pool's decisions come from the plane the forward wrote, or are recomputed too when argmax2 is NULL --
+ * the same bits either way.  Per-workgroup partial gradients go through ws (>= gnf_lenet_conv_bwd_ws_bytes) and are summed
+ * in a fixed order: no float atomics, two calls on the same operands return the same bits, with or without ge. */
+int64_t gnf_lenet_conv_bwd_ws_bytes(int C, int H, int W, int k, int64_t n_img);
+int gnf_lenet_conv_bwd(const float* e, int64_t ld_e, int C, int H, int W, int k,
+                       const float* W1, const float* b1, const float* W2, const float* b2,
+                       const unsigned char* argmax2, const float* g_feat,
+                       float* ge, int64_t ld_ge, float* gW1, float* gb1, float* gW2, float* gb2,
+                       void* ws, int64_t ws_bytes, int64_t n_img, gnf_stream_t stream);
 
 /* ---- sparse masked-image front for a DETERMINISTIC DAG gate ---------------
  * Replaces, for evaluation / sampling, the chain  e = x * P[i]  (DAGConditioner.py:142-153, deterministic branches)
