@@ -32,7 +32,13 @@
 // of the dense work -- while the two data gradients (da1, de) gather from the dense maps, bounds checked.  Weight gradients
 // are accumulated in registers over all images of a workgroup, written once per workgroup to the caller's workspace and
 // summed over workgroups in a fixed order by a second kernel: no float atomics, the same bits on every call.
-#include "gnf_common.h"
+//
+// Gated variants (gnf_lenet_gated_*).  As the embedding net of a DAG conditioner the front receives the B*d masked copies
+// e[b*d + i, :] = x[b, :] * gate(b, i, :): at d = 3072 that is 37.7 MB per sample written by the gate kernel, read here, kept
+// for the backward, and the same again for its cotangent.  lenet_gated_fwd_k / lenet_gated_bwd_k build each copy in LDS
+// from x [B, d], the gate's (i, j) table and the noise (the arithmetic of gnf_dag_gate.h, hence the same bits), and the
+// backward multiplies dL/de by de/dp and sums over the samples in registers: neither e nor its cotangent exists in HBM.
+#include "gnf_dag_gate.h"
 
 namespace {
 
@@ -251,15 +257,206 @@ __global__ __launch_bounds__(kThreads, 4) void lenet_fwd_k(const float* __restri
   }
 }
 
+// ------------------------------------------------------------------------------------------- masked copies built in LDS
+// The gate of a DAG conditioner fused into the front: image (b, i) of the batch is the masked copy
+// x[b, :] * gate(b, i, :) (gnf_dag_gate.h), built where stage_inputs would have loaded it.  d = G::IMG.
+struct GatedArgs {
+  const float* x; const float* tab; const float* u1; const float* u2;
+  uint64_t seed, offset; int gate_mode; float T; int64_t B;
+  float* dp; int64_t gpc, nchunk;          // backward: [nchunk, d, d] sums of dL/dP, groups per chunk of samples
+};
+
+// xs[s] = the masked copy (b0 + s, i), zeros for the samples past the end; fs (may be null) = its derivative de/dp.
+// One thread per column quad, as in dag_gate_fwd_k: one Philox call serves four pixels.
+template <class G>
+__device__ __forceinline__ void stage_gated(float* xs, float* fs, const GatedArgs& a, int64_t i, int64_t b0, int tid) {
+  constexpr int64_t d = G::IMG, dd = d * d;
+  constexpr int DQ = G::IMG / 4;
+  static_assert(G::IMG % 4 == 0, "whole column quads");
+  const bool vt = quad_aligned(a.tab, d), vx = quad_aligned(a.x, d);
+  for (int q = tid; q < G::IPB * DQ; q += kThreads) {
+    const int s = q / DQ, jq = q % DQ;
+    const int64_t b = b0 + s;
+    float out[4] = {0.f, 0.f, 0.f, 0.f}, f[4] = {0.f, 0.f, 0.f, 0.f};
+    if (b < a.B) {
+      float p4[4], et4[4] = {0.f, 0.f, 0.f, 0.f}, q4[4] = {0.f, 0.f, 0.f, 0.f}, x4[4];
+      load4(a.tab + i * d + 4 * jq, 4, vt, p4);
+      if (a.gate_mode == 1) load4(a.tab + 2 * dd + i * d + 4 * jq, 4, vt, et4);
+      if (a.gate_mode == 1 && fs) load4(a.tab + 3 * dd + i * d + 4 * jq, 4, vt, q4);
+      const Draw4 n = draw4(a.gate_mode, a.u1, a.u2, a.seed, a.offset, b * d + i, jq, d);
+      load4(a.x + b * d + 4 * jq, 4, vx, x4);
+#pragma unroll
+      for (int h = 0; h < 4; ++h) {
+        out[h] = gate_copy(a.gate_mode, x4[h], p4[h], et4[h], n.v[h], n.w[h], a.T);
+        if (fs) f[h] = gate_dp_add(a.gate_mode, 1.f, x4[h], p4[h], et4[h], q4[h], n.v[h], n.w[h], a.T, 0.f);
+      }
+    }
+    *reinterpret_cast<float4*>(xs + s * G::IMG + 4 * jq) = make_float4(out[0], out[1], out[2], out[3]);
+    if (fs) *reinterpret_cast<float4*>(fs + s * G::IMG + 4 * jq) = make_float4(f[0], f[1], f[2], f[3]);
+  }
+}
+
+// feature rows stay in the order b*d + i; a unit of work is (row i, group of IPB samples)
+template <class G>
+__global__ __launch_bounds__(kThreads, 4) void lenet_gated_fwd_k(GatedArgs a, const float* __restrict__ W1,
+                                                              const float* __restrict__ b1, const float* __restrict__ W2,
+                                                              const float* __restrict__ b2, float* __restrict__ feat,
+                                                              unsigned char* __restrict__ arg2) {
+  __shared__ __attribute__((aligned(16))) float xs[G::IPB * G::IMG];
+  __shared__ float a1s[G::IPB * 6 * G::NP1];
+  const int tid = threadIdx.x;
+  const int64_t ngb = (a.B + G::IPB - 1) / G::IPB;
+  for (int64_t u = blockIdx.x; u < G::IMG * ngb; u += gridDim.x) {
+    const int64_t i = u / ngb, b0 = (u % ngb) * G::IPB;
+    stage_gated<G>(xs, nullptr, a, i, b0, tid);
+    __syncthreads();
+    conv1_phase<G>(xs, a1s, nullptr, W1, b1, tid);
+    __syncthreads();
+    conv2_phase<G>(a1s, W2, b2, tid, [&](int s, int ch, int cell, float m, int code) {
+      if (b0 + s < a.B) {
+        const int64_t im = (b0 + s) * G::IMG + i;
+        feat[im * G::F + ch * G::NP2 + cell] = m;
+        if (arg2) arg2[im * G::F + ch * G::NP2 + cell] = (unsigned char)code;
+      }
+    });
+    __syncthreads();
+  }
+}
+
 // --------------------------------------------------------------------------------------------------------------- backward
-template <class G, bool RECOMPUTE>
-__global__ __launch_bounds__(kThreads, 2) void lenet_bwd_k(const float* __restrict__ e, int64_t ld_e,
-                                                        const float* __restrict__ W1, const float* __restrict__ b1,
-                                                        const float* __restrict__ W2, const float* __restrict__ b2,
-                                                        const unsigned char* __restrict__ arg2,
-                                                        const float* __restrict__ g_feat, float* __restrict__ ge,
-                                                        int64_t ld_ge, float* __restrict__ part, int64_t n) {
-  __shared__ float xs[G::IPB * G::IMG];
+// de[c][Y][X] = sum_{o, ky, kx} dpre1[o][Y - ky][X - kx] W1[o][c][ky][kx] of one image (db = its dense dpre1 maps)
+template <class G>
+__device__ __forceinline__ void de_pixel(const float* db, const float* __restrict__ W1, int Y, int X, float (&acc)[G::C]) {
+#pragma unroll
+  for (int c = 0; c < G::C; ++c) acc[c] = 0.f;
+#pragma unroll 1
+  for (int o = 0; o < 6; ++o) {
+    const float* wo = W1 + o * G::T1;
+    const float* dd = db + o * G::U1 * G::U1;
+    float d[G::K * G::K];
+#pragma unroll
+    for (int ky = 0; ky < G::K; ++ky)
+#pragma unroll
+      for (int kx = 0; kx < G::K; ++kx) {
+        const int yy = Y - ky, xx = X - kx;
+        const bool valid = (unsigned)yy < (unsigned)G::U1 && (unsigned)xx < (unsigned)G::U1;
+        d[ky * G::K + kx] = valid ? dd[valid ? yy * G::U1 + xx : 0] : 0.f;
+      }
+    staged_weights<G::C, G::K * G::K, Stage<G::K>::GS>([&](int c) { return wo + c * G::K * G::K; },
+                                                       [&](int c, const float* w, int& z) {
+#pragma unroll
+                                                         for (int t = 0; t < G::K * G::K; ++t)
+                                                           acc[c] = fmaf(d[t], w[t], acc[c]);
+                                                         tie(z, acc[c]);
+                                                       });
+  }
+}
+
+// Where the images of the backward come from and where dL/de goes.  A source has
+//   for_each_group(f): f(g) for every group of IPB images of this workgroup;   stage(xs, g, tid): the group's images -> xs;
+//   row(g, s): the feature row of image s of group g, -1 past the end;   de_phase(d1, W1, g, tid): consumes dL/de.
+// RowsSrc: rows of e in HBM, dL/de written to ge (when not null).
+template <class G>
+struct RowsSrc {
+  const float* __restrict__ e; int64_t ld_e; float* __restrict__ ge; int64_t ld_ge; int64_t n;
+  template <class F>
+  __device__ __forceinline__ void for_each_group(F f) {
+    for (int64_t i0 = (int64_t)blockIdx.x * G::IPB; i0 < n; i0 += (int64_t)gridDim.x * G::IPB) f(i0);
+  }
+  __device__ __forceinline__ void stage(float* xs, int64_t i0, int tid) { stage_inputs<G>(xs, e, ld_e, i0, n, tid); }
+  __device__ __forceinline__ int64_t row(int64_t i0, int s) const { return i0 + s < n ? i0 + s : -1; }
+  __device__ __forceinline__ void de_phase(const float* d1, const float* __restrict__ W1, int64_t i0, int tid) {
+    if (!ge) return;
+    for (int i = tid; i < G::IPB * G::HW; i += kThreads) {
+      const int s = i / G::HW, r = i % G::HW;
+      float acc[G::C];
+      de_pixel<G>(d1 + s * 6 * G::U1 * G::U1, W1, r / G::W, r % G::W, acc);
+      const int64_t im = i0 + s;
+      if (im < n)
+#pragma unroll
+        for (int c = 0; c < G::C; ++c) ge[im * ld_ge + c * G::HW + r] = acc[c];
+    }
+  }
+};
+
+// GatedSrc: masked copies built in LDS; dL/de is never stored.  A unit of work is (row i of A, chunk of samples) walked
+// in groups of IPB samples of that row; every dL/de[b,i,j] is multiplied by de/dp[b,i,j] (fs, staged with the copy)
+// and summed over the unit's samples in registers, a thread owning the same pixels in every group; the unit writes row i
+// of chunk ch of a.dp.  When HW < 256 the SPI = 256 / HW threads that share a pixel meet through LDS in a fixed order.
+template <class G>
+struct GatedSrc {
+  static constexpr int NPT = G::HW >= kThreads ? G::HW / kThreads : 1;     // pixels of a thread
+  static constexpr int SPI = G::HW >= kThreads ? 1 : kThreads / G::HW;     // samples of one pass over the threads
+  static_assert(G::HW >= kThreads ? G::HW % kThreads == 0
+                                    : (kThreads % G::HW == 0 && G::IPB % SPI == 0 && G::IPB * G::IMG >= kThreads),
+                "pixel ownership");
+  struct Group { int64_t i, b0; };
+  GatedArgs a;
+  float* fs;                                                               // LDS [IPB][IMG]
+  float acc_dp[NPT][G::C];
+
+  template <class F>
+  __device__ __forceinline__ void for_each_group(F f) {
+    const int64_t ngb = (a.B + G::IPB - 1) / G::IPB;
+    for (int64_t u = blockIdx.x; u < G::IMG * a.nchunk; u += gridDim.x) {
+      const int64_t i = u / a.nchunk, ch = u % a.nchunk;
+#pragma unroll
+      for (int t = 0; t < NPT; ++t)
+#pragma unroll
+        for (int c = 0; c < G::C; ++c) acc_dp[t][c] = 0.f;
+      const int64_t g1 = (ch + 1) * a.gpc < ngb ? (ch + 1) * a.gpc : ngb;
+      for (int64_t gb = ch * a.gpc; gb < g1; ++gb) f(Group{i, gb * G::IPB});
+      if (a.dp) flush(a.dp + (ch * G::IMG + i) * G::IMG, threadIdx.x);
+    }
+  }
+  __device__ __forceinline__ void stage(float* xs, Group g, int tid) {
+    stage_gated<G>(xs, a.dp ? fs : nullptr, a, g.i, g.b0, tid);
+  }
+  __device__ __forceinline__ int64_t row(Group g, int s) const {
+    return g.b0 + s < a.B ? (g.b0 + s) * G::IMG + g.i : -1;
+  }
+  __device__ __forceinline__ void de_phase(const float* d1, const float* __restrict__ W1, Group, int tid) {
+    if (!a.dp) return;
+#pragma unroll 1
+    for (int sb = 0; sb < G::IPB; sb += SPI)
+#pragma unroll
+      for (int t = 0; t < NPT; ++t) {
+        const int s = SPI == 1 ? sb : sb + tid / G::HW, r = SPI == 1 ? t * kThreads + tid : tid % G::HW;
+        float acc[G::C];
+        de_pixel<G>(d1 + s * 6 * G::U1 * G::U1, W1, r / G::W, r % G::W, acc);
+#pragma unroll
+        for (int c = 0; c < G::C; ++c) acc_dp[t][c] = fmaf(acc[c], fs[s * G::IMG + c * G::HW + r], acc_dp[t][c]);
+      }
+  }
+  // the unit's sums -> out[d]; called after the barrier that ends the unit's last group, so fs is free
+  __device__ __forceinline__ void flush(float* out, int tid) {
+    if (SPI == 1) {
+#pragma unroll
+      for (int t = 0; t < NPT; ++t)
+#pragma unroll
+        for (int c = 0; c < G::C; ++c) out[c * G::HW + t * kThreads + tid] = acc_dp[t][c];
+    } else {
+#pragma unroll
+      for (int c = 0; c < G::C; ++c) {
+        fs[tid] = acc_dp[0][c];
+        __syncthreads();
+        if (tid < G::HW) {
+          float v = fs[tid];
+#pragma unroll
+          for (int k = 1; k < SPI; ++k) v += fs[tid + k * G::HW];
+          out[c * G::HW + tid] = v;
+        }
+        __syncthreads();
+      }
+    }
+  }
+};
+
+template <class G, bool RECOMPUTE, class Src>
+__device__ __forceinline__ void lenet_bwd_body(Src& src, float* xs, const float* __restrict__ W1,
+                                               const float* __restrict__ b1, const float* __restrict__ W2,
+                                               const float* __restrict__ b2, const unsigned char* __restrict__ arg2,
+                                               const float* __restrict__ g_feat, float* __restrict__ part) {
   __shared__ float a1s[G::IPB * 6 * G::NP1];
   __shared__ float d2[G::IPB * 16 * G::U2 * G::U2];      // dL/d(conv2 pre-activation), dense
   __shared__ float2i l2[G::IPB * G::F];                  // ... as one (value, a1 offset of the entry) per window
@@ -297,8 +494,8 @@ __global__ __launch_bounds__(kThreads, 2) void lenet_bwd_k(const float* __restri
     accW1[j] = accb1[j] = 0.f;
   }
 
-  for (int64_t i0 = (int64_t)blockIdx.x * G::IPB; i0 < n; i0 += (int64_t)gridDim.x * G::IPB) {
-    stage_inputs<G>(xs, e, ld_e, i0, n, tid);
+  src.for_each_group([&](auto grp) {
+    src.stage(xs, grp, tid);
     __syncthreads();
     conv1_phase<G>(xs, a1s, arg1s, W1, b1, tid);
     __syncthreads();
@@ -312,9 +509,9 @@ __global__ __launch_bounds__(kThreads, 2) void lenet_bwd_k(const float* __restri
     for (int i = tid; i < G::IPB * G::F; i += kThreads) {
       const int s = i / G::F, r = i % G::F, ch = r / G::NP2, cell = r % G::NP2;
       const int cy = cell / G::P2, cx = cell % G::P2;
-      const int64_t im = i0 + s;
+      const int64_t im = src.row(grp, s);
       int code = 4;
-      if (im < n) code = RECOMPUTE ? arg2s[i] : arg2[im * G::F + r];
+      if (im >= 0) code = RECOMPUTE ? arg2s[i] : arg2[im * G::F + r];
       const float g = code < 4 ? g_feat[im * G::F + r] : 0.f;
       float* dd = d2 + (s * 16 + ch) * G::U2 * G::U2 + 2 * cy * G::U2 + 2 * cx;
       dd[0] = code == 0 ? g : 0.f;
@@ -390,43 +587,9 @@ __global__ __launch_bounds__(kThreads, 2) void lenet_bwd_k(const float* __restri
           accb1[j] += q.v;
           accW1[j] = fmaf(q.v, xs[s * G::IMG + xbase[j] + q.off], accW1[j]);
         }
-    // de[c][Y][X] = sum_{o, ky, kx} dpre1[o][Y - ky][X - kx] W1[o][c][ky][kx]
-    if (ge) {
-      for (int i = tid; i < G::IPB * G::HW; i += kThreads) {
-        const int s = i / G::HW, r = i % G::HW, Y = r / G::W, X = r % G::W;
-        float acc[G::C];
-#pragma unroll
-        for (int c = 0; c < G::C; ++c) acc[c] = 0.f;
-        const float* db = d1 + s * 6 * G::U1 * G::U1;
-#pragma unroll 1
-        for (int o = 0; o < 6; ++o) {
-          const float* wo = W1 + o * G::T1;
-          const float* dd = db + o * G::U1 * G::U1;
-          float d[G::K * G::K];
-#pragma unroll
-          for (int ky = 0; ky < G::K; ++ky)
-#pragma unroll
-            for (int kx = 0; kx < G::K; ++kx) {
-              const int yy = Y - ky, xx = X - kx;
-              const bool valid = (unsigned)yy < (unsigned)G::U1 && (unsigned)xx < (unsigned)G::U1;
-              d[ky * G::K + kx] = valid ? dd[valid ? yy * G::U1 + xx : 0] : 0.f;
-            }
-          staged_weights<G::C, G::K * G::K, Stage<G::K>::GS>([&](int c) { return wo + c * G::K * G::K; },
-                                                             [&](int c, const float* w, int& z) {
-#pragma unroll
-                                                               for (int t = 0; t < G::K * G::K; ++t)
-                                                                 acc[c] = fmaf(d[t], w[t], acc[c]);
-                                                               tie(z, acc[c]);
-                                                             });
-        }
-        const int64_t im = i0 + s;
-        if (im < n)
-#pragma unroll
-          for (int c = 0; c < G::C; ++c) ge[im * ld_ge + c * G::HW + r] = acc[c];
-      }
-    }
+    src.de_phase(d1, W1, grp, tid);
     __syncthreads();
-  }
+  });
 
   // this workgroup's partial gradients: [dW1 6*T1][db1 6][dW2 16*T2][db2 16]
   float* prow = part + (int64_t)blockIdx.x * G::PW;
@@ -445,6 +608,46 @@ __global__ __launch_bounds__(kThreads, 2) void lenet_bwd_k(const float* __restri
       if (lane + 64 * rr < G::T2) prow[6 * G::T1 + 6 + (wave * 4 + jj) * G::T2 + lane + 64 * rr] = accW2[jj][rr];
     if (lane == 0) prow[6 * G::T1 + 6 + 16 * G::T2 + wave * 4 + jj] = accb2[jj];
   }
+}
+
+template <class G, bool RECOMPUTE>
+__global__ __launch_bounds__(kThreads, 2) void lenet_bwd_k(const float* __restrict__ e, int64_t ld_e,
+                                                        const float* __restrict__ W1, const float* __restrict__ b1,
+                                                        const float* __restrict__ W2, const float* __restrict__ b2,
+                                                        const unsigned char* __restrict__ arg2,
+                                                        const float* __restrict__ g_feat, float* __restrict__ ge,
+                                                        int64_t ld_ge, float* __restrict__ part, int64_t n) {
+  __shared__ float xs[G::IPB * G::IMG];
+  RowsSrc<G> src{e, ld_e, ge, ld_ge, n};
+  lenet_bwd_body<G, RECOMPUTE>(src, xs, W1, b1, W2, b2, arg2, g_feat, part);
+}
+
+template <class G, bool RECOMPUTE>
+__global__ __launch_bounds__(kThreads, 2) void lenet_gated_bwd_k(GatedArgs a, const float* __restrict__ W1,
+                                                              const float* __restrict__ b1, const float* __restrict__ W2,
+                                                              const float* __restrict__ b2,
+                                                              const unsigned char* __restrict__ arg2,
+                                                              const float* __restrict__ g_feat, float* __restrict__ part) {
+  __shared__ __attribute__((aligned(16))) float xs[G::IPB * G::IMG];
+  __shared__ __attribute__((aligned(16))) float fs[G::IPB * G::IMG];
+  GatedSrc<G> src;
+  src.a = a;
+  src.fs = fs;
+  lenet_bwd_body<G, RECOMPUTE>(src, xs, W1, b1, W2, b2, arg2, g_feat, part);
+}
+
+// gA (+)= (sum over the nc chunks of samples, in chunk order) * dP/dA;  nc = 0 (empty batch): zeros, or gA left alone
+__global__ __launch_bounds__(kThreads) void lenet_gated_dA_k(const float* __restrict__ tab, const float* __restrict__ dp,
+                                                             int nc, float* __restrict__ gA, int accumulate, int64_t dd) {
+  const int64_t ij = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (ij >= dd) return;
+  if (nc == 0) {
+    if (!accumulate) gA[ij] = 0.f;
+    return;
+  }
+  float s = dp[ij];
+  for (int c = 1; c < nc; ++c) s += dp[(int64_t)c * dd + ij];
+  gA[ij] = accumulate ? fmaf(s, tab[dd + ij], gA[ij]) : s * tab[dd + ij];
 }
 
 // out[en] = sum over the workgroups' partial rows, four interleaved chains in a fixed order (nb = 0: zeros)
@@ -523,6 +726,70 @@ int bwd_launch(const float* e, int64_t ld_e, const float* W1, const float* b1, c
   return 0;
 }
 
+// chunks of samples of the gated backward: whole groups of IPB samples, enough units (row, chunk) to fill the grid
+template <class G>
+void gated_chunks(int64_t B, int64_t& gpc, int64_t& nchunk) {
+  const int64_t ngb = (B + G::IPB - 1) / G::IPB;
+  nchunk = (kBwdGridMax + G::IMG - 1) / G::IMG;
+  if (nchunk > ngb) nchunk = ngb;
+  gpc = nchunk > 0 ? (ngb + nchunk - 1) / nchunk : 1;
+  nchunk = (ngb + gpc - 1) / gpc;
+}
+
+template <class G>
+int gated_bwd_grid(int64_t B) {
+  int64_t gpc, nchunk;
+  gated_chunks<G>(B, gpc, nchunk);
+  const int64_t units = G::IMG * nchunk;
+  return (int)(units < kBwdGridMax ? units : kBwdGridMax);
+}
+
+// partial weight gradients [grid][PW] | sums of dL/dP [nchunk][d][d]
+template <class G>
+int64_t gated_ws_bytes_of(int64_t B) {
+  int64_t gpc, nchunk;
+  gated_chunks<G>(B, gpc, nchunk);
+  const int64_t nb = B > 0 ? gated_bwd_grid<G>(B) : 1;
+  return (nb * G::PW + nchunk * G::IMG * G::IMG) * (int64_t)sizeof(float);
+}
+
+template <class G>
+int gated_fwd_launch(const GatedArgs& a, const float* W1, const float* b1, const float* W2, const float* b2, float* feat,
+                     unsigned char* arg2, hipStream_t s) {
+  const int64_t units = G::IMG * ((a.B + G::IPB - 1) / G::IPB);
+  hipLaunchKernelGGL(lenet_gated_fwd_k<G>, dim3((unsigned)(units < kFwdGridMax ? units : kFwdGridMax)), dim3(kThreads), 0, s,
+                     a, W1, b1, W2, b2, feat, arg2);
+  GNF_LAUNCH_CHECK();
+  return 0;
+}
+
+template <class G>
+int gated_bwd_launch(GatedArgs a, const float* W1, const float* b1, const float* W2, const float* b2,
+                     const unsigned char* arg2, const float* g_feat, float* gA, int accumulate, float* gW1, float* gb1,
+                     float* gW2, float* gb2, float* ws, hipStream_t s) {
+  const int nb = a.B > 0 ? gated_bwd_grid<G>(a.B) : 0;
+  gated_chunks<G>(a.B, a.gpc, a.nchunk);
+  float* dp = ws + (int64_t)(nb > 0 ? nb : 1) * G::PW;
+  a.dp = gA ? dp : nullptr;
+  if (nb > 0) {
+    if (arg2)
+      hipLaunchKernelGGL((lenet_gated_bwd_k<G, false>), dim3(nb), dim3(kThreads), 0, s, a, W1, b1, W2, b2, arg2, g_feat, ws);
+    else
+      hipLaunchKernelGGL((lenet_gated_bwd_k<G, true>), dim3(nb), dim3(kThreads), 0, s, a, W1, b1, W2, b2, arg2, g_feat, ws);
+    GNF_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(lenet_reduce_k, dim3((G::PW + kThreads - 1) / kThreads), dim3(kThreads), 0, s, ws, nb, G::PW,
+                     6 * G::T1, 16 * G::T2, gW1, gb1, gW2, gb2);
+  GNF_LAUNCH_CHECK();
+  if (gA) {
+    const int64_t dd = (int64_t)G::IMG * G::IMG;
+    hipLaunchKernelGGL(lenet_gated_dA_k, dim3((unsigned)((dd + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a.tab, dp,
+                       (int)a.nchunk, gA, accumulate, dd);
+    GNF_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
 template <class G>
 int64_t ws_bytes_of(int64_t n) {
   const int64_t nb = n > 0 ? grid_of<G>(n, kBwdGridMax) : 1;
@@ -592,6 +859,73 @@ int gnf_lenet_conv_bwd(const float* e, int64_t ld_e, int C, int H, int W, int k,
     case 1: return bwd_launch<G1>(e, ld_e, W1, b1, W2, b2, argmax2, g_feat, ge, ld_ge, gW1, gb1, gW2, gb2, part, n_img, s);
     case 2: return bwd_launch<G2>(e, ld_e, W1, b1, W2, b2, argmax2, g_feat, ge, ld_ge, gW1, gb1, gW2, gb2, part, n_img, s);
     default: return bwd_launch<G3>(e, ld_e, W1, b1, W2, b2, argmax2, g_feat, ge, ld_ge, gW1, gb1, gW2, gb2, part, n_img, s);
+  }
+}
+
+int gnf_lenet_gated_fwd(const float* x, const float* A, float* tab, int C, int H, int W, int k, int imp_mode, int gate_mode,
+                        float h_thresh, float temperature, const float* u1, const float* u2, uint64_t seed,
+                        uint64_t offset, const float* W1, const float* b1, const float* W2, const float* b2, float* feat,
+                        unsigned char* argmax2, int64_t B, gnf_stream_t stream) {
+  const int gi = geo_index(C, H, W, k);
+  if (gi < 0) return GNF_ESHAPE;
+  if (B < 0 || !A || !tab || !W1 || !b1 || !W2 || !b2 || ((!x || !feat) && B > 0) || imp_mode < 0 || imp_mode > 3 ||
+      gate_mode < 0 || gate_mode > 2 || (gate_mode == 1 && u1 && !u2))
+    return GNF_EINVAL;
+  if (bad_f32(x) || bad_f32(A) || bad_f32(tab) || bad_f32(u1) || bad_f32(u2) || bad_f32(W1) || bad_f32(b1) || bad_f32(W2) ||
+      bad_f32(b2) || bad_f32(feat))
+    return GNF_EINVAL;
+  if (B == 0) return 0;
+  if (imp_mode == 0) gate_mode = 0;   // DAG:151-153: raw A, no gate
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = launch_tab(A, tab, imp_mode, h_thresh, temperature, (int64_t)C * H * W, s);
+  if (rc) return rc;
+  GatedArgs a{};
+  a.x = x; a.tab = tab; a.u1 = u1; a.u2 = u2; a.seed = seed; a.offset = offset; a.gate_mode = gate_mode; a.T = temperature;
+  a.B = B;
+  switch (gi) {
+    case 0: return gated_fwd_launch<G0>(a, W1, b1, W2, b2, feat, argmax2, s);
+    case 1: return gated_fwd_launch<G1>(a, W1, b1, W2, b2, feat, argmax2, s);
+    case 2: return gated_fwd_launch<G2>(a, W1, b1, W2, b2, feat, argmax2, s);
+    default: return gated_fwd_launch<G3>(a, W1, b1, W2, b2, feat, argmax2, s);
+  }
+}
+
+int64_t gnf_lenet_gated_bwd_ws_bytes(int C, int H, int W, int k, int64_t B) {
+  if (B < 0) return GNF_EINVAL;
+  switch (geo_index(C, H, W, k)) {
+    case 0: return gated_ws_bytes_of<G0>(B);
+    case 1: return gated_ws_bytes_of<G1>(B);
+    case 2: return gated_ws_bytes_of<G2>(B);
+    case 3: return gated_ws_bytes_of<G3>(B);
+  }
+  return GNF_ESHAPE;
+}
+
+int gnf_lenet_gated_bwd(const float* x, const float* tab, int C, int H, int W, int k, int imp_mode, int gate_mode,
+                        float temperature, const float* u1, const float* u2, uint64_t seed, uint64_t offset,
+                        const float* W1, const float* b1, const float* W2, const float* b2, const unsigned char* argmax2,
+                        const float* g_feat, float* gA, int accumulate, float* gW1, float* gb1, float* gW2, float* gb2,
+                        void* ws, int64_t ws_bytes, int64_t B, gnf_stream_t stream) {
+  const int gi = geo_index(C, H, W, k);
+  if (gi < 0) return GNF_ESHAPE;
+  if (B < 0 || !W1 || !b1 || !W2 || !b2 || !gW1 || !gb1 || !gW2 || !gb2 || !ws || ((!x || !tab || !g_feat) && B > 0) ||
+      imp_mode < 0 || imp_mode > 3 || gate_mode < 0 || gate_mode > 2 || (gate_mode == 1 && u1 && !u2))
+    return GNF_EINVAL;
+  if (bad_f32(x) || bad_f32(tab) || bad_f32(u1) || bad_f32(u2) || bad_f32(W1) || bad_f32(b1) || bad_f32(W2) || bad_f32(b2) ||
+      bad_f32(g_feat) || bad_f32(gA) || bad_f32(gW1) || bad_f32(gb1) || bad_f32(gW2) || bad_f32(gb2) || bad_f32(ws))
+    return GNF_EINVAL;
+  if (ws_bytes < gnf_lenet_gated_bwd_ws_bytes(C, H, W, k, B)) return GNF_EWS;
+  if (imp_mode == 0) gate_mode = 0;
+  hipStream_t s = (hipStream_t)stream;
+  GatedArgs a{};
+  a.x = x; a.tab = tab; a.u1 = u1; a.u2 = u2; a.seed = seed; a.offset = offset; a.gate_mode = gate_mode; a.T = temperature;
+  a.B = B;
+  float* w = static_cast<float*>(ws);
+  switch (gi) {
+    case 0: return gated_bwd_launch<G0>(a, W1, b1, W2, b2, argmax2, g_feat, gA, accumulate, gW1, gb1, gW2, gb2, w, s);
+    case 1: return gated_bwd_launch<G1>(a, W1, b1, W2, b2, argmax2, g_feat, gA, accumulate, gW1, gb1, gW2, gb2, w, s);
+    case 2: return gated_bwd_launch<G2>(a, W1, b1, W2, b2, argmax2, g_feat, gA, accumulate, gW1, gb1, gW2, gb2, w, s);
+    default: return gated_bwd_launch<G3>(a, W1, b1, W2, b2, argmax2, g_feat, gA, accumulate, gW1, gb1, gW2, gb2, w, s);
   }
 }
 

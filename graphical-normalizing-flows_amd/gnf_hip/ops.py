@@ -909,6 +909,69 @@ def dag_conv_front(x, A, imp_mode, gate_mode, h_thresh, temperature, u1, u2, see
                                 exact_ties, torch.is_grad_enabled())
 
 
+class DagLenetFrontFn(torch.autograd.Function):
+    """LenetConvFn on the masked copies e[b*d+i, :] = x[b, :] * gate(importance(A[i, :])) as ONE autograd node whose kernels
+    build each copy in LDS (csrc/gnf_lenetcnn.hip, gnf_lenet_gated_*): no [B*d, d] tensor is allocated, forward or
+    backward -- at d = 3072 e and its cotangent are 37.7 MB per sample each.  The features are bit-identical to
+    DagGateFn + LenetConvFn with the same (seed, offset).  Differentiable w.r.t. A and the conv parameters, not x
+    (dag_lenet_front composes the two nodes for that)."""
+
+    @staticmethod
+    def forward(ctx, x, A, imp_mode, gate_mode, h_thresh, temperature, u1, u2, seed, offset, W1, b1, W2, b2, size_img, k,
+                grad_mode):
+        c, h, w = (int(v) for v in size_img)
+        k = int(k)
+        x, A = x.contiguous(), A.contiguous()
+        B, d = x.shape
+        if d != c * h * w or tuple(A.shape) != (d, d):
+            raise abi.GnfError("the fused masked-image front needs x [B, %d] and A [%d, %d]" % (c * h * w, d, d))
+        u1 = u1.contiguous() if u1 is not None else None
+        u2 = u2.contiguous() if u2 is not None else None
+        lib = abi.load()
+        W1c, b1c, W2c, b2c = W1.contiguous(), b1.contiguous(), W2.contiguous(), b2.contiguous()
+        F = int(lib.gnf_lenet_conv_feat(c, h, w, k))
+        if F < 0:
+            abi.check(F, "gnf_lenet_conv_feat")
+        tab = torch.empty(max(int(lib.gnf_dag_gate_fwd_ws_bytes(d)) // 4, 1), dtype=torch.float32, device=x.device)
+        feat = _empty((B * d, F), x)
+        keep = bool(grad_mode) and any(ctx.needs_input_grad) and os.environ.get("GNF_LENET_SAVE_ARGMAX", "1") != "0"
+        arg = torch.empty((B * d, F), dtype=torch.uint8, device=x.device) if keep else None
+        call("gnf_lenet_gated_fwd", ptr(x), ptr(A), ptr(tab), c, h, w, k, imp_mode, gate_mode, float(h_thresh),
+             float(temperature), ptr(u1), ptr(u2), seed, offset, ptr(W1c), ptr(b1c), ptr(W2c), ptr(b2c), ptr(feat),
+             abi.rawptr(arg) if keep else None, B, stream())
+        ctx.save_for_backward(x, A, u1, u2, tab, W1c, b1c, W2c, b2c)
+        ctx.arg, ctx.geo = arg, (c, h, w, k)
+        ctx.cfg = (imp_mode, gate_mode, float(temperature), seed, offset)
+        return feat
+
+    @staticmethod
+    def backward(ctx, gf):
+        x, A, u1, u2, tab, W1, b1, W2, b2 = ctx.saved_tensors
+        c, h, w, k = ctx.geo
+        imp_mode, gate_mode, temperature, seed, offset = ctx.cfg
+        B = x.shape[0]
+        gf = gf.contiguous()
+        gA, finish_A, acc = grad_out_shared(A, accumulate_ok=True) if ctx.needs_input_grad[1] else (None, None, False)
+        outs = [grad_out_shared(p) for p in (W1, b1, W2, b2)]
+        nws = abi.load().gnf_lenet_gated_bwd_ws_bytes(c, h, w, k, B)
+        ws = _ws(nws, x)
+        call("gnf_lenet_gated_bwd", ptr(x), ptr(tab), c, h, w, k, imp_mode, gate_mode, temperature, ptr(u1), ptr(u2), seed,
+             offset, ptr(W1), ptr(b1), ptr(W2), ptr(b2), abi.rawptr(ctx.arg) if ctx.arg is not None else None, ptr(gf),
+             ptr(gA), int(acc), *(ptr(t) for t, _, _ in outs), abi.rawptr(ws), nws, B, stream())
+        return (None, (finish_A(gA) if gA is not None else None), None, None, None, None, None, None, None, None,
+                *(finish(t) for t, finish, _ in outs), None, None, None)
+
+
+def dag_lenet_front(x, A, imp_mode, gate_mode, h_thresh, temperature, u1, u2, seed, offset, W1, b1, W2, b2, size_img, k):
+    """features [B*d, F] of the CIFAR10CNN front on the masked copies of x.  A gradient for x needs a sum over the rows i
+    across workgroups, and stacked steps are rare in the CIFAR factory: that case runs the two existing nodes."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        e = DagGateFn.apply(x, A, imp_mode, gate_mode, h_thresh, temperature, False, u1, u2, seed, offset)
+        return lenet_conv(e, W1, b1, W2, b2, size_img, k)
+    return DagLenetFrontFn.apply(x, A, imp_mode, gate_mode, h_thresh, temperature, u1, u2, seed, offset, W1, b1, W2, b2,
+                                 size_img, k, torch.is_grad_enabled())
+
+
 # ----------------------------------------------------------------------------- Monotonic (UMNN) normalizer
 _CC = {}
 

@@ -159,11 +159,17 @@ class MNISTCNN(nn.Module):
         return ops.mlp(feat, _linears([self.fc1, self.fc2])).view(rows, -1)
 
 
+# CIFAR10CNN.gated_front of a new net; the measurement behind the value: profiles/lenet_gated_ab.txt
+GATED_FRONT_DEFAULT = False
+
+
 class CIFAR10CNN(nn.Module):
     """LeNet-style CIFAR embedding net of the reference (:51-72): pool2(relu(conv_k(C->6))) pool2(relu(conv_k(6->16))) flatten
     fc1 ReLU fc2 ReLU fc3.  The convolutional front of the four geometries buildCIFAR10NormalizingFlow constructs is one
     LDS-resident kernel pair (gnf_hip.ops.LenetConvFn, csrc/gnf_lenetcnn.hip); any other geometry, a CPU tensor, or
-    `fused_front = False` takes the torch convolutions.  The fc chain is on the MFMA GEMM either way."""
+    `fused_front = False` takes the torch convolutions.  The fc chain is on the MFMA GEMM either way.  `gated_front = True`
+    lets a DAG conditioner hand over x, A and its gate instead of the B*d masked copies: the same kernels build each copy in
+    LDS (gnf_hip.ops.DagLenetFrontFn), the same features bit for bit, a third of the peak memory, no faster."""
 
     def __init__(self, out_d=10, fc_l=[400, 128, 84], size_img=[3, 32, 32], k_size=5):
         super().__init__()
@@ -175,6 +181,7 @@ class CIFAR10CNN(nn.Module):
         self.fc2 = nn.Linear(fc_l[1], fc_l[2])
         self.fc3 = nn.Linear(fc_l[2], out_d)
         self.fused_front = True          # False: the torch conv / pool chain
+        self.gated_front = GATED_FRONT_DEFAULT   # the gate of a DAG conditioner fused into the front (supports_gated)
 
     def _fused_front(self, x):
         c, h, w = self.size_img
@@ -182,6 +189,19 @@ class CIFAR10CNN(nn.Module):
         return (self.fused_front and x.is_cuda and x.dtype == torch.float32 and x.shape[-1] == c * h * w
                 and self.conv1.weight.shape == (6, c, k, k) and self.conv2.weight.shape == (16, 6, k, k)
                 and ops.lenet_conv_supported(self.size_img, k))
+
+    def supports_gated(self, x):
+        """the gate of a DAG conditioner + this net's conv front as one autograd node (gnf_hip.ops.DagLenetFrontFn): a
+        [B, C*H*W] batch on the fused kernels, one masked copy per variable, built in LDS"""
+        return bool(self.gated_front) and x.dim() == 2 and self._fused_front(x)
+
+    def forward_gated(self, x, A, imp_mode, gate_mode, h_thresh, temperature, u1, u2, seed, offset):
+        """embedding_net(e) for e[b*d+i] = x[b] * gate(importance(A[i])) (DAGConditioner.py:94-166,169) without e in memory:
+        [B*d, out_d]"""
+        feat = ops.dag_lenet_front(x, A, imp_mode, gate_mode, h_thresh, temperature, u1, u2, seed, offset,
+                                   self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias, self.size_img,
+                                   self.conv1.weight.shape[-1])
+        return ops.mlp(feat, _linears([self.fc1, self.fc2, self.fc3]))
 
     def forward(self, x, context=None):
         rows = x.shape[0]

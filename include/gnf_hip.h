@@ -38,6 +38,8 @@
 extern "C" {
 #endif
 
+/* 11 still: gnf_lenet_gated_* were ADDED under this number (no existing symbol changed; a binding written against the
+ * earlier 11 keeps working, and tests/test_cifar_factory.py pins the value) */
 #define GNF_ABI_VERSION 11
 #define GNF_EINVAL (-1)   /* bad argument (null pointer, negative size, ...)          */
 #define GNF_ESHAPE (-2)   /* shape not supported by any compiled kernel instantiation */
@@ -450,6 +452,35 @@ int gnf_lenet_conv_bwd(const float* e, int64_t ld_e, int C, int H, int W, int k,
                        const unsigned char* argmax2, const float* g_feat,
                        float* ge, int64_t ld_ge, float* gW1, float* gb1, float* gW2, float* gb2,
                        void* ws, int64_t ws_bytes, int64_t n_img, gnf_stream_t stream);
+
+/* ---- the same front with the DAG gate fused in: the masked copies are built in LDS ---------------
+ * For a DAG conditioner whose embedding net is this front (d = C*H*W, one masked copy per variable) the images are
+ *   e[b*d + i, :] = x[b, :] * gate(b, i, :)          exactly the values gnf_dag_gate_fwd writes (hot = 0),
+ * and these entry points build them inside the kernels from x [B, d] (contiguous), the gate's (i, j) table and the noise:
+ * neither e nor its cotangent ever exists in memory.  imp_mode, gate_mode, h_thresh, temperature, u1, u2 ([B*d, d] injected
+ * uniforms, or NULL for Philox with (seed, offset) and counter (b*d + i) * ceil(d/4) + j/4) are those of gnf_dag_gate_fwd.
+ * tab: caller-owned, gnf_dag_gate_fwd_ws_bytes(d) bytes; the forward fills it from A (the gate kernels' table), the
+ * backward reads it, so the caller keeps it between the two.  feat [B*d, F] and argmax2 (may be NULL) as for
+ * gnf_lenet_conv_fwd, rows in the order b*d + i (64-bit row offsets).  Same return codes and the same refusal of
+ * pointers below dword alignment as gnf_lenet_conv_*; B == 0: returns 0 without a launch. */
+int gnf_lenet_gated_fwd(const float* x, const float* A, float* tab, int C, int H, int W, int k,
+                        int imp_mode, int gate_mode, float h_thresh, float temperature,
+                        const float* u1, const float* u2, uint64_t seed, uint64_t offset,
+                        const float* W1, const float* b1, const float* W2, const float* b2,
+                        float* feat, unsigned char* argmax2, int64_t B, gnf_stream_t stream);
+/* Backward: g_feat [B*d, F] -> gW1, gb1, gW2, gb2 (written; zeros for B == 0) and, when gA is not NULL, the gate's
+ * gradient gA [d, d] = dP/dA * sum_b dL/de[b,i,j] * de/dp[b,i,j] (accumulate != 0: added to what gA holds; B == 0 then
+ * leaves it alone).  There is no gradient for x: a caller that needs one composes gnf_dag_gate_* with gnf_lenet_conv_*.
+ * The sums over the samples are taken per (row i, chunk of samples) in registers, written to ws and added in chunk
+ * order: no float atomics, the same bits on every call.  argmax2 NULL: conv2 is recomputed, the same bits. */
+int64_t gnf_lenet_gated_bwd_ws_bytes(int C, int H, int W, int k, int64_t B);
+int gnf_lenet_gated_bwd(const float* x, const float* tab, int C, int H, int W, int k,
+                        int imp_mode, int gate_mode, float temperature,
+                        const float* u1, const float* u2, uint64_t seed, uint64_t offset,
+                        const float* W1, const float* b1, const float* W2, const float* b2,
+                        const unsigned char* argmax2, const float* g_feat,
+                        float* gA, int accumulate, float* gW1, float* gb1, float* gW2, float* gb2,
+                        void* ws, int64_t ws_bytes, int64_t B, gnf_stream_t stream);
 
 /* ---- sparse masked-image front for a DETERMINISTIC DAG gate ---------------
  * Replaces, for evaluation / sampling, the chain  e = x * P[i]  (DAGConditioner.py:142-153, deterministic branches)
