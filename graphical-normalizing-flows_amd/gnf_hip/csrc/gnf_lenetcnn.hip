@@ -38,6 +38,8 @@
 // for the backward, and the same again for its cotangent.  lenet_gated_fwd_k / lenet_gated_bwd_k build each copy in LDS
 // from x [B, d], the gate's (i, j) table and the noise (the arithmetic of gnf_dag_gate.h, hence the same bits), and the
 // backward multiplies dL/de by de/dp and sums over the samples in registers: neither e nor its cotangent exists in HBM.
+// lenet_rows_fwd_k is the no-grad sibling for a deterministic gate: the rows i of a level of the inversion (or all d of them)
+// as x[b, :] * P[i, :], the [B, R, d] broadcast product of DAGConditioner.forward_rows built in LDS.
 #include "gnf_dag_gate.h"
 
 namespace {
@@ -317,6 +319,63 @@ __global__ __launch_bounds__(kThreads, 4) void lenet_gated_fwd_k(GatedArgs a, co
         const int64_t im = (b0 + s) * G::IMG + i;
         feat[im * G::F + ch * G::NP2 + cell] = m;
         if (arg2) arg2[im * G::F + ch * G::NP2 + cell] = (unsigned char)code;
+      }
+    });
+    __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------------- a subset of the deterministic gate's rows
+// Inversion and deterministic evaluation ask for the rows i of an importance matrix P [d, d] (pitch ld_p): image (b, r) is
+// x[b, :] * P[i, :], i = rows ? rows[r] : r -- the [B, R, d] tensor torch would broadcast, built in LDS instead.
+// xs[s] = that copy of sample b0 + s, zeros for the samples past the end.  One thread per column quad, as stage_gated.
+template <class G>
+__device__ __forceinline__ void stage_rows(float* xs, const float* __restrict__ x, const float* __restrict__ P, int64_t ld_p,
+                                           int64_t i, int64_t b0, int64_t B, int tid) {
+  constexpr int64_t d = G::IMG;
+  constexpr int DQ = G::IMG / 4;
+  static_assert(G::IMG % 4 == 0, "whole column quads");
+  const bool vp = quad_aligned(P, ld_p), vx = quad_aligned(x, d);
+  for (int q = tid; q < G::IPB * DQ; q += kThreads) {
+    const int s = q / DQ, jq = q % DQ;
+    const int64_t b = b0 + s;
+    float out[4] = {0.f, 0.f, 0.f, 0.f};
+    if (b < B) {
+      float p4[4], x4[4];
+      load4(P + i * ld_p + 4 * jq, 4, vp, p4);
+      load4(x + b * d + 4 * jq, 4, vx, x4);
+#pragma unroll
+      for (int h = 0; h < 4; ++h) out[h] = gate_copy(0, x4[h], p4[h], 0.f, 0.f, 1.f, 1.f);   // one fp32 product
+    }
+    *reinterpret_cast<float4*>(xs + s * G::IMG + 4 * jq) = make_float4(out[0], out[1], out[2], out[3]);
+  }
+}
+
+// a unit of work is (row slot r, group of IPB samples), r-major: consecutive units reuse one row of P.  Feature row of
+// (b, r): b*R + r, or r*B + b when variable_major
+template <class G>
+__global__ __launch_bounds__(kThreads, 4) void lenet_rows_fwd_k(const float* __restrict__ x, const float* __restrict__ P,
+                                                             int64_t ld_p, const int32_t* __restrict__ rows, int64_t R,
+                                                             int64_t B, const float* __restrict__ W1,
+                                                             const float* __restrict__ b1, const float* __restrict__ W2,
+                                                             const float* __restrict__ b2, float* __restrict__ feat,
+                                                             int variable_major) {
+  __shared__ __attribute__((aligned(16))) float xs[G::IPB * G::IMG];
+  __shared__ float a1s[G::IPB * 6 * G::NP1];
+  const int tid = threadIdx.x;
+  const int64_t ngb = (B + G::IPB - 1) / G::IPB;
+  for (int64_t u = blockIdx.x; u < R * ngb; u += gridDim.x) {
+    const int64_t r = u / ngb, b0 = (u % ngb) * G::IPB;
+    const int64_t i = rows ? (int64_t)rows[r] : r;
+    stage_rows<G>(xs, x, P, ld_p, i, b0, B, tid);
+    __syncthreads();
+    conv1_phase<G>(xs, a1s, nullptr, W1, b1, tid);
+    __syncthreads();
+    conv2_phase<G>(a1s, W2, b2, tid, [&](int s, int ch, int cell, float m, int) {
+      const int64_t b = b0 + s;
+      if (b < B) {
+        const int64_t im = variable_major ? r * B + b : b * R + r;
+        feat[im * G::F + ch * G::NP2 + cell] = m;
       }
     });
     __syncthreads();
@@ -764,6 +823,19 @@ int gated_fwd_launch(const GatedArgs& a, const float* W1, const float* b1, const
 }
 
 template <class G>
+int rows_fwd_launch(const float* x, const float* P, int64_t ld_p, const int32_t* rows, int64_t R, const float* W1,
+                    const float* b1, const float* W2, const float* b2, float* feat, int variable_major, int64_t B,
+                    hipStream_t s) {
+  if (ld_p < G::IMG || (!rows && R > G::IMG)) return GNF_EINVAL;
+  if (B == 0 || R == 0) return 0;
+  const int64_t units = R * ((B + G::IPB - 1) / G::IPB);
+  hipLaunchKernelGGL(lenet_rows_fwd_k<G>, dim3((unsigned)(units < kFwdGridMax ? units : kFwdGridMax)), dim3(kThreads), 0, s,
+                     x, P, ld_p, rows, R, B, W1, b1, W2, b2, feat, variable_major);
+  GNF_LAUNCH_CHECK();
+  return 0;
+}
+
+template <class G>
 int gated_bwd_launch(GatedArgs a, const float* W1, const float* b1, const float* W2, const float* b2,
                      const unsigned char* arg2, const float* g_feat, float* gA, int accumulate, float* gW1, float* gb1,
                      float* gW2, float* gb2, float* ws, hipStream_t s) {
@@ -887,6 +959,23 @@ int gnf_lenet_gated_fwd(const float* x, const float* A, float* tab, int C, int H
     case 1: return gated_fwd_launch<G1>(a, W1, b1, W2, b2, feat, argmax2, s);
     case 2: return gated_fwd_launch<G2>(a, W1, b1, W2, b2, feat, argmax2, s);
     default: return gated_fwd_launch<G3>(a, W1, b1, W2, b2, feat, argmax2, s);
+  }
+}
+
+int gnf_lenet_rows_fwd(const float* x, const float* P, int64_t ld_p, const int32_t* rows, int64_t R, int C, int H, int W,
+                       int k, const float* W1, const float* b1, const float* W2, const float* b2, float* feat,
+                       int variable_major, int64_t B, gnf_stream_t stream) {
+  const int gi = geo_index(C, H, W, k);
+  if (gi < 0) return GNF_ESHAPE;
+  if (B < 0 || R < 0 || !P || !W1 || !b1 || !W2 || !b2 || ((!x || !feat) && B > 0 && R > 0)) return GNF_EINVAL;
+  if (bad_f32(x) || bad_f32(P) || bad_f32(rows) || bad_f32(W1) || bad_f32(b1) || bad_f32(W2) || bad_f32(b2) || bad_f32(feat))
+    return GNF_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  switch (gi) {
+    case 0: return rows_fwd_launch<G0>(x, P, ld_p, rows, R, W1, b1, W2, b2, feat, variable_major, B, s);
+    case 1: return rows_fwd_launch<G1>(x, P, ld_p, rows, R, W1, b1, W2, b2, feat, variable_major, B, s);
+    case 2: return rows_fwd_launch<G2>(x, P, ld_p, rows, R, W1, b1, W2, b2, feat, variable_major, B, s);
+    default: return rows_fwd_launch<G3>(x, P, ld_p, rows, R, W1, b1, W2, b2, feat, variable_major, B, s);
   }
 }
 

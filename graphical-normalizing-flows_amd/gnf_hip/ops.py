@@ -610,6 +610,38 @@ def lenet_conv(e, W1, b1, W2, b2, size_img, k):
     return LenetConvFn.apply(e, W1, b1, W2, b2, size_img, k, torch.is_grad_enabled())
 
 
+def lenet_rows(x, P, rows32, W1, b1, W2, b2, size_img, k, variable_major=False):
+    """Features of the CIFAR10CNN front on the masked copies x[b] * P[rows32[r]] of a deterministic gate (rows32: int32
+    device indices, None = all d rows in order): [B, R, F], or [R, B, F] when variable_major.  The copies are built in LDS
+    (csrc/gnf_lenetcnn.hip, gnf_lenet_rows_fwd): the [B, R, d] tensor of the broadcast product never exists.  The bits of
+    lenet_conv on that product.  Evaluation only: a plain function, no autograd node."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, P, W1, b1, W2, b2)):
+        raise abi.GnfError("lenet_rows has no backward: call it under torch.no_grad() or on operands without requires_grad")
+    c, h, w = (int(v) for v in size_img)
+    k = int(k)
+    x = x.contiguous()
+    B, d = x.shape
+    if d != c * h * w or tuple(P.shape) != (d, d):
+        raise abi.GnfError("the row-subset front needs x [B, %d] and P [%d, %d]" % (c * h * w, d, d))
+    if P.stride(1) != 1 or P.stride(0) < d:
+        P = P.contiguous()
+    if rows32 is None:
+        R = d
+    else:
+        if rows32.dtype != torch.int32 or rows32.device != x.device:
+            raise abi.GnfError("lenet_rows: rows32 must be an int32 tensor on the device of x")
+        rows32 = rows32.contiguous()
+        R = rows32.numel()
+    F = int(abi.load().gnf_lenet_conv_feat(c, h, w, k))
+    if F < 0:
+        abi.check(F, "gnf_lenet_conv_feat")
+    feat = _empty((R, B, F) if variable_major else (B, R, F), x)
+    call("gnf_lenet_rows_fwd", ptr(x), ptr(P), P.stride(0), abi.rawptr(rows32) if rows32 is not None else None, R, c, h, w, k,
+         ptr(W1.contiguous()), ptr(b1.contiguous()), ptr(W2.contiguous()), ptr(b2.contiguous()), ptr(feat),
+         int(bool(variable_major)), B, stream())
+    return feat
+
+
 def crop_origin(p):
     """cell origin of the 5x5 pooled block that can deviate from the background for a pixel row / column p"""
     return min(max((p - 6) >> 1, 0), 7)

@@ -198,6 +198,13 @@ class DAGConditioner(Conditioner):
             self._sparse_plans[plan_key] = ops.SparseRows(rows, x.shape[0], x.device)
         return self._sparse_plans[plan_key]
 
+    def _rows_front(self, x):
+        """True when the embedding net builds the masked copies x * P[i] of a deterministic gate itself
+        (CIFAR10CNN.forward_rows): evaluation only, plain [B, d] inputs"""
+        net = self.embedding_net
+        return (not torch.is_grad_enabled() and not self.hot_encoding and not self.cond_in
+                and hasattr(net, "supports_rows") and x.dim() == 2 and x.shape[1] == self.in_size and net.supports_rows(x))
+
     def forward(self, x, context=None):
         no_context(context, self.cond_in)
         P = self.deterministic_importance()
@@ -205,6 +212,8 @@ class DAGConditioner(Conditioner):
             plan = self._sparse_plan(x, None, P)
             if plan is not None:
                 return self.embedding_net.sparse_rows(x, P, plan)
+            if self._rows_front(x):
+                return self.embedding_net.forward_rows(x, P, None, False)      # all d rows, neither e nor a gate table
         if hasattr(self.embedding_net, "exact_pool_ties"):
             # deterministic gate on the dense kernels (trainable A, or a gradient wanted for x): the masked copies
             # have exactly-constant regions, so the embedding net must break pool ties the way torch does
@@ -415,15 +424,18 @@ class DAGConditioner(Conditioner):
             return self.soft_thresholded_A()
         return self.A
 
-    def forward_rows(self, x, rows, P, host_rows=None, variable_major=False):
+    def forward_rows(self, x, rows, P, host_rows=None, variable_major=False, rows32=None):
         """h[:, rows, :] only: the conditioner output of row i depends on x through x * P[i] alone, so a
         level-scheduled inversion evaluates each row exactly once.  variable_major: the result as
         [R, B, out] (any strides) instead of [B, R, out] -- the sparse kernels produce that layout, and the level loop
-        of the inversion consumes it without a permuting copy."""
+        of the inversion consumes it without a permuting copy.  rows32: `rows` as int32 on the device, for a caller that
+        keeps such a table (the row-subset front of CIFAR10CNN reads it)."""
         B, R = x.shape[0], rows.numel()
         plan = self._sparse_plan(x, rows.tolist() if host_rows is None else host_rows, P)
         if plan is not None:
             return self.embedding_net.sparse_rows(x, P, plan, variable_major=variable_major)
+        if self._rows_front(x):
+            return self.embedding_net.forward_rows(x, P, rows.to(torch.int32) if rows32 is None else rows32, variable_major)
         if variable_major:
             return self.forward_rows(x, rows, P, host_rows).permute(1, 0, 2)
         if hasattr(self.embedding_net, "exact_pool_ties"):

@@ -162,6 +162,9 @@ class MNISTCNN(nn.Module):
 # CIFAR10CNN.gated_front of a new net; the measurement behind the value: profiles/lenet_gated_ab.txt
 GATED_FRONT_DEFAULT = False
 
+# CIFAR10CNN.rows_front of a new net; the measurement behind the value: profiles/lenet_rows_ab.txt
+ROWS_FRONT_DEFAULT = True
+
 
 class CIFAR10CNN(nn.Module):
     """LeNet-style CIFAR embedding net of the reference (:51-72): pool2(relu(conv_k(C->6))) pool2(relu(conv_k(6->16))) flatten
@@ -169,7 +172,9 @@ class CIFAR10CNN(nn.Module):
     LDS-resident kernel pair (gnf_hip.ops.LenetConvFn, csrc/gnf_lenetcnn.hip); any other geometry, a CPU tensor, or
     `fused_front = False` takes the torch convolutions.  The fc chain is on the MFMA GEMM either way.  `gated_front = True`
     lets a DAG conditioner hand over x, A and its gate instead of the B*d masked copies: the same kernels build each copy in
-    LDS (gnf_hip.ops.DagLenetFrontFn), the same features bit for bit, a third of the peak memory, no faster."""
+    LDS (gnf_hip.ops.DagLenetFrontFn), the same features bit for bit, a third of the peak memory, no faster.  `rows_front = True`
+    does the same for the no-grad, deterministic-gate calls of a DAG conditioner -- the levels of an inversion, evaluation
+    after post_process() -- which hand over x, the importance matrix and row indices (gnf_hip.ops.lenet_rows)."""
 
     def __init__(self, out_d=10, fc_l=[400, 128, 84], size_img=[3, 32, 32], k_size=5):
         super().__init__()
@@ -182,6 +187,7 @@ class CIFAR10CNN(nn.Module):
         self.fc3 = nn.Linear(fc_l[2], out_d)
         self.fused_front = True          # False: the torch conv / pool chain
         self.gated_front = GATED_FRONT_DEFAULT   # the gate of a DAG conditioner fused into the front (supports_gated)
+        self.rows_front = ROWS_FRONT_DEFAULT     # no-grad rows of a deterministic gate built in the front (supports_rows)
 
     def _fused_front(self, x):
         c, h, w = self.size_img
@@ -202,6 +208,19 @@ class CIFAR10CNN(nn.Module):
                                    self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias, self.size_img,
                                    self.conv1.weight.shape[-1])
         return ops.mlp(feat, _linears([self.fc1, self.fc2, self.fc3]))
+
+    def supports_rows(self, x):
+        """the masked copies x[b] * P[i] of a deterministic gate built inside the conv front (gnf_hip.ops.lenet_rows): a
+        [B, C*H*W] batch on the fused kernels; evaluation only, the caller checks that autograd is off"""
+        return bool(self.rows_front) and x.dim() == 2 and self._fused_front(x)
+
+    def forward_rows(self, x, P, rows32, variable_major=False):
+        """embedding_net(x[b] * P[rows32[r]]) (rows32 None: every row of P) without the copies in memory: [B, R, out_d], or
+        [R, B, out_d] when variable_major -- written in that order, no permuting copy"""
+        feat = ops.lenet_rows(x, P, rows32, self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias,
+                              self.size_img, self.conv1.weight.shape[-1], variable_major)
+        n0, n1, F = feat.shape
+        return ops.mlp(feat.view(n0 * n1, F), _linears([self.fc1, self.fc2, self.fc3])).view(n0, n1, -1)
 
     def forward(self, x, context=None):
         rows = x.shape[0]

@@ -136,7 +136,8 @@ class NormalizingFlowStep(NormalizingFlow):
             into = None
         for k, (rows, host_rows) in enumerate(levels):
             R = rows.numel()
-            h = cond.forward_rows(x, rows, importance, host_rows, variable_major=True)
+            h = cond.forward_rows(x, rows, importance, host_rows, variable_major=True,
+                                  rows32=rows32[k] if rows32 is not None and len(rows32) == len(levels) else None)
             # the normalizer writes its [R, B] result into columns `rows` of x itself where it can
             if into is None or not into(zt[off:off + R], h, x, rows32[k]):
                 x[:, rows] = self.normalizer.inverse_transform(zt[off:off + R], h, context).t()
@@ -185,6 +186,7 @@ class NormalizingFlowStep(NormalizingFlow):
         # what a captured pass bakes in: shapes, the node count, the front, and the ADDRESSES of every parameter and buffer
         # (values may change freely; a re-bound or moved tensor must not be read through a stale pointer)
         key = (tuple(z.shape), int(getattr(self.normalizer, "nb_steps", 0)), bool(getattr(cond, "sparse_front", False)),
+               bool(getattr(getattr(cond, "embedding_net", None), "rows_front", False)),
                tuple(t.data_ptr() for t in self.parameters()), tuple(t.data_ptr() for t in self.buffers()))
         graphs = _INV_GRAPHS.setdefault(self, {})
         entry = graphs.get(key)

@@ -482,6 +482,23 @@ int gnf_lenet_gated_bwd(const float* x, const float* tab, int C, int H, int W, i
                         float* gA, int accumulate, float* gW1, float* gb1, float* gW2, float* gb2,
                         void* ws, int64_t ws_bytes, int64_t B, gnf_stream_t stream);
 
+/* ---- the same front on a subset of the rows of a DETERMINISTIC gate: inversion and evaluation ---------------
+ * NormalizingFlowStep.invert asks a DAG conditioner for the rows of one topological level at a time, and deterministic
+ * evaluation for all d of them (DAGConditioner.py:142-153): image (b, r) is
+ *   x[b, :] * P[i, :],   i = rows[r]   (rows == NULL: i = r, which needs R <= d),
+ * one fp32 product per element -- the bits of torch's broadcast x.unsqueeze(1) * P[rows].unsqueeze(0) -- built in LDS: the
+ * [B, R, d] tensor (37.7 MB per sample for a level of all roots at d = 3072) never exists in memory.  Forward only, no
+ * argmax plane, nothing kept for a backward.
+ * x: [B, d] contiguous, d = C*H*W;  P: the importance matrix [d, d], rows of pitch ld_p (elements, >= d);  rows: R device
+ * indices in [0, d), any order, repeats allowed, NOT checked by the kernel;  W1, b1, W2, b2 as for gnf_lenet_conv_fwd.
+ * feat: [B, R, F] contiguous (row b*R + r), or [R, B, F] (row r*B + b) when variable_major != 0; 64-bit row offsets.
+ * GNF_ESHAPE outside the four geometries; GNF_EINVAL for a NULL operand, B < 0, R < 0, R > d with rows == NULL, ld_p < d and
+ * pointers below dword alignment (rows included).  B == 0 or R == 0: returns 0 without a launch (x and feat may be NULL). */
+int gnf_lenet_rows_fwd(const float* x, const float* P, int64_t ld_p, const int32_t* rows, int64_t R,
+                       int C, int H, int W, int k,
+                       const float* W1, const float* b1, const float* W2, const float* b2,
+                       float* feat, int variable_major, int64_t B, gnf_stream_t stream);
+
 /* ---- sparse masked-image front for a DETERMINISTIC DAG gate ---------------
  * Replaces, for evaluation / sampling, the chain  e = x * P[i]  (DAGConditioner.py:142-153, deterministic branches)
  * -> conv1/ReLU/conv2/maxpool (MLP.py:36-41) -> fc1 + ReLU (MLP.py:43-44)  when every row i of the importance matrix
