@@ -143,6 +143,12 @@ SIGNATURES = {
                                     c_i64, c_i64, c_stream]),
     "gnf_lenet_rows_fwd": (c_int, [c_f, c_f, c_i64, ctypes.c_void_p, c_i64, c_int, c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_f,
                                    c_int, c_i64, c_stream]),
+    "gnf_lenet_rows_fwd_arg": (c_int, [c_f, c_f, c_i64, ctypes.c_void_p, c_i64, c_int, c_int, c_int, c_int, c_f, c_f, c_f, c_f,
+                                       c_f, ctypes.c_void_p, c_int, c_i64, c_stream]),
+    "gnf_lenet_rows_bwd_ws_bytes": (c_i64, [c_int, c_int, c_int, c_int, c_i64, c_i64, c_int]),
+    "gnf_lenet_rows_bwd": (c_int, [c_f, c_f, c_i64, ctypes.c_void_p, c_i64, c_int, c_int, c_int, c_int, c_f, c_f, c_f, c_f,
+                                   ctypes.c_void_p, c_f, c_int, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p, c_i64, c_i64,
+                                   c_stream]),
     "gnf_mnistcnn_sparse_ws_bytes": (c_i64, [c_i64, c_i64]),
     "gnf_mnistcnn_sparse_fwd": (c_int, [c_f, c_i64, c_f, ctypes.c_void_p, c_i64, ctypes.c_void_p, c_i64, c_f, c_f, c_f,
                                         c_f, c_f, c_f, c_i64, c_f, c_f, ctypes.c_void_p, ctypes.c_void_p, c_i64,

@@ -40,6 +40,9 @@
 // backward multiplies dL/de by de/dp and sums over the samples in registers: neither e nor its cotangent exists in HBM.
 // lenet_rows_fwd_k is the no-grad sibling for a deterministic gate: the rows i of a level of the inversion (or all d of them)
 // as x[b, :] * P[i, :], the [B, R, d] broadcast product of DAGConditioner.forward_rows built in LDS.
+// lenet_rows_fwd_arg_k / lenet_rows_bwd_k are its training form for a FROZEN gate (P a constant): the forward also keeps the
+// second pool's decisions, the backward rebuilds each copy in LDS, skips dL/de altogether when x is data and otherwise
+// sums dL/dx over the rows in registers (DetRowsSrc).
 #include "gnf_dag_gate.h"
 
 namespace {
@@ -352,14 +355,15 @@ __device__ __forceinline__ void stage_rows(float* xs, const float* __restrict__ 
 }
 
 // a unit of work is (row slot r, group of IPB samples), r-major: consecutive units reuse one row of P.  Feature row of
-// (b, r): b*R + r, or r*B + b when variable_major
-template <class G>
-__global__ __launch_bounds__(kThreads, 4) void lenet_rows_fwd_k(const float* __restrict__ x, const float* __restrict__ P,
-                                                             int64_t ld_p, const int32_t* __restrict__ rows, int64_t R,
-                                                             int64_t B, const float* __restrict__ W1,
-                                                             const float* __restrict__ b1, const float* __restrict__ W2,
-                                                             const float* __restrict__ b2, float* __restrict__ feat,
-                                                             int variable_major) {
+// (b, r): b*R + r, or r*B + b when variable_major.  SAVE: the training form, which also writes the second pool's decisions
+// to arg2 (same row order as feat) for lenet_rows_bwd_k
+template <class G, bool SAVE>
+__device__ __forceinline__ void rows_fwd_body(const float* __restrict__ x, const float* __restrict__ P, int64_t ld_p,
+                                              const int32_t* __restrict__ rows, int64_t R, int64_t B,
+                                              const float* __restrict__ W1, const float* __restrict__ b1,
+                                              const float* __restrict__ W2, const float* __restrict__ b2,
+                                              float* __restrict__ feat, unsigned char* __restrict__ arg2,
+                                              int variable_major) {
   __shared__ __attribute__((aligned(16))) float xs[G::IPB * G::IMG];
   __shared__ float a1s[G::IPB * 6 * G::NP1];
   const int tid = threadIdx.x;
@@ -371,15 +375,36 @@ __global__ __launch_bounds__(kThreads, 4) void lenet_rows_fwd_k(const float* __r
     __syncthreads();
     conv1_phase<G>(xs, a1s, nullptr, W1, b1, tid);
     __syncthreads();
-    conv2_phase<G>(a1s, W2, b2, tid, [&](int s, int ch, int cell, float m, int) {
+    conv2_phase<G>(a1s, W2, b2, tid, [&](int s, int ch, int cell, float m, int code) {
       const int64_t b = b0 + s;
       if (b < B) {
         const int64_t im = variable_major ? r * B + b : b * R + r;
         feat[im * G::F + ch * G::NP2 + cell] = m;
+        if (SAVE) arg2[im * G::F + ch * G::NP2 + cell] = (unsigned char)code;
       }
     });
     __syncthreads();
   }
+}
+
+template <class G>
+__global__ __launch_bounds__(kThreads, 4) void lenet_rows_fwd_k(const float* __restrict__ x, const float* __restrict__ P,
+                                                             int64_t ld_p, const int32_t* __restrict__ rows, int64_t R,
+                                                             int64_t B, const float* __restrict__ W1,
+                                                             const float* __restrict__ b1, const float* __restrict__ W2,
+                                                             const float* __restrict__ b2, float* __restrict__ feat,
+                                                             int variable_major) {
+  rows_fwd_body<G, false>(x, P, ld_p, rows, R, B, W1, b1, W2, b2, feat, nullptr, variable_major);
+}
+
+template <class G>
+__global__ __launch_bounds__(kThreads, 4) void lenet_rows_fwd_arg_k(const float* __restrict__ x, const float* __restrict__ P,
+                                                                 int64_t ld_p, const int32_t* __restrict__ rows, int64_t R,
+                                                                 int64_t B, const float* __restrict__ W1,
+                                                                 const float* __restrict__ b1, const float* __restrict__ W2,
+                                                                 const float* __restrict__ b2, float* __restrict__ feat,
+                                                                 unsigned char* __restrict__ arg2, int variable_major) {
+  rows_fwd_body<G, true>(x, P, ld_p, rows, R, B, W1, b1, W2, b2, feat, arg2, variable_major);
 }
 
 // --------------------------------------------------------------------------------------------------------------- backward
@@ -508,6 +533,91 @@ struct GatedSrc {
         __syncthreads();
       }
     }
+  }
+};
+
+// DetRowsSrc: the copies x[b] * P[rows[r]] of a FROZEN deterministic gate built in LDS (stage_rows): no noise, no de/dp
+// plane, no dL/dP.  A unit of work is (chunk ch of a.rpc whole rows, group of IPB samples), chunk-major so that the
+// workgroups of one wave of the grid read the same rows of P.
+//   WANT_DX = false (x is data): the host sets rpc = 1, i.e. the r-major units of lenet_rows_fwd_k; de_phase is empty.
+//   WANT_DX = true: dL/dx[b, j] = sum_r P[rows[r], j] dL/de[b, r, j].  A thread owns the same (sample slot, pixel) set in
+//     every row of the chunk -- NPASS x NPT x C accumulators, 12 at (3,32,32,5), 7 at (1,8,8,2) -- and adds dL/de * P in
+//     registers; P[i, pixel] is read again from L2 (one row, 12 KB at d = 3072: no second LDS plane), and a pixel whose P
+//     entries are all zero -- most of them once post_process() has left a 0/1 DAG -- skips its W1^T dpre1 gather.  The unit
+//     writes its sums to plane ch of a.dxp [nchunk][B][d]; every (ch, b, j) has exactly one writer, and lenet_rows_dx_k
+//     adds the planes in chunk order.
+struct RowsArgs {
+  const float* x; const float* P; int64_t ld_p; const int32_t* rows; int64_t R, B; int variable_major;
+  float* dxp; int64_t rpc, nchunk;         // backward: [nchunk, B, d] sums of dL/dx, rows per chunk
+};
+
+template <class G, bool WANT_DX>
+struct DetRowsSrc {
+  static constexpr int NPT = GatedSrc<G>::NPT, SPI = GatedSrc<G>::SPI;     // the pixel ownership of GatedSrc
+  static constexpr int NPASS = G::IPB / SPI;                               // passes over the group's samples
+  struct Group { int64_t r, i, b0; };
+  RowsArgs a;
+  float acc_dx[WANT_DX ? NPASS : 1][NPT][G::C];
+
+  template <class F>
+  __device__ __forceinline__ void for_each_group(F f) {
+    const int64_t ngb = (a.B + G::IPB - 1) / G::IPB;
+    for (int64_t u = blockIdx.x; u < a.nchunk * ngb; u += gridDim.x) {
+      const int64_t ch = u / ngb, b0 = (u % ngb) * G::IPB;
+      if (WANT_DX) {
+#pragma unroll
+        for (int ps = 0; ps < NPASS; ++ps)
+#pragma unroll
+          for (int t = 0; t < NPT; ++t)
+#pragma unroll
+            for (int c = 0; c < G::C; ++c) acc_dx[ps][t][c] = 0.f;
+      }
+      const int64_t r1 = (ch + 1) * a.rpc < a.R ? (ch + 1) * a.rpc : a.R;
+      for (int64_t r = ch * a.rpc; r < r1; ++r) f(Group{r, a.rows ? (int64_t)a.rows[r] : r, b0});
+      if (WANT_DX) flush(a.dxp + ch * a.B * G::IMG, b0, threadIdx.x);
+    }
+  }
+  __device__ __forceinline__ void stage(float* xs, Group g, int tid) {
+    stage_rows<G>(xs, a.x, a.P, a.ld_p, g.i, g.b0, a.B, tid);
+  }
+  __device__ __forceinline__ int64_t row(Group g, int s) const {
+    const int64_t b = g.b0 + s;
+    return b < a.B ? (a.variable_major ? g.r * a.B + b : b * a.R + g.r) : -1;
+  }
+  __device__ __forceinline__ void de_phase(const float* d1, const float* __restrict__ W1, Group g, int tid) {
+    if (!WANT_DX) return;
+    const float* __restrict__ pr = a.P + g.i * a.ld_p;
+#pragma unroll
+    for (int ps = 0; ps < NPASS; ++ps)
+#pragma unroll
+      for (int t = 0; t < NPT; ++t) {
+        const int s = SPI == 1 ? ps : ps * SPI + tid / G::HW, r = SPI == 1 ? t * kThreads + tid : tid % G::HW;
+        float p[G::C];
+        bool any = false;
+#pragma unroll
+        for (int c = 0; c < G::C; ++c) {
+          p[c] = pr[c * G::HW + r];
+          any = any || p[c] != 0.f;
+        }
+        if (any && g.b0 + s < a.B) {
+          float acc[G::C];
+          de_pixel<G>(d1 + s * 6 * G::U1 * G::U1, W1, r / G::W, r % G::W, acc);
+#pragma unroll
+          for (int c = 0; c < G::C; ++c) acc_dx[ps][t][c] = fmaf(acc[c], p[c], acc_dx[ps][t][c]);
+        }
+      }
+  }
+  // the unit's sums -> rows b0 .. b0 + IPB - 1 of one chunk's plane out [B][d]
+  __device__ __forceinline__ void flush(float* out, int64_t b0, int tid) {
+#pragma unroll
+    for (int ps = 0; ps < NPASS; ++ps)
+#pragma unroll
+      for (int t = 0; t < NPT; ++t) {
+        const int s = SPI == 1 ? ps : ps * SPI + tid / G::HW, r = SPI == 1 ? t * kThreads + tid : tid % G::HW;
+        if (b0 + s < a.B)
+#pragma unroll
+          for (int c = 0; c < G::C; ++c) out[(b0 + s) * G::IMG + c * G::HW + r] = acc_dx[ps][t][c];
+      }
   }
 };
 
@@ -695,6 +805,29 @@ __global__ __launch_bounds__(kThreads, 2) void lenet_gated_bwd_k(GatedArgs a, co
   lenet_bwd_body<G, RECOMPUTE>(src, xs, W1, b1, W2, b2, arg2, g_feat, part);
 }
 
+template <class G, bool RECOMPUTE, bool WANT_DX>
+__global__ __launch_bounds__(kThreads, 2) void lenet_rows_bwd_k(RowsArgs a, const float* __restrict__ W1,
+                                                             const float* __restrict__ b1, const float* __restrict__ W2,
+                                                             const float* __restrict__ b2,
+                                                             const unsigned char* __restrict__ arg2,
+                                                             const float* __restrict__ g_feat, float* __restrict__ part) {
+  __shared__ __attribute__((aligned(16))) float xs[G::IPB * G::IMG];
+  DetRowsSrc<G, WANT_DX> src;
+  src.a = a;
+  lenet_bwd_body<G, RECOMPUTE>(src, xs, W1, b1, W2, b2, arg2, g_feat, part);
+}
+
+// gx = sum over the nc chunks of rows, in chunk order;  nc = 0 (no rows): zeros
+__global__ __launch_bounds__(kThreads) void lenet_rows_dx_k(const float* __restrict__ dxp, int nc, float* __restrict__ gx,
+                                                            int64_t n) {
+  const int64_t ij = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (ij >= n) return;
+  float s = 0.f;
+  if (nc > 0) s = dxp[ij];
+  for (int c = 1; c < nc; ++c) s += dxp[(int64_t)c * n + ij];
+  gx[ij] = s;
+}
+
 // gA (+)= (sum over the nc chunks of samples, in chunk order) * dP/dA;  nc = 0 (empty batch): zeros, or gA left alone
 __global__ __launch_bounds__(kThreads) void lenet_gated_dA_k(const float* __restrict__ tab, const float* __restrict__ dp,
                                                              int nc, float* __restrict__ gA, int accumulate, int64_t dd) {
@@ -824,14 +957,84 @@ int gated_fwd_launch(const GatedArgs& a, const float* W1, const float* b1, const
 
 template <class G>
 int rows_fwd_launch(const float* x, const float* P, int64_t ld_p, const int32_t* rows, int64_t R, const float* W1,
-                    const float* b1, const float* W2, const float* b2, float* feat, int variable_major, int64_t B,
-                    hipStream_t s) {
+                    const float* b1, const float* W2, const float* b2, float* feat, unsigned char* arg2, int variable_major,
+                    int64_t B, hipStream_t s) {
   if (ld_p < G::IMG || (!rows && R > G::IMG)) return GNF_EINVAL;
   if (B == 0 || R == 0) return 0;
   const int64_t units = R * ((B + G::IPB - 1) / G::IPB);
-  hipLaunchKernelGGL(lenet_rows_fwd_k<G>, dim3((unsigned)(units < kFwdGridMax ? units : kFwdGridMax)), dim3(kThreads), 0, s,
-                     x, P, ld_p, rows, R, B, W1, b1, W2, b2, feat, variable_major);
+  const dim3 grid((unsigned)(units < kFwdGridMax ? units : kFwdGridMax));
+  if (arg2)
+    hipLaunchKernelGGL(lenet_rows_fwd_arg_k<G>, grid, dim3(kThreads), 0, s, x, P, ld_p, rows, R, B, W1, b1, W2, b2, feat, arg2,
+                       variable_major);
+  else
+    hipLaunchKernelGGL(lenet_rows_fwd_k<G>, grid, dim3(kThreads), 0, s, x, P, ld_p, rows, R, B, W1, b1, W2, b2, feat,
+                       variable_major);
   GNF_LAUNCH_CHECK();
+  return 0;
+}
+
+// chunks of rows of the rows backward with dL/dx: whole rows, enough units (chunk, group of samples) to fill the grid,
+// nchunk <= R.  Without dL/dx a chunk is one row (the units of the forward)
+template <class G>
+void rows_chunks(int64_t R, int64_t B, bool want_gx, int64_t& rpc, int64_t& nchunk) {
+  if (!want_gx || R == 0 || B == 0) {
+    rpc = 1;
+    nchunk = (B == 0) ? 0 : R;
+    return;
+  }
+  const int64_t ngb = (B + G::IPB - 1) / G::IPB;
+  nchunk = (kBwdGridMax + ngb - 1) / ngb;
+  if (nchunk > R) nchunk = R;
+  rpc = (R + nchunk - 1) / nchunk;
+  nchunk = (R + rpc - 1) / rpc;
+}
+
+template <class G>
+int rows_bwd_grid(int64_t R, int64_t B, bool want_gx) {
+  int64_t rpc, nchunk;
+  rows_chunks<G>(R, B, want_gx, rpc, nchunk);
+  const int64_t units = nchunk * ((B + G::IPB - 1) / G::IPB);
+  return (int)(units < kBwdGridMax ? units : kBwdGridMax);
+}
+
+// partial weight gradients [grid][PW] | sums of dL/dx [nchunk][B][d] (want_gx)
+template <class G>
+int64_t rows_ws_bytes_of(int64_t R, int64_t B, bool want_gx) {
+  int64_t rpc, nchunk;
+  rows_chunks<G>(R, B, want_gx, rpc, nchunk);
+  const int64_t nb = rows_bwd_grid<G>(R, B, want_gx);
+  return ((nb > 0 ? nb : 1) * G::PW + (want_gx ? nchunk * B * G::IMG : 0)) * (int64_t)sizeof(float);
+}
+
+template <class G>
+int rows_bwd_launch(RowsArgs a, const float* W1, const float* b1, const float* W2, const float* b2,
+                    const unsigned char* arg2, const float* g_feat, float* gx, float* gW1, float* gb1, float* gW2,
+                    float* gb2, float* ws, hipStream_t s) {
+  if (a.ld_p < G::IMG || (!a.rows && a.R > G::IMG)) return GNF_EINVAL;
+  const int nb = rows_bwd_grid<G>(a.R, a.B, gx != nullptr);
+  rows_chunks<G>(a.R, a.B, gx != nullptr, a.rpc, a.nchunk);
+  a.dxp = gx ? ws + (int64_t)(nb > 0 ? nb : 1) * G::PW : nullptr;
+  if (nb > 0) {
+    const dim3 grid(nb), block(kThreads);
+    if (arg2 && gx)
+      hipLaunchKernelGGL((lenet_rows_bwd_k<G, false, true>), grid, block, 0, s, a, W1, b1, W2, b2, arg2, g_feat, ws);
+    else if (arg2)
+      hipLaunchKernelGGL((lenet_rows_bwd_k<G, false, false>), grid, block, 0, s, a, W1, b1, W2, b2, arg2, g_feat, ws);
+    else if (gx)
+      hipLaunchKernelGGL((lenet_rows_bwd_k<G, true, true>), grid, block, 0, s, a, W1, b1, W2, b2, arg2, g_feat, ws);
+    else
+      hipLaunchKernelGGL((lenet_rows_bwd_k<G, true, false>), grid, block, 0, s, a, W1, b1, W2, b2, arg2, g_feat, ws);
+    GNF_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(lenet_reduce_k, dim3((G::PW + kThreads - 1) / kThreads), dim3(kThreads), 0, s, ws, nb, G::PW,
+                     6 * G::T1, 16 * G::T2, gW1, gb1, gW2, gb2);
+  GNF_LAUNCH_CHECK();
+  const int64_t n = a.B * G::IMG;
+  if (gx && n > 0) {
+    hipLaunchKernelGGL(lenet_rows_dx_k, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a.dxp,
+                       nb > 0 ? (int)a.nchunk : 0, gx, n);
+    GNF_LAUNCH_CHECK();
+  }
   return 0;
 }
 
@@ -962,9 +1165,9 @@ int gnf_lenet_gated_fwd(const float* x, const float* A, float* tab, int C, int H
   }
 }
 
-int gnf_lenet_rows_fwd(const float* x, const float* P, int64_t ld_p, const int32_t* rows, int64_t R, int C, int H, int W,
-                       int k, const float* W1, const float* b1, const float* W2, const float* b2, float* feat,
-                       int variable_major, int64_t B, gnf_stream_t stream) {
+int gnf_lenet_rows_fwd_arg(const float* x, const float* P, int64_t ld_p, const int32_t* rows, int64_t R, int C, int H, int W,
+                           int k, const float* W1, const float* b1, const float* W2, const float* b2, float* feat,
+                           unsigned char* argmax2, int variable_major, int64_t B, gnf_stream_t stream) {
   const int gi = geo_index(C, H, W, k);
   if (gi < 0) return GNF_ESHAPE;
   if (B < 0 || R < 0 || !P || !W1 || !b1 || !W2 || !b2 || ((!x || !feat) && B > 0 && R > 0)) return GNF_EINVAL;
@@ -972,10 +1175,53 @@ int gnf_lenet_rows_fwd(const float* x, const float* P, int64_t ld_p, const int32
     return GNF_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   switch (gi) {
-    case 0: return rows_fwd_launch<G0>(x, P, ld_p, rows, R, W1, b1, W2, b2, feat, variable_major, B, s);
-    case 1: return rows_fwd_launch<G1>(x, P, ld_p, rows, R, W1, b1, W2, b2, feat, variable_major, B, s);
-    case 2: return rows_fwd_launch<G2>(x, P, ld_p, rows, R, W1, b1, W2, b2, feat, variable_major, B, s);
-    default: return rows_fwd_launch<G3>(x, P, ld_p, rows, R, W1, b1, W2, b2, feat, variable_major, B, s);
+    case 0: return rows_fwd_launch<G0>(x, P, ld_p, rows, R, W1, b1, W2, b2, feat, argmax2, variable_major, B, s);
+    case 1: return rows_fwd_launch<G1>(x, P, ld_p, rows, R, W1, b1, W2, b2, feat, argmax2, variable_major, B, s);
+    case 2: return rows_fwd_launch<G2>(x, P, ld_p, rows, R, W1, b1, W2, b2, feat, argmax2, variable_major, B, s);
+    default: return rows_fwd_launch<G3>(x, P, ld_p, rows, R, W1, b1, W2, b2, feat, argmax2, variable_major, B, s);
+  }
+}
+
+int gnf_lenet_rows_fwd(const float* x, const float* P, int64_t ld_p, const int32_t* rows, int64_t R, int C, int H, int W,
+                       int k, const float* W1, const float* b1, const float* W2, const float* b2, float* feat,
+                       int variable_major, int64_t B, gnf_stream_t stream) {
+  return gnf_lenet_rows_fwd_arg(x, P, ld_p, rows, R, C, H, W, k, W1, b1, W2, b2, feat, nullptr, variable_major, B, stream);
+}
+
+int64_t gnf_lenet_rows_bwd_ws_bytes(int C, int H, int W, int k, int64_t R, int64_t B, int want_gx) {
+  if (R < 0 || B < 0) return GNF_EINVAL;
+  switch (geo_index(C, H, W, k)) {
+    case 0: return rows_ws_bytes_of<G0>(R, B, want_gx != 0);
+    case 1: return rows_ws_bytes_of<G1>(R, B, want_gx != 0);
+    case 2: return rows_ws_bytes_of<G2>(R, B, want_gx != 0);
+    case 3: return rows_ws_bytes_of<G3>(R, B, want_gx != 0);
+  }
+  return GNF_ESHAPE;
+}
+
+int gnf_lenet_rows_bwd(const float* x, const float* P, int64_t ld_p, const int32_t* rows, int64_t R, int C, int H, int W,
+                       int k, const float* W1, const float* b1, const float* W2, const float* b2,
+                       const unsigned char* argmax2, const float* g_feat, int variable_major, float* gx, float* gW1,
+                       float* gb1, float* gW2, float* gb2, void* ws, int64_t ws_bytes, int64_t B, gnf_stream_t stream) {
+  const int gi = geo_index(C, H, W, k);
+  if (gi < 0) return GNF_ESHAPE;
+  if (B < 0 || R < 0 || !P || !W1 || !b1 || !W2 || !b2 || !gW1 || !gb1 || !gW2 || !gb2 || !ws ||
+      ((!x || !g_feat) && B > 0 && R > 0))
+    return GNF_EINVAL;
+  if (bad_f32(x) || bad_f32(P) || bad_f32(rows) || bad_f32(W1) || bad_f32(b1) || bad_f32(W2) || bad_f32(b2) ||
+      bad_f32(g_feat) || bad_f32(gx) || bad_f32(gW1) || bad_f32(gb1) || bad_f32(gW2) || bad_f32(gb2) || bad_f32(ws))
+    return GNF_EINVAL;
+  if (ld_p < (int64_t)C * H * W || (!rows && R > (int64_t)C * H * W)) return GNF_EINVAL;
+  if (ws_bytes < gnf_lenet_rows_bwd_ws_bytes(C, H, W, k, R, B, gx != nullptr)) return GNF_EWS;
+  hipStream_t s = (hipStream_t)stream;
+  RowsArgs a{};
+  a.x = x; a.P = P; a.ld_p = ld_p; a.rows = rows; a.R = R; a.B = B; a.variable_major = variable_major;
+  float* w = static_cast<float*>(ws);
+  switch (gi) {
+    case 0: return rows_bwd_launch<G0>(a, W1, b1, W2, b2, argmax2, g_feat, gx, gW1, gb1, gW2, gb2, w, s);
+    case 1: return rows_bwd_launch<G1>(a, W1, b1, W2, b2, argmax2, g_feat, gx, gW1, gb1, gW2, gb2, w, s);
+    case 2: return rows_bwd_launch<G2>(a, W1, b1, W2, b2, argmax2, g_feat, gx, gW1, gb1, gW2, gb2, w, s);
+    default: return rows_bwd_launch<G3>(a, W1, b1, W2, b2, argmax2, g_feat, gx, gW1, gb1, gW2, gb2, w, s);
   }
 }
 

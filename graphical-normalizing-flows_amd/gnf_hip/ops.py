@@ -617,10 +617,21 @@ def lenet_rows(x, P, rows32, W1, b1, W2, b2, size_img, k, variable_major=False):
     lenet_conv on that product.  Evaluation only: a plain function, no autograd node."""
     if torch.is_grad_enabled() and any(t.requires_grad for t in (x, P, W1, b1, W2, b2)):
         raise abi.GnfError("lenet_rows has no backward: call it under torch.no_grad() or on operands without requires_grad")
+    x, P, rows32, R, geo, F = _rows_operands(x, P, rows32, size_img, k)
+    B = x.shape[0]
+    feat = _empty((R, B, F) if variable_major else (B, R, F), x)
+    call("gnf_lenet_rows_fwd", ptr(x), ptr(P), P.stride(0), abi.rawptr(rows32) if rows32 is not None else None, R, *geo,
+         ptr(W1.contiguous()), ptr(b1.contiguous()), ptr(W2.contiguous()), ptr(b2.contiguous()), ptr(feat),
+         int(bool(variable_major)), B, stream())
+    return feat
+
+
+def _rows_operands(x, P, rows32, size_img, k):
+    """the operands of gnf_lenet_rows_* as the kernels want them: (x, P, rows32, R, (C, H, W, k), F)"""
     c, h, w = (int(v) for v in size_img)
     k = int(k)
     x = x.contiguous()
-    B, d = x.shape
+    d = x.shape[1]
     if d != c * h * w or tuple(P.shape) != (d, d):
         raise abi.GnfError("the row-subset front needs x [B, %d] and P [%d, %d]" % (c * h * w, d, d))
     if P.stride(1) != 1 or P.stride(0) < d:
@@ -635,11 +646,53 @@ def lenet_rows(x, P, rows32, W1, b1, W2, b2, size_img, k, variable_major=False):
     F = int(abi.load().gnf_lenet_conv_feat(c, h, w, k))
     if F < 0:
         abi.check(F, "gnf_lenet_conv_feat")
-    feat = _empty((R, B, F) if variable_major else (B, R, F), x)
-    call("gnf_lenet_rows_fwd", ptr(x), ptr(P), P.stride(0), abi.rawptr(rows32) if rows32 is not None else None, R, c, h, w, k,
-         ptr(W1.contiguous()), ptr(b1.contiguous()), ptr(W2.contiguous()), ptr(b2.contiguous()), ptr(feat),
-         int(bool(variable_major)), B, stream())
-    return feat
+    return x, P, rows32, R, (c, h, w, k), F
+
+
+class LenetRowsFn(torch.autograd.Function):
+    """lenet_rows with a backward, for training behind a FROZEN deterministic gate (csrc/gnf_lenetcnn.hip,
+    gnf_lenet_rows_fwd_arg / gnf_lenet_rows_bwd): differentiable w.r.t. the four conv parameters and, when it asks for one,
+    x; never w.r.t. P.  Saved for the backward: x, P, rows32, the parameters and one byte per feature (the second pool's
+    decisions) -- never a [B, R, d] tensor, forward or backward.  No host synchronisation: safe under hipGraph capture."""
+
+    @staticmethod
+    def forward(ctx, x, P, rows32, W1, b1, W2, b2, size_img, k, variable_major, grad_mode=None):
+        x, P, rows32, R, geo, F = _rows_operands(x, P, rows32, size_img, k)
+        B = x.shape[0]
+        W1c, b1c, W2c, b2c = W1.contiguous(), b1.contiguous(), W2.contiguous(), b2.contiguous()
+        feat = _empty((R, B, F) if variable_major else (B, R, F), x)
+        keep = bool(grad_mode) and any(ctx.needs_input_grad) and os.environ.get("GNF_LENET_SAVE_ARGMAX", "1") != "0"
+        arg = torch.empty((B * R, F), dtype=torch.uint8, device=x.device) if keep else None
+        rp = abi.rawptr(rows32) if rows32 is not None else None
+        call("gnf_lenet_rows_fwd_arg", ptr(x), ptr(P), P.stride(0), rp, R, *geo, ptr(W1c), ptr(b1c), ptr(W2c), ptr(b2c),
+             ptr(feat), abi.rawptr(arg) if keep else None, int(bool(variable_major)), B, stream())
+        ctx.save_for_backward(x, P, rows32, W1c, b1c, W2c, b2c)
+        ctx.arg, ctx.cfg = arg, (R, geo, int(bool(variable_major)))
+        return feat
+
+    @staticmethod
+    def backward(ctx, gf):
+        x, P, rows32, W1, b1, W2, b2 = ctx.saved_tensors
+        R, geo, vm = ctx.cfg
+        B, d = x.shape
+        gf = gf.contiguous()
+        gx = _empty((B, d), x) if ctx.needs_input_grad[0] else None
+        outs = [grad_out_shared(p) for p in (W1, b1, W2, b2)]
+        nws = abi.load().gnf_lenet_rows_bwd_ws_bytes(*geo, R, B, int(gx is not None))
+        ws = _ws(nws, x)
+        call("gnf_lenet_rows_bwd", ptr(x), ptr(P), P.stride(0), abi.rawptr(rows32) if rows32 is not None else None, R, *geo,
+             ptr(W1), ptr(b1), ptr(W2), ptr(b2), abi.rawptr(ctx.arg) if ctx.arg is not None else None, ptr(gf), vm,
+             ptr(gx), *(ptr(t) for t, _, _ in outs), abi.rawptr(ws), nws, B, stream())
+        return (gx, None, None, *(finish(t) for t, finish, _ in outs), None, None, None, None)
+
+
+def lenet_rows_train(x, P, rows32, W1, b1, W2, b2, size_img, k, variable_major=False):
+    """lenet_rows as an autograd node (LenetRowsFn): the features [B, R, F] ([R, B, F] when variable_major) of the copies
+    x[b] * P[rows32[r]], with gradients for W1, b1, W2, b2 and for x when x.requires_grad.  P is a constant of the node: a P
+    that requires grad (a trainable A) is refused, the caller takes the composed path for it."""
+    if P.requires_grad:
+        raise abi.GnfError("lenet_rows_train has no gradient for P: freeze A (post_process()) or take the composed path")
+    return LenetRowsFn.apply(x, P, rows32, W1, b1, W2, b2, size_img, k, bool(variable_major), torch.is_grad_enabled())
 
 
 def crop_origin(p):

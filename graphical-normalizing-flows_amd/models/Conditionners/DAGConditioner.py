@@ -198,12 +198,18 @@ class DAGConditioner(Conditioner):
             self._sparse_plans[plan_key] = ops.SparseRows(rows, x.shape[0], x.device)
         return self._sparse_plans[plan_key]
 
-    def _rows_front(self, x):
+    def _rows_front(self, x, P):
         """True when the embedding net builds the masked copies x * P[i] of a deterministic gate itself
-        (CIFAR10CNN.forward_rows): evaluation only, plain [B, d] inputs"""
+        (CIFAR10CNN.forward_rows), plain [B, d] inputs: under no_grad whenever the net offers it (`rows_front`); with
+        autograd on only behind a frozen gate -- P needs no gradient -- and when the net offers the training form
+        (`rows_train_front`: gradients for the net's parameters and for x)"""
         net = self.embedding_net
-        return (not torch.is_grad_enabled() and not self.hot_encoding and not self.cond_in
-                and hasattr(net, "supports_rows") and x.dim() == 2 and x.shape[1] == self.in_size and net.supports_rows(x))
+        if (self.hot_encoding or self.cond_in or not hasattr(net, "supports_rows") or x.dim() != 2
+                or x.shape[1] != self.in_size):
+            return False
+        if not torch.is_grad_enabled():
+            return net.supports_rows(x)
+        return not P.requires_grad and hasattr(net, "supports_rows_train") and net.supports_rows_train(x)
 
     def forward(self, x, context=None):
         no_context(context, self.cond_in)
@@ -212,7 +218,7 @@ class DAGConditioner(Conditioner):
             plan = self._sparse_plan(x, None, P)
             if plan is not None:
                 return self.embedding_net.sparse_rows(x, P, plan)
-            if self._rows_front(x):
+            if self._rows_front(x, P):
                 return self.embedding_net.forward_rows(x, P, None, False)      # all d rows, neither e nor a gate table
         if hasattr(self.embedding_net, "exact_pool_ties"):
             # deterministic gate on the dense kernels (trainable A, or a gradient wanted for x): the masked copies
@@ -434,7 +440,7 @@ class DAGConditioner(Conditioner):
         plan = self._sparse_plan(x, rows.tolist() if host_rows is None else host_rows, P)
         if plan is not None:
             return self.embedding_net.sparse_rows(x, P, plan, variable_major=variable_major)
-        if self._rows_front(x):
+        if self._rows_front(x, P):
             return self.embedding_net.forward_rows(x, P, rows.to(torch.int32) if rows32 is None else rows32, variable_major)
         if variable_major:
             return self.forward_rows(x, rows, P, host_rows).permute(1, 0, 2)

@@ -165,6 +165,9 @@ GATED_FRONT_DEFAULT = False
 # CIFAR10CNN.rows_front of a new net; the measurement behind the value: profiles/lenet_rows_ab.txt
 ROWS_FRONT_DEFAULT = True
 
+# CIFAR10CNN.rows_train_front of a new net; the measurement behind the value: profiles/lenet_rows_train_ab.txt
+ROWS_TRAIN_FRONT_DEFAULT = False
+
 
 class CIFAR10CNN(nn.Module):
     """LeNet-style CIFAR embedding net of the reference (:51-72): pool2(relu(conv_k(C->6))) pool2(relu(conv_k(6->16))) flatten
@@ -174,7 +177,9 @@ class CIFAR10CNN(nn.Module):
     lets a DAG conditioner hand over x, A and its gate instead of the B*d masked copies: the same kernels build each copy in
     LDS (gnf_hip.ops.DagLenetFrontFn), the same features bit for bit, a third of the peak memory, no faster.  `rows_front = True`
     does the same for the no-grad, deterministic-gate calls of a DAG conditioner -- the levels of an inversion, evaluation
-    after post_process() -- which hand over x, the importance matrix and row indices (gnf_hip.ops.lenet_rows)."""
+    after post_process() -- which hand over x, the importance matrix and row indices (gnf_hip.ops.lenet_rows).
+    `rows_train_front = True` extends that to the calls with autograd on behind a FROZEN deterministic gate -- training after
+    post_process() -- through gnf_hip.ops.lenet_rows_train: gradients for the conv parameters and for x, none for the gate."""
 
     def __init__(self, out_d=10, fc_l=[400, 128, 84], size_img=[3, 32, 32], k_size=5):
         super().__init__()
@@ -188,6 +193,7 @@ class CIFAR10CNN(nn.Module):
         self.fused_front = True          # False: the torch conv / pool chain
         self.gated_front = GATED_FRONT_DEFAULT   # the gate of a DAG conditioner fused into the front (supports_gated)
         self.rows_front = ROWS_FRONT_DEFAULT     # no-grad rows of a deterministic gate built in the front (supports_rows)
+        self.rows_train_front = ROWS_TRAIN_FRONT_DEFAULT   # the same with autograd on, frozen gate (supports_rows_train)
 
     def _fused_front(self, x):
         c, h, w = self.size_img
@@ -214,11 +220,18 @@ class CIFAR10CNN(nn.Module):
         [B, C*H*W] batch on the fused kernels; evaluation only, the caller checks that autograd is off"""
         return bool(self.rows_front) and x.dim() == 2 and self._fused_front(x)
 
+    def supports_rows_train(self, x):
+        """supports_rows for a call with autograd on (gnf_hip.ops.lenet_rows_train): the caller checks that the importance
+        matrix needs no gradient"""
+        return bool(self.rows_train_front) and x.dim() == 2 and self._fused_front(x)
+
     def forward_rows(self, x, P, rows32, variable_major=False):
         """embedding_net(x[b] * P[rows32[r]]) (rows32 None: every row of P) without the copies in memory: [B, R, out_d], or
-        [R, B, out_d] when variable_major -- written in that order, no permuting copy"""
-        feat = ops.lenet_rows(x, P, rows32, self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias,
-                              self.size_img, self.conv1.weight.shape[-1], variable_major)
+        [R, B, out_d] when variable_major -- written in that order, no permuting copy.  With autograd on the front is the
+        node gnf_hip.ops.LenetRowsFn (P a constant), without it the plain function gnf_hip.ops.lenet_rows"""
+        front = ops.lenet_rows_train if torch.is_grad_enabled() else ops.lenet_rows
+        feat = front(x, P, rows32, self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias,
+                     self.size_img, self.conv1.weight.shape[-1], variable_major)
         n0, n1, F = feat.shape
         return ops.mlp(feat.view(n0 * n1, F), _linears([self.fc1, self.fc2, self.fc3])).view(n0, n1, -1)
 

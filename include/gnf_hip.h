@@ -499,6 +499,31 @@ int gnf_lenet_rows_fwd(const float* x, const float* P, int64_t ld_p, const int32
                        const float* W1, const float* b1, const float* W2, const float* b2,
                        float* feat, int variable_major, int64_t B, gnf_stream_t stream);
 
+/* Training behind a FROZEN deterministic gate (A fixed by post_process(), P without a gradient): the same copies, forward
+ * with the second pool's decisions kept and a backward for the conv parameters and, optionally, x.  Neither the [B, R, d]
+ * product nor its cotangent exists in memory.
+ * gnf_lenet_rows_fwd_arg: gnf_lenet_rows_fwd plus argmax2 [B*R, F] bytes in the row order of feat (NULL: exactly
+ * gnf_lenet_rows_fwd).
+ * gnf_lenet_rows_bwd: g_feat (rows as feat, per variable_major) -> gW1, gb1, gW2, gb2 (written, not accumulated) and, when
+ * gx is not NULL, gx[b, j] = sum_r P[rows[r], j] * dL/de[b, r, j], [B, d] contiguous (written).  Repeated indices in rows
+ * are rows of their own.  argmax2 NULL: conv2 is recomputed, the same bits.  gx NULL: dL/de is not computed at all, the
+ * parameter gradients keep their bits.  There is no gradient for P.  The sums over the rows are taken per (chunk of rows,
+ * group of samples) in registers, written to ws and added in chunk order: no float atomics, the same bits on every call.
+ * ws: >= gnf_lenet_rows_bwd_ws_bytes(C, H, W, k, R, B, gx != NULL) bytes, else GNF_EWS.  Other return codes as
+ * gnf_lenet_rows_fwd (gradient outputs and ws must not be NULL).  B == 0 or R == 0: no zero-sized grid is launched; the
+ * parameter gradients, and gx when given, are written as zeros. */
+int gnf_lenet_rows_fwd_arg(const float* x, const float* P, int64_t ld_p, const int32_t* rows, int64_t R,
+                           int C, int H, int W, int k,
+                           const float* W1, const float* b1, const float* W2, const float* b2,
+                           float* feat, unsigned char* argmax2, int variable_major, int64_t B, gnf_stream_t stream);
+int64_t gnf_lenet_rows_bwd_ws_bytes(int C, int H, int W, int k, int64_t R, int64_t B, int want_gx);
+int gnf_lenet_rows_bwd(const float* x, const float* P, int64_t ld_p, const int32_t* rows, int64_t R,
+                       int C, int H, int W, int k,
+                       const float* W1, const float* b1, const float* W2, const float* b2,
+                       const unsigned char* argmax2, const float* g_feat, int variable_major,
+                       float* gx, float* gW1, float* gb1, float* gW2, float* gb2,
+                       void* ws, int64_t ws_bytes, int64_t B, gnf_stream_t stream);
+
 /* ---- sparse masked-image front for a DETERMINISTIC DAG gate ---------------
  * Replaces, for evaluation / sampling, the chain  e = x * P[i]  (DAGConditioner.py:142-153, deterministic branches)
  * -> conv1/ReLU/conv2/maxpool (MLP.py:36-41) -> fc1 + ReLU (MLP.py:43-44)  when every row i of the importance matrix
