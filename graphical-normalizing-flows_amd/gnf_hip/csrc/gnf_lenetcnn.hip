@@ -871,315 +871,194 @@ typedef Geo<1, 16, 3> G2;
 typedef Geo<1, 8, 2> G3;
 static_assert(G0::F == 400 && G1::F == 576 && G2::F == 64 && G3::F == 16, "feature widths of the factory's geometries");
 
-int geo_index(int C, int H, int W, int k) {
-  if (C == 3 && H == 32 && W == 32 && k == 5) return 0;
-  if (C == 1 && H == 32 && W == 32 && k == 3) return 1;
-  if (C == 1 && H == 16 && W == 16 && k == 3) return 2;
-  if (C == 1 && H == 8 && W == 8 && k == 2) return 3;
-  return -1;
+// f(G{}) with the Geo of (C, H, W, k); GNF_ESHAPE for a geometry that has none
+template <class F>
+auto with_geo(int C, int H, int W, int k, F f) -> decltype(f(G0{})) {
+  if (C == 3 && H == 32 && W == 32 && k == 5) return f(G0{});
+  if (C == 1 && H == 32 && W == 32 && k == 3) return f(G1{});
+  if (C == 1 && H == 16 && W == 16 && k == 3) return f(G2{});
+  if (C == 1 && H == 8 && W == 8 && k == 2) return f(G3{});
+  return GNF_ESHAPE;
 }
 
-inline bool bad_f32(const void* p) { return ((uintptr_t)p & 3) != 0; }
+template <class... P>
+bool any_null(P... p) { return (... || (p == nullptr)); }
+template <class... P>
+bool any_misaligned(P... p) { return (... || (((uintptr_t)p & 3) != 0)); }      // below dword alignment; null passes
 
-template <class G>
-int grid_of(int64_t n, int cap) {
-  const int64_t groups = (n + G::IPB - 1) / G::IPB;
-  return (int)(groups < cap ? groups : cap);
+inline bool bad_gate(int imp_mode, int gate_mode, const float* u1, const float* u2) {
+  return imp_mode < 0 || imp_mode > 3 || gate_mode < 0 || gate_mode > 2 || (gate_mode == 1 && u1 && !u2);
+}
+
+inline GatedArgs gated_args(const float* x, const float* tab, int imp_mode, int gate_mode, float T, const float* u1,
+                            const float* u2, uint64_t seed, uint64_t offset, int64_t B) {
+  if (imp_mode == 0) gate_mode = 0;   // DAG:151-153: raw A, no gate
+  GatedArgs a{};                      // dp, gpc, nchunk: the backward's, filled in by it
+  a.x = x; a.tab = tab; a.u1 = u1; a.u2 = u2; a.seed = seed; a.offset = offset; a.gate_mode = gate_mode; a.T = T; a.B = B;
+  return a;
 }
 
 template <class G>
-int fwd_launch(const float* e, int64_t ld_e, const float* W1, const float* b1, const float* W2, const float* b2, float* feat,
-               unsigned char* arg2, int64_t n, hipStream_t s) {
-  if (ld_e < G::IMG) return GNF_EINVAL;
-  hipLaunchKernelGGL(lenet_fwd_k<G>, dim3(grid_of<G>(n, kFwdGridMax)), dim3(kThreads), 0, s, e, ld_e, W1, b1, W2, b2, feat,
-                     arg2, n);
-  GNF_LAUNCH_CHECK();
-  return 0;
+int64_t groups_of(int64_t n) { return (n + G::IPB - 1) / G::IPB; }
+
+inline int grid_of(int64_t units, int cap) { return (int)(units < cap ? units : cap); }
+
+// the backward's chunks (of samples when gated, of rows behind a frozen gate) and its grid
+struct Chunks { int64_t per, n; int grid; };
+
+// whole groups of IPB samples, enough units (row, chunk) to fill the grid
+template <class G>
+Chunks gated_chunks(int64_t B) {
+  const int64_t ngb = groups_of<G>(B);
+  int64_t nchunk = (kBwdGridMax + G::IMG - 1) / G::IMG;
+  if (nchunk > ngb) nchunk = ngb;
+  const int64_t gpc = nchunk > 0 ? (ngb + nchunk - 1) / nchunk : 1;
+  nchunk = (ngb + gpc - 1) / gpc;
+  return Chunks{gpc, nchunk, grid_of(G::IMG * nchunk, kBwdGridMax)};
 }
 
+// with dL/dx: whole rows, enough units (chunk, group of samples) to fill the grid, nchunk <= R.  Without it a chunk is one
+// row (the units of the forward)
 template <class G>
-int bwd_launch(const float* e, int64_t ld_e, const float* W1, const float* b1, const float* W2, const float* b2,
-               const unsigned char* arg2, const float* g_feat, float* ge, int64_t ld_ge, float* gW1, float* gb1, float* gW2,
-               float* gb2, float* part, int64_t n, hipStream_t s) {
-  if (n > 0 && (ld_e < G::IMG || (ge && ld_ge < G::IMG))) return GNF_EINVAL;
-  const int nb = n > 0 ? grid_of<G>(n, kBwdGridMax) : 0;
-  if (nb > 0) {
-    if (arg2)
-      hipLaunchKernelGGL((lenet_bwd_k<G, false>), dim3(nb), dim3(kThreads), 0, s, e, ld_e, W1, b1, W2, b2, arg2, g_feat, ge,
-                         ld_ge, part, n);
-    else
-      hipLaunchKernelGGL((lenet_bwd_k<G, true>), dim3(nb), dim3(kThreads), 0, s, e, ld_e, W1, b1, W2, b2, arg2, g_feat, ge,
-                         ld_ge, part, n);
-    GNF_LAUNCH_CHECK();
+Chunks rows_chunks(int64_t R, int64_t B, bool want_gx) {
+  const int64_t ngb = groups_of<G>(B);
+  int64_t rpc = 1, nchunk = (B == 0) ? 0 : R;
+  if (want_gx && R > 0 && B > 0) {
+    nchunk = (kBwdGridMax + ngb - 1) / ngb;
+    if (nchunk > R) nchunk = R;
+    rpc = (R + nchunk - 1) / nchunk;
+    nchunk = (R + rpc - 1) / rpc;
   }
+  return Chunks{rpc, nchunk, grid_of(nchunk * ngb, kBwdGridMax)};
+}
+
+// floats of the partial weight gradients [grid][PW] at the head of a backward's workspace
+template <class G>
+int64_t part_floats(int grid) { return (int64_t)(grid > 0 ? grid : 1) * G::PW; }
+
+template <class G>
+int64_t ws_bytes_of(int64_t n) { return part_floats<G>(grid_of(groups_of<G>(n), kBwdGridMax)) * (int64_t)sizeof(float); }
+
+// ... | sums of dL/dP [nchunk][d][d]
+template <class G>
+int64_t gated_ws_bytes_of(int64_t B) {
+  const Chunks c = gated_chunks<G>(B);
+  return (part_floats<G>(c.grid) + c.n * G::IMG * G::IMG) * (int64_t)sizeof(float);
+}
+
+// ... | sums of dL/dx [nchunk][B][d] (want_gx)
+template <class G>
+int64_t rows_ws_bytes_of(int64_t R, int64_t B, bool want_gx) {
+  const Chunks c = rows_chunks<G>(R, B, want_gx);
+  return (part_floats<G>(c.grid) + (want_gx ? c.n * B * G::IMG : 0)) * (int64_t)sizeof(float);
+}
+
+// the nb workgroups' partial gradients -> gW1, gb1, gW2, gb2
+template <class G>
+int reduce_launch(const float* part, int nb, float* gW1, float* gb1, float* gW2, float* gb2, hipStream_t s) {
   hipLaunchKernelGGL(lenet_reduce_k, dim3((G::PW + kThreads - 1) / kThreads), dim3(kThreads), 0, s, part, nb, G::PW,
                      6 * G::T1, 16 * G::T2, gW1, gb1, gW2, gb2);
   GNF_LAUNCH_CHECK();
   return 0;
 }
 
-// chunks of samples of the gated backward: whole groups of IPB samples, enough units (row, chunk) to fill the grid
-template <class G>
-void gated_chunks(int64_t B, int64_t& gpc, int64_t& nchunk) {
-  const int64_t ngb = (B + G::IPB - 1) / G::IPB;
-  nchunk = (kBwdGridMax + G::IMG - 1) / G::IMG;
-  if (nchunk > ngb) nchunk = ngb;
-  gpc = nchunk > 0 ? (ngb + nchunk - 1) / nchunk : 1;
-  nchunk = (ngb + gpc - 1) / gpc;
-}
-
-template <class G>
-int gated_bwd_grid(int64_t B) {
-  int64_t gpc, nchunk;
-  gated_chunks<G>(B, gpc, nchunk);
-  const int64_t units = G::IMG * nchunk;
-  return (int)(units < kBwdGridMax ? units : kBwdGridMax);
-}
-
-// partial weight gradients [grid][PW] | sums of dL/dP [nchunk][d][d]
-template <class G>
-int64_t gated_ws_bytes_of(int64_t B) {
-  int64_t gpc, nchunk;
-  gated_chunks<G>(B, gpc, nchunk);
-  const int64_t nb = B > 0 ? gated_bwd_grid<G>(B) : 1;
-  return (nb * G::PW + nchunk * G::IMG * G::IMG) * (int64_t)sizeof(float);
-}
-
-template <class G>
-int gated_fwd_launch(const GatedArgs& a, const float* W1, const float* b1, const float* W2, const float* b2, float* feat,
-                     unsigned char* arg2, hipStream_t s) {
-  const int64_t units = G::IMG * ((a.B + G::IPB - 1) / G::IPB);
-  hipLaunchKernelGGL(lenet_gated_fwd_k<G>, dim3((unsigned)(units < kFwdGridMax ? units : kFwdGridMax)), dim3(kThreads), 0, s,
-                     a, W1, b1, W2, b2, feat, arg2);
-  GNF_LAUNCH_CHECK();
-  return 0;
-}
-
-template <class G>
-int rows_fwd_launch(const float* x, const float* P, int64_t ld_p, const int32_t* rows, int64_t R, const float* W1,
-                    const float* b1, const float* W2, const float* b2, float* feat, unsigned char* arg2, int variable_major,
-                    int64_t B, hipStream_t s) {
-  if (ld_p < G::IMG || (!rows && R > G::IMG)) return GNF_EINVAL;
-  if (B == 0 || R == 0) return 0;
-  const int64_t units = R * ((B + G::IPB - 1) / G::IPB);
-  const dim3 grid((unsigned)(units < kFwdGridMax ? units : kFwdGridMax));
-  if (arg2)
-    hipLaunchKernelGGL(lenet_rows_fwd_arg_k<G>, grid, dim3(kThreads), 0, s, x, P, ld_p, rows, R, B, W1, b1, W2, b2, feat, arg2,
-                       variable_major);
-  else
-    hipLaunchKernelGGL(lenet_rows_fwd_k<G>, grid, dim3(kThreads), 0, s, x, P, ld_p, rows, R, B, W1, b1, W2, b2, feat,
-                       variable_major);
-  GNF_LAUNCH_CHECK();
-  return 0;
-}
-
-// chunks of rows of the rows backward with dL/dx: whole rows, enough units (chunk, group of samples) to fill the grid,
-// nchunk <= R.  Without dL/dx a chunk is one row (the units of the forward)
-template <class G>
-void rows_chunks(int64_t R, int64_t B, bool want_gx, int64_t& rpc, int64_t& nchunk) {
-  if (!want_gx || R == 0 || B == 0) {
-    rpc = 1;
-    nchunk = (B == 0) ? 0 : R;
-    return;
-  }
-  const int64_t ngb = (B + G::IPB - 1) / G::IPB;
-  nchunk = (kBwdGridMax + ngb - 1) / ngb;
-  if (nchunk > R) nchunk = R;
-  rpc = (R + nchunk - 1) / nchunk;
-  nchunk = (R + rpc - 1) / rpc;
-}
-
-template <class G>
-int rows_bwd_grid(int64_t R, int64_t B, bool want_gx) {
-  int64_t rpc, nchunk;
-  rows_chunks<G>(R, B, want_gx, rpc, nchunk);
-  const int64_t units = nchunk * ((B + G::IPB - 1) / G::IPB);
-  return (int)(units < kBwdGridMax ? units : kBwdGridMax);
-}
-
-// partial weight gradients [grid][PW] | sums of dL/dx [nchunk][B][d] (want_gx)
-template <class G>
-int64_t rows_ws_bytes_of(int64_t R, int64_t B, bool want_gx) {
-  int64_t rpc, nchunk;
-  rows_chunks<G>(R, B, want_gx, rpc, nchunk);
-  const int64_t nb = rows_bwd_grid<G>(R, B, want_gx);
-  return ((nb > 0 ? nb : 1) * G::PW + (want_gx ? nchunk * B * G::IMG : 0)) * (int64_t)sizeof(float);
-}
-
-template <class G>
-int rows_bwd_launch(RowsArgs a, const float* W1, const float* b1, const float* W2, const float* b2,
-                    const unsigned char* arg2, const float* g_feat, float* gx, float* gW1, float* gb1, float* gW2,
-                    float* gb2, float* ws, hipStream_t s) {
-  if (a.ld_p < G::IMG || (!a.rows && a.R > G::IMG)) return GNF_EINVAL;
-  const int nb = rows_bwd_grid<G>(a.R, a.B, gx != nullptr);
-  rows_chunks<G>(a.R, a.B, gx != nullptr, a.rpc, a.nchunk);
-  a.dxp = gx ? ws + (int64_t)(nb > 0 ? nb : 1) * G::PW : nullptr;
-  if (nb > 0) {
-    const dim3 grid(nb), block(kThreads);
-    if (arg2 && gx)
-      hipLaunchKernelGGL((lenet_rows_bwd_k<G, false, true>), grid, block, 0, s, a, W1, b1, W2, b2, arg2, g_feat, ws);
-    else if (arg2)
-      hipLaunchKernelGGL((lenet_rows_bwd_k<G, false, false>), grid, block, 0, s, a, W1, b1, W2, b2, arg2, g_feat, ws);
-    else if (gx)
-      hipLaunchKernelGGL((lenet_rows_bwd_k<G, true, true>), grid, block, 0, s, a, W1, b1, W2, b2, arg2, g_feat, ws);
-    else
-      hipLaunchKernelGGL((lenet_rows_bwd_k<G, true, false>), grid, block, 0, s, a, W1, b1, W2, b2, arg2, g_feat, ws);
-    GNF_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(lenet_reduce_k, dim3((G::PW + kThreads - 1) / kThreads), dim3(kThreads), 0, s, ws, nb, G::PW,
-                     6 * G::T1, 16 * G::T2, gW1, gb1, gW2, gb2);
-  GNF_LAUNCH_CHECK();
-  const int64_t n = a.B * G::IMG;
-  if (gx && n > 0) {
-    hipLaunchKernelGGL(lenet_rows_dx_k, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a.dxp,
-                       nb > 0 ? (int)a.nchunk : 0, gx, n);
-    GNF_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-template <class G>
-int gated_bwd_launch(GatedArgs a, const float* W1, const float* b1, const float* W2, const float* b2,
-                     const unsigned char* arg2, const float* g_feat, float* gA, int accumulate, float* gW1, float* gb1,
-                     float* gW2, float* gb2, float* ws, hipStream_t s) {
-  const int nb = a.B > 0 ? gated_bwd_grid<G>(a.B) : 0;
-  gated_chunks<G>(a.B, a.gpc, a.nchunk);
-  float* dp = ws + (int64_t)(nb > 0 ? nb : 1) * G::PW;
-  a.dp = gA ? dp : nullptr;
-  if (nb > 0) {
-    if (arg2)
-      hipLaunchKernelGGL((lenet_gated_bwd_k<G, false>), dim3(nb), dim3(kThreads), 0, s, a, W1, b1, W2, b2, arg2, g_feat, ws);
-    else
-      hipLaunchKernelGGL((lenet_gated_bwd_k<G, true>), dim3(nb), dim3(kThreads), 0, s, a, W1, b1, W2, b2, arg2, g_feat, ws);
-    GNF_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(lenet_reduce_k, dim3((G::PW + kThreads - 1) / kThreads), dim3(kThreads), 0, s, ws, nb, G::PW,
-                     6 * G::T1, 16 * G::T2, gW1, gb1, gW2, gb2);
-  GNF_LAUNCH_CHECK();
-  if (gA) {
-    const int64_t dd = (int64_t)G::IMG * G::IMG;
-    hipLaunchKernelGGL(lenet_gated_dA_k, dim3((unsigned)((dd + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a.tab, dp,
-                       (int)a.nchunk, gA, accumulate, dd);
-    GNF_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-template <class G>
-int64_t ws_bytes_of(int64_t n) {
-  const int64_t nb = n > 0 ? grid_of<G>(n, kBwdGridMax) : 1;
-  return nb * G::PW * (int64_t)sizeof(float);
-}
-
 }  // namespace
 
 extern "C" {
 
-int gnf_lenet_conv_supported(int C, int H, int W, int k) { return geo_index(C, H, W, k) >= 0; }
+int gnf_lenet_conv_supported(int C, int H, int W, int k) {
+  return with_geo(C, H, W, k, [](auto) { return 0; }) == 0;
+}
 
 int64_t gnf_lenet_conv_feat(int C, int H, int W, int k) {
-  switch (geo_index(C, H, W, k)) {
-    case 0: return G0::F;
-    case 1: return G1::F;
-    case 2: return G2::F;
-    case 3: return G3::F;
-  }
-  return GNF_ESHAPE;
+  return with_geo(C, H, W, k, [](auto g) -> int64_t { return decltype(g)::F; });
 }
 
 int gnf_lenet_conv_fwd(const float* e, int64_t ld_e, int C, int H, int W, int k, const float* W1, const float* b1,
                        const float* W2, const float* b2, float* feat, unsigned char* argmax2, int64_t n_img,
                        gnf_stream_t stream) {
-  const int gi = geo_index(C, H, W, k);
-  if (gi < 0) return GNF_ESHAPE;
-  if (n_img < 0 || !W1 || !b1 || !W2 || !b2 || ((!e || !feat) && n_img > 0)) return GNF_EINVAL;
-  if (bad_f32(e) || bad_f32(W1) || bad_f32(b1) || bad_f32(W2) || bad_f32(b2) || bad_f32(feat)) return GNF_EINVAL;
-  if (n_img == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  switch (gi) {
-    case 0: return fwd_launch<G0>(e, ld_e, W1, b1, W2, b2, feat, argmax2, n_img, s);
-    case 1: return fwd_launch<G1>(e, ld_e, W1, b1, W2, b2, feat, argmax2, n_img, s);
-    case 2: return fwd_launch<G2>(e, ld_e, W1, b1, W2, b2, feat, argmax2, n_img, s);
-    default: return fwd_launch<G3>(e, ld_e, W1, b1, W2, b2, feat, argmax2, n_img, s);
-  }
+  return with_geo(C, H, W, k, [&](auto g) -> int {
+    using G = decltype(g);
+    if (n_img < 0 || any_null(W1, b1, W2, b2) || (any_null(e, feat) && n_img > 0)) return GNF_EINVAL;
+    if (any_misaligned(e, W1, b1, W2, b2, feat)) return GNF_EINVAL;
+    if (n_img == 0) return 0;
+    if (ld_e < G::IMG) return GNF_EINVAL;
+    hipLaunchKernelGGL(lenet_fwd_k<G>, dim3(grid_of(groups_of<G>(n_img), kFwdGridMax)), dim3(kThreads), 0,
+                       (hipStream_t)stream, e, ld_e, W1, b1, W2, b2, feat, argmax2, n_img);
+    GNF_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int64_t gnf_lenet_conv_bwd_ws_bytes(int C, int H, int W, int k, int64_t n_img) {
   if (n_img < 0) return GNF_EINVAL;
-  switch (geo_index(C, H, W, k)) {
-    case 0: return ws_bytes_of<G0>(n_img);
-    case 1: return ws_bytes_of<G1>(n_img);
-    case 2: return ws_bytes_of<G2>(n_img);
-    case 3: return ws_bytes_of<G3>(n_img);
-  }
-  return GNF_ESHAPE;
+  return with_geo(C, H, W, k, [&](auto g) { return ws_bytes_of<decltype(g)>(n_img); });
 }
 
 int gnf_lenet_conv_bwd(const float* e, int64_t ld_e, int C, int H, int W, int k, const float* W1, const float* b1,
                        const float* W2, const float* b2, const unsigned char* argmax2, const float* g_feat, float* ge,
                        int64_t ld_ge, float* gW1, float* gb1, float* gW2, float* gb2, void* ws, int64_t ws_bytes,
                        int64_t n_img, gnf_stream_t stream) {
-  const int gi = geo_index(C, H, W, k);
-  if (gi < 0) return GNF_ESHAPE;
-  if (n_img < 0 || !W1 || !b1 || !W2 || !b2 || !gW1 || !gb1 || !gW2 || !gb2 || !ws || ((!e || !g_feat) && n_img > 0))
-    return GNF_EINVAL;
-  if (bad_f32(e) || bad_f32(W1) || bad_f32(b1) || bad_f32(W2) || bad_f32(b2) || bad_f32(g_feat) || bad_f32(ge) ||
-      bad_f32(gW1) || bad_f32(gb1) || bad_f32(gW2) || bad_f32(gb2) || bad_f32(ws))
-    return GNF_EINVAL;
-  if (ws_bytes < gnf_lenet_conv_bwd_ws_bytes(C, H, W, k, n_img)) return GNF_EWS;
-  hipStream_t s = (hipStream_t)stream;
-  float* part = static_cast<float*>(ws);
-  switch (gi) {
-    case 0: return bwd_launch<G0>(e, ld_e, W1, b1, W2, b2, argmax2, g_feat, ge, ld_ge, gW1, gb1, gW2, gb2, part, n_img, s);
-    case 1: return bwd_launch<G1>(e, ld_e, W1, b1, W2, b2, argmax2, g_feat, ge, ld_ge, gW1, gb1, gW2, gb2, part, n_img, s);
-    case 2: return bwd_launch<G2>(e, ld_e, W1, b1, W2, b2, argmax2, g_feat, ge, ld_ge, gW1, gb1, gW2, gb2, part, n_img, s);
-    default: return bwd_launch<G3>(e, ld_e, W1, b1, W2, b2, argmax2, g_feat, ge, ld_ge, gW1, gb1, gW2, gb2, part, n_img, s);
-  }
+  return with_geo(C, H, W, k, [&](auto g) -> int {
+    using G = decltype(g);
+    if (n_img < 0 || any_null(W1, b1, W2, b2, gW1, gb1, gW2, gb2, ws) || (any_null(e, g_feat) && n_img > 0))
+      return GNF_EINVAL;
+    if (any_misaligned(e, W1, b1, W2, b2, g_feat, ge, gW1, gb1, gW2, gb2, ws)) return GNF_EINVAL;
+    if (ws_bytes < ws_bytes_of<G>(n_img)) return GNF_EWS;
+    if (n_img > 0 && (ld_e < G::IMG || (ge && ld_ge < G::IMG))) return GNF_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    float* part = static_cast<float*>(ws);
+    const int nb = grid_of(groups_of<G>(n_img), kBwdGridMax);
+    if (nb > 0) {
+      const auto kern = argmax2 ? lenet_bwd_k<G, false> : lenet_bwd_k<G, true>;       // no saved decisions: recompute
+      hipLaunchKernelGGL(kern, dim3(nb), dim3(kThreads), 0, s, e, ld_e, W1, b1, W2, b2, argmax2, g_feat, ge, ld_ge, part,
+                         n_img);
+      GNF_LAUNCH_CHECK();
+    }
+    return reduce_launch<G>(part, nb, gW1, gb1, gW2, gb2, s);
+  });
 }
 
 int gnf_lenet_gated_fwd(const float* x, const float* A, float* tab, int C, int H, int W, int k, int imp_mode, int gate_mode,
                         float h_thresh, float temperature, const float* u1, const float* u2, uint64_t seed,
                         uint64_t offset, const float* W1, const float* b1, const float* W2, const float* b2, float* feat,
                         unsigned char* argmax2, int64_t B, gnf_stream_t stream) {
-  const int gi = geo_index(C, H, W, k);
-  if (gi < 0) return GNF_ESHAPE;
-  if (B < 0 || !A || !tab || !W1 || !b1 || !W2 || !b2 || ((!x || !feat) && B > 0) || imp_mode < 0 || imp_mode > 3 ||
-      gate_mode < 0 || gate_mode > 2 || (gate_mode == 1 && u1 && !u2))
-    return GNF_EINVAL;
-  if (bad_f32(x) || bad_f32(A) || bad_f32(tab) || bad_f32(u1) || bad_f32(u2) || bad_f32(W1) || bad_f32(b1) || bad_f32(W2) ||
-      bad_f32(b2) || bad_f32(feat))
-    return GNF_EINVAL;
-  if (B == 0) return 0;
-  if (imp_mode == 0) gate_mode = 0;   // DAG:151-153: raw A, no gate
-  hipStream_t s = (hipStream_t)stream;
-  const int rc = launch_tab(A, tab, imp_mode, h_thresh, temperature, (int64_t)C * H * W, s);
-  if (rc) return rc;
-  GatedArgs a{};
-  a.x = x; a.tab = tab; a.u1 = u1; a.u2 = u2; a.seed = seed; a.offset = offset; a.gate_mode = gate_mode; a.T = temperature;
-  a.B = B;
-  switch (gi) {
-    case 0: return gated_fwd_launch<G0>(a, W1, b1, W2, b2, feat, argmax2, s);
-    case 1: return gated_fwd_launch<G1>(a, W1, b1, W2, b2, feat, argmax2, s);
-    case 2: return gated_fwd_launch<G2>(a, W1, b1, W2, b2, feat, argmax2, s);
-    default: return gated_fwd_launch<G3>(a, W1, b1, W2, b2, feat, argmax2, s);
-  }
+  return with_geo(C, H, W, k, [&](auto g) -> int {
+    using G = decltype(g);
+    if (B < 0 || any_null(A, tab, W1, b1, W2, b2) || (any_null(x, feat) && B > 0) || bad_gate(imp_mode, gate_mode, u1, u2))
+      return GNF_EINVAL;
+    if (any_misaligned(x, A, tab, u1, u2, W1, b1, W2, b2, feat)) return GNF_EINVAL;
+    if (B == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = launch_tab(A, tab, imp_mode, h_thresh, temperature, (int64_t)G::IMG, s)) return rc;
+    const GatedArgs a = gated_args(x, tab, imp_mode, gate_mode, temperature, u1, u2, seed, offset, B);
+    hipLaunchKernelGGL(lenet_gated_fwd_k<G>, dim3(grid_of(G::IMG * groups_of<G>(B), kFwdGridMax)), dim3(kThreads), 0, s, a,
+                       W1, b1, W2, b2, feat, argmax2);
+    GNF_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int gnf_lenet_rows_fwd_arg(const float* x, const float* P, int64_t ld_p, const int32_t* rows, int64_t R, int C, int H, int W,
                            int k, const float* W1, const float* b1, const float* W2, const float* b2, float* feat,
                            unsigned char* argmax2, int variable_major, int64_t B, gnf_stream_t stream) {
-  const int gi = geo_index(C, H, W, k);
-  if (gi < 0) return GNF_ESHAPE;
-  if (B < 0 || R < 0 || !P || !W1 || !b1 || !W2 || !b2 || ((!x || !feat) && B > 0 && R > 0)) return GNF_EINVAL;
-  if (bad_f32(x) || bad_f32(P) || bad_f32(rows) || bad_f32(W1) || bad_f32(b1) || bad_f32(W2) || bad_f32(b2) || bad_f32(feat))
-    return GNF_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  switch (gi) {
-    case 0: return rows_fwd_launch<G0>(x, P, ld_p, rows, R, W1, b1, W2, b2, feat, argmax2, variable_major, B, s);
-    case 1: return rows_fwd_launch<G1>(x, P, ld_p, rows, R, W1, b1, W2, b2, feat, argmax2, variable_major, B, s);
-    case 2: return rows_fwd_launch<G2>(x, P, ld_p, rows, R, W1, b1, W2, b2, feat, argmax2, variable_major, B, s);
-    default: return rows_fwd_launch<G3>(x, P, ld_p, rows, R, W1, b1, W2, b2, feat, argmax2, variable_major, B, s);
-  }
+  return with_geo(C, H, W, k, [&](auto g) -> int {
+    using G = decltype(g);
+    if (B < 0 || R < 0 || any_null(P, W1, b1, W2, b2) || (any_null(x, feat) && B > 0 && R > 0)) return GNF_EINVAL;
+    if (any_misaligned(x, P, rows, W1, b1, W2, b2, feat)) return GNF_EINVAL;
+    if (ld_p < G::IMG || (!rows && R > G::IMG)) return GNF_EINVAL;
+    if (B == 0 || R == 0) return 0;
+    const dim3 grid(grid_of(R * groups_of<G>(B), kFwdGridMax));
+    hipStream_t s = (hipStream_t)stream;
+    if (argmax2)
+      hipLaunchKernelGGL(lenet_rows_fwd_arg_k<G>, grid, dim3(kThreads), 0, s, x, P, ld_p, rows, R, B, W1, b1, W2, b2, feat,
+                         argmax2, variable_major);
+    else
+      hipLaunchKernelGGL(lenet_rows_fwd_k<G>, grid, dim3(kThreads), 0, s, x, P, ld_p, rows, R, B, W1, b1, W2, b2, feat,
+                         variable_major);
+    GNF_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int gnf_lenet_rows_fwd(const float* x, const float* P, int64_t ld_p, const int32_t* rows, int64_t R, int C, int H, int W,
@@ -1190,50 +1069,46 @@ int gnf_lenet_rows_fwd(const float* x, const float* P, int64_t ld_p, const int32
 
 int64_t gnf_lenet_rows_bwd_ws_bytes(int C, int H, int W, int k, int64_t R, int64_t B, int want_gx) {
   if (R < 0 || B < 0) return GNF_EINVAL;
-  switch (geo_index(C, H, W, k)) {
-    case 0: return rows_ws_bytes_of<G0>(R, B, want_gx != 0);
-    case 1: return rows_ws_bytes_of<G1>(R, B, want_gx != 0);
-    case 2: return rows_ws_bytes_of<G2>(R, B, want_gx != 0);
-    case 3: return rows_ws_bytes_of<G3>(R, B, want_gx != 0);
-  }
-  return GNF_ESHAPE;
+  return with_geo(C, H, W, k, [&](auto g) { return rows_ws_bytes_of<decltype(g)>(R, B, want_gx != 0); });
 }
 
 int gnf_lenet_rows_bwd(const float* x, const float* P, int64_t ld_p, const int32_t* rows, int64_t R, int C, int H, int W,
                        int k, const float* W1, const float* b1, const float* W2, const float* b2,
                        const unsigned char* argmax2, const float* g_feat, int variable_major, float* gx, float* gW1,
                        float* gb1, float* gW2, float* gb2, void* ws, int64_t ws_bytes, int64_t B, gnf_stream_t stream) {
-  const int gi = geo_index(C, H, W, k);
-  if (gi < 0) return GNF_ESHAPE;
-  if (B < 0 || R < 0 || !P || !W1 || !b1 || !W2 || !b2 || !gW1 || !gb1 || !gW2 || !gb2 || !ws ||
-      ((!x || !g_feat) && B > 0 && R > 0))
-    return GNF_EINVAL;
-  if (bad_f32(x) || bad_f32(P) || bad_f32(rows) || bad_f32(W1) || bad_f32(b1) || bad_f32(W2) || bad_f32(b2) ||
-      bad_f32(g_feat) || bad_f32(gx) || bad_f32(gW1) || bad_f32(gb1) || bad_f32(gW2) || bad_f32(gb2) || bad_f32(ws))
-    return GNF_EINVAL;
-  if (ld_p < (int64_t)C * H * W || (!rows && R > (int64_t)C * H * W)) return GNF_EINVAL;
-  if (ws_bytes < gnf_lenet_rows_bwd_ws_bytes(C, H, W, k, R, B, gx != nullptr)) return GNF_EWS;
-  hipStream_t s = (hipStream_t)stream;
-  RowsArgs a{};
-  a.x = x; a.P = P; a.ld_p = ld_p; a.rows = rows; a.R = R; a.B = B; a.variable_major = variable_major;
-  float* w = static_cast<float*>(ws);
-  switch (gi) {
-    case 0: return rows_bwd_launch<G0>(a, W1, b1, W2, b2, argmax2, g_feat, gx, gW1, gb1, gW2, gb2, w, s);
-    case 1: return rows_bwd_launch<G1>(a, W1, b1, W2, b2, argmax2, g_feat, gx, gW1, gb1, gW2, gb2, w, s);
-    case 2: return rows_bwd_launch<G2>(a, W1, b1, W2, b2, argmax2, g_feat, gx, gW1, gb1, gW2, gb2, w, s);
-    default: return rows_bwd_launch<G3>(a, W1, b1, W2, b2, argmax2, g_feat, gx, gW1, gb1, gW2, gb2, w, s);
-  }
+  return with_geo(C, H, W, k, [&](auto g) -> int {
+    using G = decltype(g);
+    if (B < 0 || R < 0 || any_null(P, W1, b1, W2, b2, gW1, gb1, gW2, gb2, ws) || (any_null(x, g_feat) && B > 0 && R > 0))
+      return GNF_EINVAL;
+    if (any_misaligned(x, P, rows, W1, b1, W2, b2, g_feat, gx, gW1, gb1, gW2, gb2, ws)) return GNF_EINVAL;
+    if (ld_p < G::IMG || (!rows && R > G::IMG)) return GNF_EINVAL;
+    if (ws_bytes < rows_ws_bytes_of<G>(R, B, gx != nullptr)) return GNF_EWS;
+    hipStream_t s = (hipStream_t)stream;
+    float* part = static_cast<float*>(ws);
+    const Chunks c = rows_chunks<G>(R, B, gx != nullptr);
+    RowsArgs a{};
+    a.x = x; a.P = P; a.ld_p = ld_p; a.rows = rows; a.R = R; a.B = B; a.variable_major = variable_major;
+    a.dxp = gx ? part + part_floats<G>(c.grid) : nullptr; a.rpc = c.per; a.nchunk = c.n;
+    if (c.grid > 0) {
+      const auto kern = argmax2 ? (gx ? lenet_rows_bwd_k<G, false, true> : lenet_rows_bwd_k<G, false, false>)
+                                : (gx ? lenet_rows_bwd_k<G, true, true> : lenet_rows_bwd_k<G, true, false>);
+      hipLaunchKernelGGL(kern, dim3(c.grid), dim3(kThreads), 0, s, a, W1, b1, W2, b2, argmax2, g_feat, part);
+      GNF_LAUNCH_CHECK();
+    }
+    if (const int rc = reduce_launch<G>(part, c.grid, gW1, gb1, gW2, gb2, s)) return rc;
+    const int64_t n = B * G::IMG;
+    if (gx && n > 0) {
+      hipLaunchKernelGGL(lenet_rows_dx_k, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a.dxp,
+                         c.grid > 0 ? (int)c.n : 0, gx, n);
+      GNF_LAUNCH_CHECK();
+    }
+    return 0;
+  });
 }
 
 int64_t gnf_lenet_gated_bwd_ws_bytes(int C, int H, int W, int k, int64_t B) {
   if (B < 0) return GNF_EINVAL;
-  switch (geo_index(C, H, W, k)) {
-    case 0: return gated_ws_bytes_of<G0>(B);
-    case 1: return gated_ws_bytes_of<G1>(B);
-    case 2: return gated_ws_bytes_of<G2>(B);
-    case 3: return gated_ws_bytes_of<G3>(B);
-  }
-  return GNF_ESHAPE;
+  return with_geo(C, H, W, k, [&](auto g) { return gated_ws_bytes_of<decltype(g)>(B); });
 }
 
 int gnf_lenet_gated_bwd(const float* x, const float* tab, int C, int H, int W, int k, int imp_mode, int gate_mode,
@@ -1241,27 +1116,35 @@ int gnf_lenet_gated_bwd(const float* x, const float* tab, int C, int H, int W, i
                         const float* W1, const float* b1, const float* W2, const float* b2, const unsigned char* argmax2,
                         const float* g_feat, float* gA, int accumulate, float* gW1, float* gb1, float* gW2, float* gb2,
                         void* ws, int64_t ws_bytes, int64_t B, gnf_stream_t stream) {
-  const int gi = geo_index(C, H, W, k);
-  if (gi < 0) return GNF_ESHAPE;
-  if (B < 0 || !W1 || !b1 || !W2 || !b2 || !gW1 || !gb1 || !gW2 || !gb2 || !ws || ((!x || !tab || !g_feat) && B > 0) ||
-      imp_mode < 0 || imp_mode > 3 || gate_mode < 0 || gate_mode > 2 || (gate_mode == 1 && u1 && !u2))
-    return GNF_EINVAL;
-  if (bad_f32(x) || bad_f32(tab) || bad_f32(u1) || bad_f32(u2) || bad_f32(W1) || bad_f32(b1) || bad_f32(W2) || bad_f32(b2) ||
-      bad_f32(g_feat) || bad_f32(gA) || bad_f32(gW1) || bad_f32(gb1) || bad_f32(gW2) || bad_f32(gb2) || bad_f32(ws))
-    return GNF_EINVAL;
-  if (ws_bytes < gnf_lenet_gated_bwd_ws_bytes(C, H, W, k, B)) return GNF_EWS;
-  if (imp_mode == 0) gate_mode = 0;
-  hipStream_t s = (hipStream_t)stream;
-  GatedArgs a{};
-  a.x = x; a.tab = tab; a.u1 = u1; a.u2 = u2; a.seed = seed; a.offset = offset; a.gate_mode = gate_mode; a.T = temperature;
-  a.B = B;
-  float* w = static_cast<float*>(ws);
-  switch (gi) {
-    case 0: return gated_bwd_launch<G0>(a, W1, b1, W2, b2, argmax2, g_feat, gA, accumulate, gW1, gb1, gW2, gb2, w, s);
-    case 1: return gated_bwd_launch<G1>(a, W1, b1, W2, b2, argmax2, g_feat, gA, accumulate, gW1, gb1, gW2, gb2, w, s);
-    case 2: return gated_bwd_launch<G2>(a, W1, b1, W2, b2, argmax2, g_feat, gA, accumulate, gW1, gb1, gW2, gb2, w, s);
-    default: return gated_bwd_launch<G3>(a, W1, b1, W2, b2, argmax2, g_feat, gA, accumulate, gW1, gb1, gW2, gb2, w, s);
-  }
+  return with_geo(C, H, W, k, [&](auto g) -> int {
+    using G = decltype(g);
+    if (B < 0 || any_null(W1, b1, W2, b2, gW1, gb1, gW2, gb2, ws) || (any_null(x, tab, g_feat) && B > 0) ||
+        bad_gate(imp_mode, gate_mode, u1, u2))
+      return GNF_EINVAL;
+    if (any_misaligned(x, tab, u1, u2, W1, b1, W2, b2, g_feat, gA, gW1, gb1, gW2, gb2, ws)) return GNF_EINVAL;
+    if (ws_bytes < gated_ws_bytes_of<G>(B)) return GNF_EWS;
+    hipStream_t s = (hipStream_t)stream;
+    float* part = static_cast<float*>(ws);
+    const Chunks c = gated_chunks<G>(B);
+    float* dp = part + part_floats<G>(c.grid);
+    GatedArgs a = gated_args(x, tab, imp_mode, gate_mode, temperature, u1, u2, seed, offset, B);
+    a.dp = gA ? dp : nullptr;
+    a.gpc = c.per;
+    a.nchunk = c.n;
+    if (c.grid > 0) {
+      const auto kern = argmax2 ? lenet_gated_bwd_k<G, false> : lenet_gated_bwd_k<G, true>;
+      hipLaunchKernelGGL(kern, dim3(c.grid), dim3(kThreads), 0, s, a, W1, b1, W2, b2, argmax2, g_feat, part);
+      GNF_LAUNCH_CHECK();
+    }
+    if (const int rc = reduce_launch<G>(part, c.grid, gW1, gb1, gW2, gb2, s)) return rc;
+    if (gA) {
+      const int64_t dd = (int64_t)G::IMG * G::IMG;
+      hipLaunchKernelGGL(lenet_gated_dA_k, dim3((unsigned)((dd + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, tab, dp,
+                         (int)c.n, gA, accumulate, dd);
+      GNF_LAUNCH_CHECK();
+    }
+    return 0;
+  });
 }
 
 }  // extern "C"

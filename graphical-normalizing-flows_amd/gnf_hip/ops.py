@@ -567,6 +567,16 @@ def lenet_conv_supported(size_img, k):
     return bool(abi.load().gnf_lenet_conv_supported(int(c), int(h), int(w), int(k)))
 
 
+def _keep_argmax(ctx, grad_mode):
+    """does the forward of a LeNet front keep the second pool's decisions?  Only when a backward will come (grad mode on,
+    an input that needs a gradient), and not with GNF_LENET_SAVE_ARGMAX=0 (the backward then recomputes conv2)"""
+    return bool(grad_mode) and any(ctx.needs_input_grad) and os.environ.get("GNF_LENET_SAVE_ARGMAX", "1") != "0"
+
+
+def _contiguous(*tensors):
+    return tuple(t.contiguous() for t in tensors)
+
+
 class LenetConvFn(torch.autograd.Function):
     """flatten(pool2(relu(conv_k(6->16)(pool2(relu(conv_k(C->6)(e))))))) on rows e [n, C*H*W] (reference models/MLP.py:66-68),
     fused in LDS (csrc/gnf_lenetcnn.hip).  The forward keeps the second pool's decisions (one byte per feature) when a
@@ -579,10 +589,10 @@ class LenetConvFn(torch.autograd.Function):
         if e.stride(-1) != 1 or e.stride(0) < c * h * w:
             e = e.contiguous()
         n = e.shape[0]
-        W1c, b1c, W2c, b2c = W1.contiguous(), b1.contiguous(), W2.contiguous(), b2.contiguous()
+        W1c, b1c, W2c, b2c = _contiguous(W1, b1, W2, b2)
         F = int(abi.load().gnf_lenet_conv_feat(c, h, w, k))
         feat = _empty((n, F), e)
-        keep = bool(grad_mode) and any(ctx.needs_input_grad) and os.environ.get("GNF_LENET_SAVE_ARGMAX", "1") != "0"
+        keep = _keep_argmax(ctx, grad_mode)
         arg = torch.empty((n, F), dtype=torch.uint8, device=e.device) if keep else None
         call("gnf_lenet_conv_fwd", ptr(e), e.stride(0), c, h, w, k, ptr(W1c), ptr(b1c), ptr(W2c), ptr(b2c), ptr(feat),
              abi.rawptr(arg) if keep else None, n, stream())
@@ -617,13 +627,8 @@ def lenet_rows(x, P, rows32, W1, b1, W2, b2, size_img, k, variable_major=False):
     lenet_conv on that product.  Evaluation only: a plain function, no autograd node."""
     if torch.is_grad_enabled() and any(t.requires_grad for t in (x, P, W1, b1, W2, b2)):
         raise abi.GnfError("lenet_rows has no backward: call it under torch.no_grad() or on operands without requires_grad")
-    x, P, rows32, R, geo, F = _rows_operands(x, P, rows32, size_img, k)
-    B = x.shape[0]
-    feat = _empty((R, B, F) if variable_major else (B, R, F), x)
-    call("gnf_lenet_rows_fwd", ptr(x), ptr(P), P.stride(0), abi.rawptr(rows32) if rows32 is not None else None, R, *geo,
-         ptr(W1.contiguous()), ptr(b1.contiguous()), ptr(W2.contiguous()), ptr(b2.contiguous()), ptr(feat),
-         int(bool(variable_major)), B, stream())
-    return feat
+    return _rows_forward(x, P, rows32, W1, b1, W2, b2, size_img, k, variable_major, False,
+                         profile_as="gnf_lenet_rows_fwd")[0]
 
 
 def _rows_operands(x, P, rows32, size_img, k):
@@ -649,6 +654,19 @@ def _rows_operands(x, P, rows32, size_img, k):
     return x, P, rows32, R, (c, h, w, k), F
 
 
+def _rows_forward(x, P, rows32, W1, b1, W2, b2, size_img, k, variable_major, keep, profile_as=None):
+    """the gnf_lenet_rows_fwd_arg call of lenet_rows and LenetRowsFn: (feat, the second pool's decisions or None when not
+    keep, the operands as the kernel took them, (R, geometry, variable_major))"""
+    x, P, rows32, R, geo, F = _rows_operands(x, P, rows32, size_img, k)
+    B, vm = x.shape[0], int(bool(variable_major))
+    params = _contiguous(W1, b1, W2, b2)
+    feat = _empty((R, B, F) if vm else (B, R, F), x)
+    arg = torch.empty((B * R, F), dtype=torch.uint8, device=x.device) if keep else None
+    call("gnf_lenet_rows_fwd_arg", ptr(x), ptr(P), P.stride(0), abi.rawptr(rows32) if rows32 is not None else None, R, *geo,
+         *(ptr(t) for t in params), ptr(feat), abi.rawptr(arg) if keep else None, vm, B, stream(), profile_as=profile_as)
+    return feat, arg, (x, P, rows32, *params), (R, geo, vm)
+
+
 class LenetRowsFn(torch.autograd.Function):
     """lenet_rows with a backward, for training behind a FROZEN deterministic gate (csrc/gnf_lenetcnn.hip,
     gnf_lenet_rows_fwd_arg / gnf_lenet_rows_bwd): differentiable w.r.t. the four conv parameters and, when it asks for one,
@@ -657,17 +675,9 @@ class LenetRowsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, P, rows32, W1, b1, W2, b2, size_img, k, variable_major, grad_mode=None):
-        x, P, rows32, R, geo, F = _rows_operands(x, P, rows32, size_img, k)
-        B = x.shape[0]
-        W1c, b1c, W2c, b2c = W1.contiguous(), b1.contiguous(), W2.contiguous(), b2.contiguous()
-        feat = _empty((R, B, F) if variable_major else (B, R, F), x)
-        keep = bool(grad_mode) and any(ctx.needs_input_grad) and os.environ.get("GNF_LENET_SAVE_ARGMAX", "1") != "0"
-        arg = torch.empty((B * R, F), dtype=torch.uint8, device=x.device) if keep else None
-        rp = abi.rawptr(rows32) if rows32 is not None else None
-        call("gnf_lenet_rows_fwd_arg", ptr(x), ptr(P), P.stride(0), rp, R, *geo, ptr(W1c), ptr(b1c), ptr(W2c), ptr(b2c),
-             ptr(feat), abi.rawptr(arg) if keep else None, int(bool(variable_major)), B, stream())
-        ctx.save_for_backward(x, P, rows32, W1c, b1c, W2c, b2c)
-        ctx.arg, ctx.cfg = arg, (R, geo, int(bool(variable_major)))
+        feat, ctx.arg, saved, ctx.cfg = _rows_forward(x, P, rows32, W1, b1, W2, b2, size_img, k, variable_major,
+                                                      _keep_argmax(ctx, grad_mode))
+        ctx.save_for_backward(*saved)
         return feat
 
     @staticmethod
@@ -1013,13 +1023,13 @@ class DagLenetFrontFn(torch.autograd.Function):
         u1 = u1.contiguous() if u1 is not None else None
         u2 = u2.contiguous() if u2 is not None else None
         lib = abi.load()
-        W1c, b1c, W2c, b2c = W1.contiguous(), b1.contiguous(), W2.contiguous(), b2.contiguous()
+        W1c, b1c, W2c, b2c = _contiguous(W1, b1, W2, b2)
         F = int(lib.gnf_lenet_conv_feat(c, h, w, k))
         if F < 0:
             abi.check(F, "gnf_lenet_conv_feat")
         tab = torch.empty(max(int(lib.gnf_dag_gate_fwd_ws_bytes(d)) // 4, 1), dtype=torch.float32, device=x.device)
         feat = _empty((B * d, F), x)
-        keep = bool(grad_mode) and any(ctx.needs_input_grad) and os.environ.get("GNF_LENET_SAVE_ARGMAX", "1") != "0"
+        keep = _keep_argmax(ctx, grad_mode)
         arg = torch.empty((B * d, F), dtype=torch.uint8, device=x.device) if keep else None
         call("gnf_lenet_gated_fwd", ptr(x), ptr(A), ptr(tab), c, h, w, k, imp_mode, gate_mode, float(h_thresh),
              float(temperature), ptr(u1), ptr(u2), seed, offset, ptr(W1c), ptr(b1c), ptr(W2c), ptr(b2c), ptr(feat),

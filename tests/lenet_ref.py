@@ -2,7 +2,7 @@
 dtype the operands have (fp32 against the reference fixture, fp64 as the arbiter of the kernels), plus the fp64 finder of
 knife-edge decisions: images in which a ReLU gate or a pool argmax of the front is decided within fp32 roundoff of a tie,
 where two correct fp32 evaluations may legitimately differ (tests/conftest.py: conv_front_knife_images is the MNISTCNN
-counterpart)."""
+counterpart).  Also the helpers the LeNet front's GPU test files share."""
 import torch
 import torch.nn.functional as F
 
@@ -13,6 +13,36 @@ GEOMETRIES = (((3, 32, 32), 5, (400, 128, 84)),
               ((1, 32, 32), 3, (576, 128, 32)),
               ((1, 16, 16), 3, (64, 32, 32)),
               ((1, 8, 8), 2, (16, 32, 32)))
+DEV = "cuda:0"
+
+
+def cu(t):
+    return t.to(DEV)
+
+
+def assert_grad(a, b, what):
+    from conftest import assert_close, rel_err      # here, not at the top: golden/make_golden_cifar.py imports this file outside pytest
+    b = torch.as_tensor(b)
+    assert rel_err(a.detach().cpu(), b.detach().cpu()) < 1e-4, (what, rel_err(a.detach().cpu(), b.detach().cpu()))
+    assert_close(a, b, rtol=1e-4, atol=1e-6 * float(b.detach().abs().max()), what=what)
+
+
+def geo_args(gi):
+    size_img, k, _ = GEOMETRIES[gi]
+    return size_img[0], size_img[1], size_img[2], k
+
+
+def graph_nodes(t):
+    """names of the autograd nodes behind t"""
+    seen, names, stack = set(), set(), [t.grad_fn]
+    while stack:
+        f = stack.pop()
+        if f is None or f in seen:
+            continue
+        seen.add(f)
+        names.add(type(f).__name__)
+        stack += [n for n, _ in f.next_functions]
+    return names
 
 
 def front(e, W1, b1, W2, b2, size_img):

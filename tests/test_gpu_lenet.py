@@ -12,24 +12,14 @@ import ctypes
 import pytest
 import torch
 
-from conftest import assert_close, assert_fwd, load_golden, rel_err
+from conftest import assert_fwd, load_golden, rel_err
 import lenet_ref
+from lenet_ref import DEV, assert_grad, cu, geo_args
 import misaligned
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 GEOS = lenet_ref.GEOMETRIES
 FEAT = (400, 576, 64, 16)
-
-
-def cu(t):
-    return t.to(DEV)
-
-
-def assert_grad(a, b, what):
-    b = torch.as_tensor(b)
-    assert rel_err(a.detach().cpu(), b.detach().cpu()) < 1e-4, (what, rel_err(a.detach().cpu(), b.detach().cpu()))
-    assert_close(a, b, rtol=1e-4, atol=1e-6 * float(b.detach().abs().max()), what=what)
 
 
 def conv_params(gi, seed):
@@ -38,11 +28,6 @@ def conv_params(gi, seed):
     torch.manual_seed(seed)
     c1, c2 = torch.nn.Conv2d(size_img[0], 6, k), torch.nn.Conv2d(6, 16, k)
     return [t.detach().clone() for t in (c1.weight, c1.bias, c2.weight, c2.bias)]
-
-
-def geo_args(gi):
-    size_img, k, _ = GEOS[gi]
-    return size_img[0], size_img[1], size_img[2], k
 
 
 def raw_fwd(e, P, gi, save=True):
@@ -172,6 +157,36 @@ def test_row_offsets_beyond_4gb():
     assert torch.equal(ge[rows], ge[rows % blk])
     del e, ge, gf, feat
     torch.cuda.empty_cache()
+
+
+def test_grid_stride_over_groups_of_several_images():
+    """(1,8,8,2) holds 28 images per group; n = 28 * 1024 + 5 is more groups than either grid has workgroups (1024
+    forward, 512 backward), the last of them partly filled, so every workgroup strides on to a second or third group.
+    feat, the pool decisions and ge are per-image quantities: the bits of the same entry points on consecutive slices of
+    at most 28 * 512 images, which no workgroup strides over.  The parameter gradients are sums over the images in another
+    order: the fp64 sum of the slices' gradients, under assert_grad."""
+    gi, ipb = 3, 28
+    n, step = ipb * 1024 + 5, ipb * 512
+    P = [cu(p) for p in conv_params(gi, 35)]
+    gen = torch.Generator().manual_seed(36)
+    e, gf = cu(torch.randn(n, 64, generator=gen)), cu(torch.randn(n, FEAT[gi], generator=gen))
+    feat, arg = raw_fwd(e, P, gi)
+    res = raw_bwd(e, P, arg, gf, gi)
+    feat_b, arg_b = raw_fwd(e, P, gi)                               # same operands, same bits
+    assert torch.equal(feat, feat_b) and torch.equal(arg, arg_b)
+    for a, b in zip(res, raw_bwd(e, P, arg, gf, gi)):
+        assert torch.equal(a, b)
+    sums = [torch.zeros_like(p, dtype=torch.float64) for p in P]
+    for i0 in range(0, n, step):
+        sl = slice(i0, min(i0 + step, n))
+        feat_s, arg_s = raw_fwd(e[sl], P, gi)
+        assert torch.equal(feat[sl], feat_s) and torch.equal(arg[sl], arg_s)
+        ge_s, *gP_s = raw_bwd(e[sl], P, arg_s, gf[sl], gi)
+        assert torch.equal(res[0][sl], ge_s)
+        for acc, g in zip(sums, gP_s):
+            acc += g.double()
+    for got, want, what in zip(res[1:], sums, ("gW1", "gb1", "gW2", "gb2")):
+        assert_grad(got, want, what)
 
 
 # ------------------------------------------------------------------------------------------- 5. edge cases

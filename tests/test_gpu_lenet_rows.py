@@ -14,10 +14,10 @@ import torch
 
 from conftest import assert_fwd, rel_err
 import lenet_ref
+from lenet_ref import DEV, cu, geo_args
 import misaligned
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 GEOS = lenet_ref.GEOMETRIES
 FEAT = (400, 576, 64, 16)
 DIMS = tuple(s[0] * s[1] * s[2] for s, _, _ in GEOS)          # 3072, 1024, 256, 64
@@ -26,20 +26,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BATCHES = {3: (1, 30), 2: (1, 7), 1: (1, 2), 0: (1, 2)}
 
 
-def cu(t):
-    return t.to(DEV)
-
-
 def conv_params(gi, seed):
     size_img, k, _ = GEOS[gi]
     torch.manual_seed(seed)
     c1, c2 = torch.nn.Conv2d(size_img[0], 6, k), torch.nn.Conv2d(6, 16, k)
     return [cu(t.detach().clone()) for t in (c1.weight, c1.bias, c2.weight, c2.bias)]
-
-
-def geo_args(gi):
-    size_img, k, _ = GEOS[gi]
-    return size_img[0], size_img[1], size_img[2], k
 
 
 def row_sets(d):
@@ -173,7 +164,6 @@ def test_conditioner_rows_against_fp64():
         h0 = lenet_ref.cifar10cnn(e.double(), p64, size_img).view(B, 9, 2)
     assert h.shape == (B, 9, 2)
     assert_fwd(h, h0, what="h")
-
 
 
 # ------------------------------------------------------------------------------------------- 4. conditioner parity

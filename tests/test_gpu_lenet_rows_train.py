@@ -15,45 +15,17 @@ import os
 import pytest
 import torch
 
-from conftest import assert_close, assert_fwd, rel_err
+from conftest import assert_fwd, rel_err
 import lenet_ref
+from lenet_ref import DEV, assert_grad, cu, geo_args, graph_nodes
 import misaligned
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 GEOS = lenet_ref.GEOMETRIES
 FEAT = (400, 576, 64, 16)
 DIMS = tuple(s[0] * s[1] * s[2] for s, _, _ in GEOS)          # 3072, 1024, 256, 64
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COMPOSED = {"DagGateFnBackward", "LenetConvFnBackward"}
-
-
-def cu(t):
-    return t.to(DEV)
-
-
-def assert_grad(a, b, what):
-    b = torch.as_tensor(b)
-    assert rel_err(a.detach().cpu(), b.detach().cpu()) < 1e-4, (what, rel_err(a.detach().cpu(), b.detach().cpu()))
-    assert_close(a, b, rtol=1e-4, atol=1e-6 * float(b.detach().abs().max()), what=what)
-
-
-def geo_args(gi):
-    size_img, k, _ = GEOS[gi]
-    return size_img[0], size_img[1], size_img[2], k
-
-
-def graph_nodes(t):
-    """names of the autograd nodes behind t"""
-    seen, names, stack = set(), set(), [t.grad_fn]
-    while stack:
-        f = stack.pop()
-        if f is None or f in seen:
-            continue
-        seen.add(f)
-        names.add(type(f).__name__)
-        stack += [n for n, _ in f.next_functions]
-    return names
 
 
 def row_sets(d):

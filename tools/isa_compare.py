@@ -4,7 +4,7 @@
     python tools/isa_compare.py <tree A> <tree B> [unit.hip ...]
 
 Every unit of gnf_hip/build.py's SOURCES is compiled to device assembly with that tree's own FLAGS / EXTRA_FLAGS; comments
-and the per-compile __hip_cuid_ symbol are dropped.  Per kernel: `same`, or the resources and instruction count of both sides.
+and the per-compile __hip_cuid_ symbol are dropped, the function ordinal in local labels is removed.  Per kernel: `same`, or the resources and instruction count of both sides.
 Exit status 1 if anything differs."""
 import os
 import re
@@ -16,6 +16,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 KEYS = ["vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size",
         "group_segment_fixed_size"]
+# local symbols carry the function's ordinal in its unit (.LBB41_3, .Lfunc_end41): a function that only moved is the same
+LOCAL = re.compile(r"\.L(BB|JTI|CPI|func_begin|func_end)\d+")
 
 
 def device_asm(tree, unit, tmp):
@@ -27,7 +29,7 @@ def device_asm(tree, unit, tmp):
                    ["--offload-device-only", "-S", os.path.join(b["CSRC"], unit), "-o", out], check=True)
     lines = []
     for ln in open(out):
-        ln = ln.split(";")[0].rstrip()
+        ln = LOCAL.sub(r".L\1", ln.split(";")[0].rstrip())
         if ln.strip() and "__hip_cuid_" not in ln:
             lines.append(ln)
     return lines
