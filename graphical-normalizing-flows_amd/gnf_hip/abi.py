@@ -176,6 +176,8 @@ SIGNATURES = {
                               c_stream]),
     "gnf_adam_step_dev": (c_int, [c_f, c_f, c_f, c_f, c_i64, c_double, c_double, c_double, c_double, c_double, c_double,
                                   ctypes.c_void_p, c_int, c_stream]),
+    "gnf_image_prep": (c_int, [ctypes.c_void_p, c_i64, ctypes.c_void_p, c_int, ctypes.c_void_p, c_int, c_int, c_int, c_f, c_u64,
+                               c_u64, c_float, c_f, c_f, c_i64, c_stream]),
     "gnf_probe_mfma_f32": (c_i64, [c_f, c_int, c_int, c_stream]),
     "gnf_probe_copy": (c_int, [c_f, c_f, c_i64, c_stream]),
     "gnf_probe_empty": (c_int, [c_i64, c_int, c_stream]),

@@ -138,6 +138,13 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
+// 23-bit uniform centred in its cell: never exactly 0 or 1.  (With 24 bits the + .5f is a rounding tie for words >= 2^23 and
+// rounds to even: 16777215.5 -> 16777216, i.e. V = 1.0f about four times per cfg4 step and V / (1 - V) = inf in the
+// single-uniform Gumbel ratio.  With 23 bits k + .5 is exactly representable for every k < 2^23.)
+__device__ __forceinline__ float u01_open(uint32_t w) {
+  return ((float)(w >> 9) + .5f) * (1.0f / 8388608.0f);
+}
+
 // 24-bit uniform in [0,1), the resolution torch.rand has for fp32.
 __device__ __forceinline__ float u01_24(uint32_t r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }
 

@@ -78,13 +78,7 @@ inline int launch_tab(const float* A, float* tab, int imp_mode, float h_thresh, 
 // gate_mode 1: the ratio is handed on as numerator v / denominator w (the gate then needs ONE division, see gumbel_gate)
 struct Draw4 { float v[4]; float w[4]; };
 
-// 23-bit uniform centred in its cell: never exactly 0 or 1.  (With 24 bits the + .5f is a rounding tie for words >= 2^23 and
-// rounds to even: 16777215.5 -> 16777216, i.e. V = 1.0f about four times per cfg4 step and V / (1 - V) = inf in the
-// single-uniform Gumbel ratio.  With 23 bits k + .5 is exactly representable for every k < 2^23.)
-__device__ __forceinline__ float u01_open(uint32_t w) {
-  return ((float)(w >> 9) + .5f) * (1.0f / 8388608.0f);
-}
-
+// (u01_open, the uniform of a Philox word: gnf_common.h, shared with gnf_image_prep.hip)
 __device__ __forceinline__ Draw4 draw4(int gate_mode, const float* u1, const float* u2, uint64_t seed, uint64_t offset,
                                        int64_t row, int64_t jq, int64_t d) {
   Draw4 n;

@@ -1273,6 +1273,46 @@ def module_monotonic_inverse(z, h, module, nb_steps):
     return (lo + hi) * .5
 
 
+# ----------------------------------------------------------------------------- image batch preparation
+def image_prep(data_u8, rows, flip, u, seed, offset, alpha, size_img, want_bpp):
+    """One launch of gnf_image_prep (csrc/gnf_image_prep.hip): rows of the uint8 data set [n, d] -> (x [B, d], bpp_term [B] or
+    None), x = logit(alpha + (1 - 2 alpha) (pixel + u) / 256) and bpp_term = sum_j log2 y + log2 (1 - y).
+    rows: int32 device indices [B] (any order, repeats allowed; clamped into the data set by the kernel), or None for every
+    row of data_u8 in order.  flip: None / False (no flip), True (one Philox coin per output row), or a uint8 / bool mask [B].
+    u: explicit uniforms [B, d] (parity tests) or None for Philox keyed by (seed, offset); the layout: include/gnf_hip.h.
+    size_img = (C, H, W), d = C*H*W.  The inputs are data: no autograd node."""
+    c, h, w = (int(v) for v in size_img)
+    if data_u8.dtype != torch.uint8 or data_u8.dim() != 2 or data_u8.shape[1] != c * h * w:
+        raise abi.GnfError("image_prep needs a uint8 tensor [n, %d]: got %s %s" % (c * h * w, data_u8.dtype, tuple(data_u8.shape)))
+    if not data_u8.is_contiguous():
+        data_u8 = data_u8.contiguous()
+    n, d = data_u8.shape
+    if rows is None:
+        B = n
+    else:
+        if rows.dtype != torch.int32 or rows.device != data_u8.device:
+            raise abi.GnfError("image_prep: rows must be an int32 tensor on the device of the data")
+        rows = rows.contiguous()
+        B = rows.numel()
+    mode, mask = 0, None
+    if flip is True:
+        mode = 2
+    elif flip is not None and flip is not False:
+        if flip.device != data_u8.device or flip.dtype not in (torch.uint8, torch.bool) or flip.numel() != B:
+            raise abi.GnfError("image_prep: the flip mask must be %d uint8 / bool entries on the device of the data" % B)
+        mode, mask = 1, flip.contiguous().view(torch.uint8) if flip.dtype == torch.bool else flip.contiguous()
+    if u is not None:
+        if tuple(u.shape) != (B, d):
+            raise abi.GnfError("image_prep: explicit uniforms must be [%d, %d]" % (B, d))
+        u = u.contiguous()
+    x = torch.empty((B, d), dtype=torch.float32, device=data_u8.device)
+    term = torch.empty((B,), dtype=torch.float32, device=data_u8.device) if want_bpp else None
+    call("gnf_image_prep", abi.rawptr(data_u8) if n else None, n, abi.rawptr(rows) if rows is not None and B else None, mode,
+         abi.rawptr(mask) if mask is not None and B else None, c, h, w, ptr(u), int(seed), int(offset), float(alpha), ptr(x),
+         ptr(term), B, stream())
+    return x, term
+
+
 # ----------------------------------------------------------------------------- Adam on a flat buffer
 def adam_step(p, g, m, v, step, lr=1e-3, betas=(.9, .999), eps=1e-8, weight_decay=0., grad_scale=1.):
     call("gnf_adam_step", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, betas[0], betas[1], eps, weight_decay,

@@ -1,10 +1,12 @@
 """Image density-estimation driver on the MI355X flow path -- the caller of the headline configuration (MNIST d = 784,
-Monotonic normalizer + DAG conditioner with the MNISTCNN embedding).  Argument names and defaults, model construction,
+Monotonic normalizer + DAG conditioner with the MNISTCNN embedding) and of the CIFAR-10 flows (d = 3072, CIFAR10CNN
+embeddings, one or four scales).  Argument names and defaults, model construction,
 data preparation (uniform dequantisation + logit), epoch schedule, validation / bits-per-pixel report, threshold sweep,
 sampling and checkpoint files are those of the reference's ImageExperiments.py (:23-36 data transforms and bpp, :130-170
 model, :184-253 epoch loop, :361-384 arguments), re-hosted on one process per GPU:
 
     python train_image.py -dataset MNIST -normalizer Monotonic -no_hot_encoding -prior_A_kernel 2 -b_size 100
+    python train_image.py -dataset CIFAR10 -normalizer Affine -nb_flow 1 1 1 1 -b_size 100 -data_root <dir>
     torchrun --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 train_image.py ...      (RCCL, batch sharded)
 
 What differs, on purpose:
@@ -14,16 +16,26 @@ What differs, on purpose:
     batch; here the gradient is the plain global mean.  `-nb_gpus` is accepted and ignored (the world
     size comes from the launcher).
   * MNIST is read from the IDX files torchvision leaves under `<-data_root>/MNIST/raw` (no download: there is no
-    network); `-data_root synthetic` draws sparse pseudo-digits of the same shape and dtype instead.  CIFAR10 is parsed
-    and refused: its embedding front is outside the hot path.
+    network); `-data_root synthetic` draws sparse pseudo-digits of the same shape and dtype instead.  CIFAR-10 is read
+    from `<-data_root>/cifar-10-batches-bin` or `cifar-10-batches-py` (the latter through an unpickler that admits numpy's
+    array reconstruction and nothing else); `synthetic` draws smooth pseudo-images.
+  * The reference's CIFAR10 branch raises before its first batch (a `hot_encoding=` argument its factory does not take,
+    :155-156; a Monotonic normalizer without `cond_size`) and reports bits per pixel for a logit it never applies (:23-30,
+    :93 against :33-37, :133).  Here: `cond_size = 30`, `-no_hot_encoding` accepted and irrelevant, and the preparation is
+    the MNIST one -- dequantise, squeeze with alpha = .05, logit -- plus the horizontal flip of the training rows (:97);
+    valid = test as there (:106-108).  DESIGN.md lists these among the divergences.
+  * A CIFAR-10 batch is prepared by ONE HIP launch (gnf_hip.ops.image_prep: gather, flip, Philox noise keyed per rank,
+    logit, and the data term of the bits per pixel from y itself); `-device_prep` sends MNIST the same way, whose default
+    stays the torch chain and its generator stream.
   * The matplotlib movies / degree plots of the reference (:296-333) are not produced; the numbers they show (in / out
-    degrees of the thresholded adjacency) go into the log.  Sample grids are written as binary PGM files.
+    degrees of the thresholded adjacency) go into the log.  Sample grids are written as binary PGM (MNIST) / PPM (CIFAR-10) files.
   * `model.pt` / `best_model.pt` carry the reference's `module.`-prefixed keys (it saves the DataParallel wrapper), so
     either side can resume the other's run; `ADAM.pt` is in torch.optim.Adam's format."""
 import argparse
 import gzip
 import math
 import os
+import pickle
 import struct
 import sys
 import time
@@ -35,13 +47,17 @@ import torch.distributed as dist
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from models import (buildFCNormalizingFlow, DAGConditioner, CouplingConditioner, AutoregressiveConditioner,  # noqa: E402
                     AffineNormalizer, MonotonicNormalizer)
-from models.NormalizingFlowFactories import buildMNISTNormalizingFlow  # noqa: E402
-from gnf_hip import dp  # noqa: E402
+from models.NormalizingFlowFactories import buildMNISTNormalizingFlow, buildCIFAR10NormalizingFlow  # noqa: E402
+from models.MLP import CIFAR10CNN  # noqa: E402
+from gnf_hip import dp, ops  # noqa: E402
 from train_uci import shard_batches  # noqa: E402
 
 COND = {"DAG": DAGConditioner, "Coupling": CouplingConditioner, "Autoregressive": AutoregressiveConditioner}
 THRESHOLDS = (.95, .5, .1, .01, .0001)
 TEMPERATURES = (.1, .25, .5, .75, 1.)
+CIFAR_IMG = (3, 32, 32)
+MNIST_IMG = (1, 28, 28)
+PREP_KEY = 1 << 20          # dp.gate_seed(rank, PREP_KEY): the Philox key of the batch preparation; conditioners count from 0
 
 
 # ----------------------------------------------------------------------------- data
@@ -99,6 +115,112 @@ def load_mnist(root, dataset, gen):
     return flat[:n_train], flat[n_train:], tpix.reshape(tpix.shape[0], -1)
 
 
+CIFAR_BIN, CIFAR_PY = "cifar-10-batches-bin", "cifar-10-batches-py"
+CIFAR_RECORD = 1 + 3072                                      # label byte + channel-major 3x32x32 pixels
+
+# the globals a pickled numpy array names (numpy 1.x and 2.x module paths); nothing else is ever looked up
+_PICKLE_GLOBALS = {("numpy.core.multiarray", "_reconstruct"), ("numpy._core.multiarray", "_reconstruct"),
+                   ("numpy.core.numeric", "_frombuffer"), ("numpy._core.numeric", "_frombuffer"),
+                   ("numpy", "ndarray"), ("numpy", "dtype"),
+                   ("_codecs", "encode")}                    # bytes in a protocol-2 file written by python 3
+
+
+class _ArrayUnpickler(pickle.Unpickler):
+    """the batches of `cifar-10-batches-py` are pickled dicts of numpy arrays, lists and strings: admit numpy's array
+    reconstruction, refuse every other global before it is imported or called"""
+
+    def find_class(self, module, name):
+        if (module, name) not in _PICKLE_GLOBALS:
+            raise pickle.UnpicklingError("global %s.%s is not allowed in a CIFAR-10 batch file" % (module, name))
+        if name in ("ndarray", "dtype"):
+            return getattr(np, name)
+        if name == "encode":
+            import _codecs
+            return _codecs.encode
+        core = getattr(np, "_core", None) or np.core
+        return getattr(core.multiarray if name == "_reconstruct" else core.numeric, name)
+
+
+def _cifar_bin(path):
+    raw = np.fromfile(path, dtype=np.uint8)
+    if raw.size == 0 or raw.size % CIFAR_RECORD:
+        raise ValueError("%s: %d bytes is not a whole number of %d-byte CIFAR-10 records" % (path, raw.size, CIFAR_RECORD))
+    return torch.from_numpy(raw.reshape(-1, CIFAR_RECORD)[:, 1:].copy())
+
+
+def _cifar_py(path):
+    with open(path, "rb") as f:
+        batch = _ArrayUnpickler(f, encoding="bytes").load()
+    data = batch[b"data"] if b"data" in batch else batch["data"]
+    data = np.asarray(data)
+    if data.dtype != np.uint8 or data.ndim != 2 or data.shape[1] != 3072:
+        raise ValueError("%s: data is %s %s, not uint8 [n, 3072]" % (path, data.dtype, data.shape))
+    return torch.from_numpy(np.ascontiguousarray(data))
+
+
+def find_cifar10(root):
+    """(directory, reader, file names) of the layout present under root, or SystemExit: nothing is downloaded"""
+    names = ["data_batch_%d" % k for k in range(1, 6)] + ["test_batch"]
+    for sub, reader, ext in ((CIFAR_BIN, _cifar_bin, ".bin"), (CIFAR_PY, _cifar_py, "")):
+        d = os.path.join(root, sub)
+        if all(os.path.isfile(os.path.join(d, n + ext)) for n in names):
+            return d, reader, [n + ext for n in names]
+    raise SystemExit("CIFAR10: %s/ or %s/ (data_batch_1..5, test_batch) not found under %s; no download here -- pass "
+                     "-data_root synthetic for pseudo-images" % (CIFAR_BIN, CIFAR_PY, root))
+
+
+def synthetic_cifar(n, gen):
+    """uint8 [n, 3072] smooth pseudo-images (channel-major 3x32x32): a random 4x4 colour field, bilinearly enlarged, plus a
+    little pixel noise -- neighbouring pixels correlate as in a photograph"""
+    coarse = torch.rand(n, 3, 4, 4, generator=gen)
+    img = torch.nn.functional.interpolate(coarse, size=(32, 32), mode="bilinear", align_corners=True)
+    img = img + .04 * torch.randn(n, 3, 32, 32, generator=gen)
+    return (img.clamp(0, 1) * 255).round().to(torch.uint8).reshape(n, 3072)
+
+
+def load_cifar10(root, gen):
+    """(train [50000, 3072], valid, test) uint8 tensors, rows channel-major 3x32x32 as the files hold them; valid IS test,
+    as in the reference (:106-108, "WARNING VALID = TEST").  Any record count per file is accepted."""
+    if root == "synthetic":
+        trn, tst = synthetic_cifar(24, gen), synthetic_cifar(8, gen)
+    else:
+        d, reader, names = find_cifar10(root)
+        parts = [reader(os.path.join(d, n)) for n in names]
+        trn, tst = torch.cat(parts[:5]), parts[5]
+    return trn, tst, tst
+
+
+def prepare_reference(u8, rows, flip, u, alpha, size_img, dtype=torch.float32):
+    """The arithmetic of a prepared batch in torch, on any device, fp32 or fp64, with explicit uniforms u [B, d]:
+    rows of u8 [n, d] (rows None: all, in order), mirrored where the mask flip [B] says so (flip None: nowhere),
+        y = alpha + (1 - 2 alpha) (pixel + u) / 256,   x = log y - log(1 - y),   bpp_term = sum_j log2 y + log2(1 - y),
+    with 1 - y formed as alpha + (1 - 2 alpha) (256 - pixel - u) / 256 -- the same number, without the cancellation.
+    -> (x [B, d], bpp_term [B]).  What gnf_hip.ops.image_prep computes in one launch; the tests' yardstick."""
+    c, h, w = size_img
+    pix = u8 if rows is None else u8[rows.long()]
+    img = pix.reshape(-1, c, h, w)
+    if flip is not None:
+        img = torch.where(flip.bool().view(-1, 1, 1, 1), img.flip(3), img)
+    p, u = img.reshape(img.shape[0], -1).to(dtype), u.to(dtype)
+    y = alpha + (1. - 2. * alpha) * (p + u) / 256.
+    yc = alpha + (1. - 2. * alpha) * ((256. - p) - u) / 256.
+    return torch.log(y) - torch.log(yc), (torch.log2(y) + torch.log2(yc)).sum(1)
+
+
+class DevicePrep:
+    """Batch preparation through gnf_hip.ops.image_prep: the Philox key of this rank and a per-call counter, no generator
+    state.  Stands where the torch noise generator stands in evaluate() / threshold_sweep()."""
+
+    def __init__(self, rank, alpha, size_img):
+        self.seed, self.alpha, self.size_img, self.calls = dp.gate_seed(rank, PREP_KEY), alpha, tuple(size_img), 0
+
+    def __call__(self, u8, rows=None, flip=False, want_bpp=False):
+        x, term = ops.image_prep(u8, rows, True if flip else None, None, self.seed, self.calls, self.alpha, self.size_img,
+                                 want_bpp)
+        self.calls += 1
+        return x, term
+
+
 def dequantise(u8, alpha, gen):
     """reference lib/transform.py:5-21 (AddUniformNoise): x = logit(alpha + (1 - 2 alpha) (pixel + U[0,1)) / 256); the
     noise is drawn anew every time a batch is read."""
@@ -121,6 +243,12 @@ def compute_bpp(ll, x, alpha=1e-6):
             + (torch.log2(s) + torch.log2(1. - s)).sum(1) / d)
 
 
+def bpp_from_term(ll, term, d, alpha):
+    """compute_bpp with the data term sum_d [log2 y + log2 (1 - y)] handed in (the bpp_term of the preparation kernel,
+    taken from y itself: no `1 - sigmoid(x)`)"""
+    return -ll / (d * math.log(2.)) - math.log2(1. - 2. * alpha) + 8. + term / d
+
+
 # ----------------------------------------------------------------------------- model, checkpoints
 def build(args):
     if args.normalizer == "Affine":
@@ -128,17 +256,41 @@ def build(args):
     else:
         norm_t, nargs = MonotonicNormalizer, {"integrand_net": args.int_net, "nb_steps": 15, "solver": args.solver}
     cond_t = COND[args.conditioner]
-    if cond_t is DAGConditioner:
+    cifar = args.dataset == "CIFAR10"
+    if cond_t is DAGConditioner and cifar:
+        if len(args.nb_flow) not in (1, 4):
+            raise SystemExit("-nb_flow takes 1 or 4 values with the DAG conditioner on CIFAR10 (one 3x32x32 scale or "
+                             "3x32x32 / 32x32 / 16x16 / 8x8)")
+        if norm_t is MonotonicNormalizer:
+            nargs["cond_size"] = 30                          # the factory's embedding width; the reference omits it (:115)
+        # (-no_hot_encoding: the factory has no one-hot form)
+        model = buildCIFAR10NormalizingFlow(args.nb_flow, norm_t, nargs, args.l1, nb_epoch_update=args.nb_steps_dual)
+    elif cond_t is DAGConditioner:
         model = buildMNISTNormalizingFlow(args.nb_flow, norm_t, nargs, args.l1, nb_epoch_update=args.nb_steps_dual,
                                           hot_encoding=not args.no_hot_encoding, prior_kernel=args.prior_A_kernel)
         if model is None:
             raise SystemExit("-nb_flow takes 1 or 3 values with the DAG conditioner (one 28x28 scale or 28/14/7)")
     else:
-        cargs = {"in_size": 784, "hidden": args.emb_net[:-1], "out_size": args.emb_net[-1]}
+        cargs = {"in_size": 3072 if cifar else 784, "hidden": args.emb_net[:-1], "out_size": args.emb_net[-1]}
         if norm_t is MonotonicNormalizer:
             nargs["cond_size"] = args.emb_net[-1]
         model = buildFCNormalizingFlow(args.nb_flow[0], cond_t, cargs, norm_t, nargs)
+    for net in model.modules():                              # the switches of the LDS-resident fronts; default: the nets' own
+        if isinstance(net, CIFAR10CNN):
+            if getattr(args, "gated_front", False):
+                net.gated_front = True
+            if getattr(args, "rows_train_front", False):
+                net.rows_train_front = True
     return model, cond_t, norm_t
+
+
+def image_shape(model):
+    """(C, H, W) of the images a built model takes: from the first embedding net that has one, else by the width"""
+    for m in model.modules():
+        if hasattr(m, "size_img"):
+            return tuple(int(v) for v in m.size_img)
+    d = model.getConditioners()[0].in_size
+    return CIFAR_IMG if d == 3072 else MNIST_IMG
 
 
 def wrapped_keys(sd):
@@ -163,18 +315,38 @@ def write_pgm(path, x01, nrow=4):
         f.write((grid.clamp(0, 1) * 255).round().to(torch.uint8).numpy().tobytes())
 
 
+def write_ppm(path, x01, nrow=4, size_img=CIFAR_IMG):
+    """[n, 3*H*W] channel-major images in [0, 1] as one binary PPM (P6) grid: write_pgm for 3-channel images"""
+    c, h, w = size_img
+    n = x01.shape[0]
+    rows = (n + nrow - 1) // nrow
+    grid = torch.zeros(rows * h, nrow * w, c)
+    for k in range(n):
+        r, col = divmod(k, nrow)
+        grid[h * r:h * r + h, w * col:w * col + w] = x01[k].view(c, h, w).permute(1, 2, 0).cpu()
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (grid.shape[1], grid.shape[0]))
+        f.write((grid.clamp(0, 1) * 255).round().to(torch.uint8).numpy().tobytes())
+
+
 # ----------------------------------------------------------------------------- evaluation
 @torch.no_grad()
 def evaluate(model, u8, b, alpha, gen):
-    """mean log-likelihood and bits per pixel over the full batches of a split (drop_last as the reference's loaders)"""
+    """mean log-likelihood and bits per pixel over the full batches of a split (drop_last as the reference's loaders).
+    gen: the torch generator of the dequantisation noise, or a DevicePrep -- the batch then comes from the preparation
+    kernel (no flip) together with the data term of its bits per pixel"""
     ll_sum = bpp_sum = 0.
     n = 0
     for i in range(0, u8.shape[0] - b + 1, b):
-        x = dequantise(u8[i:i + b], alpha, gen)
+        if isinstance(gen, DevicePrep):
+            x, term = gen(u8[i:i + b], want_bpp=True)
+        else:
+            x, term = dequantise(u8[i:i + b], alpha, gen), None
         z, jac = model(x)
         ll = model.z_log_density(z) + jac
         ll_sum += ll.mean().item()
-        bpp_sum += compute_bpp(ll, x, alpha).mean().item()
+        bpp = compute_bpp(ll, x, alpha) if term is None else bpp_from_term(ll, term, x.shape[1], alpha)
+        bpp_sum += bpp.mean().item()
         n += 1
     return ll_sum / max(n, 1), bpp_sum / max(n, 1)
 
@@ -183,8 +355,9 @@ def train(args):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
-    if args.dataset == "CIFAR10":
-        raise SystemExit("CIFAR10: the CIFAR embedding front is outside the MI355X hot path (DESIGN.md section 8)")
+    cifar = args.dataset == "CIFAR10"
+    if cifar and args.data_root != "synthetic":
+        find_cifar10(args.data_root)                         # SystemExit("CIFAR10: ... not found ...") before any GPU work
     if not torch.cuda.is_available():
         raise SystemExit("train_image.py needs an MI355X (the flow kernels have no CPU fallback)")
     backend = os.environ.get("GNF_DIST_BACKEND", "nccl")     # "nccl" is RCCL; "gloo" only to exercise N>1 on a 1-GPU box
@@ -200,10 +373,15 @@ def train(args):
             dist.init_process_group("nccl", device_id=dev)
         else:
             dist.init_process_group(backend)
-    alpha = 1e-6
+    alpha = .05 if cifar else 1e-6                           # reference :133
     host_gen = torch.Generator().manual_seed(1234)           # identical on every rank: same split, same global batches
-    trn, val, tst = [t.to(dev) for t in load_mnist(args.data_root, args.dataset, host_gen)]
-    noise = torch.Generator(device=dev).manual_seed(4321 + rank)
+    splits = load_cifar10(args.data_root, host_gen) if cifar else load_mnist(args.data_root, args.dataset, host_gen)
+    trn, val, tst = [t.to(dev) for t in splits]
+    # the source of a batch's noise: the preparation kernel (always for CIFAR10: the flip and the keyed noise exist only
+    # there), or the torch chain and its generator stream (MNIST unless -device_prep)
+    device_prep = cifar or args.device_prep
+    noise = (DevicePrep(rank, alpha, CIFAR_IMG if cifar else MNIST_IMG) if device_prep
+             else torch.Generator(device=dev).manual_seed(4321 + rank))
     torch.manual_seed(0)
     model, cond_t, norm_t = build(args)
     os.makedirs(args.folder, exist_ok=True)
@@ -250,7 +428,10 @@ def train(args):
                     k = args.nb_steps + int(torch.randint(0, 10, [1], generator=host_gen))
                     for nrm in model.getNormalizers():
                         nrm.nb_steps = k
-                x = dequantise(trn[rows.to(dev)], alpha, noise)
+                if device_prep:                              # gather + flip (CIFAR10 training rows, :97) + noise + logit
+                    x = noise(trn, rows.to(dev, torch.int32), flip=cifar)[0]
+                else:
+                    x = dequantise(trn[rows.to(dev)], alpha, noise)
                 if k_acc == 1:
                     loss = dp.train_step(model, state, x, lr=args.learning_rate, weight_decay=args.weight_decay)
                 else:
@@ -332,11 +513,16 @@ def threshold_sweep(model, val, b, alpha, noise, epoch, say):
 def sample_grids(model, dev, alpha, epoch, folder, say, n_images=16):
     """once the graph is a DAG (:322-330): 16 samples at five temperatures, the round-trip error, a 4x4 grid each"""
     g = torch.Generator(device=dev).manual_seed(epoch)
+    size_img = image_shape(model)
+    d = size_img[0] * size_img[1] * size_img[2]
     for T in TEMPERATURES:
-        z = torch.randn(n_images, 784, device=dev, generator=g) * T
+        z = torch.randn(n_images, d, device=dev, generator=g) * T
         x = model.invert(z)
         say("epoch: %d - T %.2f - |z - f(f^-1(z))| %.3e" % (epoch, T, (z - model(x)[0]).abs().mean().item()))
-        write_pgm(os.path.join(folder, "images_%d_%f.pgm" % (epoch, T)), logit_back(x, alpha))
+        if size_img[0] == 3:
+            write_ppm(os.path.join(folder, "images_%d_%f.ppm" % (epoch, T)), logit_back(x, alpha), size_img=size_img)
+        else:
+            write_pgm(os.path.join(folder, "images_%d_%f.pgm" % (epoch, T)), logit_back(x, alpha))
 
 
 # (flag, default, type / None for a switch, nargs, choices): names and defaults of the reference's driver
@@ -353,7 +539,10 @@ _ARGS = (
     ("emb_net", [100, 100, 100, 10], int, "+", None),
     # additions of this driver
     ("max_batches", 0, int, None, None),      # stop an epoch after this many batches (smoke runs; 0: all)
-    ("data_root", ".", str, None, None),      # directory holding MNIST/raw/*-ubyte(.gz), or `synthetic`
+    ("data_root", ".", str, None, None),      # directory holding MNIST/raw/*-ubyte(.gz) or cifar-10-batches-{bin,py}, or `synthetic`
+    ("device_prep", False, None, None, None),       # MNIST batches through the preparation kernel too (CIFAR10: always)
+    ("gated_front", False, None, None, None),       # CIFAR10CNN.gated_front = True on every net (masked copies built in LDS)
+    ("rows_train_front", False, None, None, None),  # CIFAR10CNN.rows_train_front = True on every net (frozen-gate training)
 )
 
 

@@ -38,8 +38,8 @@
 extern "C" {
 #endif
 
-/* 11 still: gnf_lenet_gated_* were ADDED under this number (no existing symbol changed; a binding written against the
- * earlier 11 keeps working, and tests/test_cifar_factory.py pins the value) */
+/* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_* and gnf_image_prep were ADDED under this number (no existing symbol
+ * changed; a binding written against the earlier 11 keeps working, and tests/test_cifar_factory.py pins the value) */
 #define GNF_ABI_VERSION 11
 #define GNF_EINVAL (-1)   /* bad argument (null pointer, negative size, ...)          */
 #define GNF_ESHAPE (-2)   /* shape not supported by any compiled kernel instantiation */
@@ -627,6 +627,38 @@ int gnf_adam_step(float* p, const float* g, float* m, float* v, int64_t n,
 int gnf_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n,
                       double lr, double beta1, double beta2, double eps, double weight_decay,
                       double grad_scale, int* step_dev, int advance, gnf_stream_t stream);
+
+/* ---- batch preparation of the image driver in one launch (train_image.py; reference lib/transform.py:5-21,
+ * ImageExperiments.py:33-37, :97) --------------------------------------------------------------------------------------
+ * Output row b < B is row rows[b] of a uint8 data set, optionally mirrored, dequantised and logit-transformed:
+ *   pixel = data[rows[b], src(j)],  y = alpha + (1 - 2 alpha) (pixel + u) / 256,  x[b, j] = log y - log (1 - y),
+ *   bpp_term[b] = sum_j log2 y + log2 (1 - y)        (the data term of bits per pixel, from y itself and not from x).
+ * 1 - y is evaluated as alpha + (1 - 2 alpha) (256 - pixel - u) / 256: the same number without the cancellation of the
+ * subtraction (a white pixel at alpha = 1e-6 keeps its full precision).  Logarithms: v_log_f32, 1 ulp.
+ * data: [n_rows, d] bytes, row-major, at ANY byte address;  d = C*H*W (C, H, W matter only for the flip).
+ * rows: B int32 device indices, any order, repeats allowed, or NULL for rows 0 .. B-1 (needs B <= n_rows).  The host copy is
+ *   not required and nothing is read back: the kernel CLAMPS every index into [0, n_rows), so an index outside the data set
+ *   prepares the first / last row instead of reading outside it.  Keeping the indices inside is the caller's contract.
+ * flip_mode 0: no flip;  1: the byte mask flip [B] decides (nonzero = mirrored);  2: one Philox coin per output row,
+ *   p = 1/2.  A mirrored row reads source column W-1-w for output (c, h, w).
+ * u: [B, d] explicit uniforms indexed by OUTPUT element (the parity hook, as u1 / u2 of the gate), or NULL for Philox.
+ * Philox layout (seed = key, offset = the caller's call counter; philox4x32_10 and u01_open of csrc/gnf_common.h):
+ *   output element e = b*d + j:  u = u01_open(r[e & 3]),  r = philox4x32_10(counter = (e >> 2, offset), key = seed),
+ *     counter words (lo32(e >> 2), hi32(e >> 2), lo32(offset), hi32(offset)), key words (lo32(seed), hi32(seed));
+ *   coin of row b (flip_mode 2): counter words (lo32(b), hi32(b) | 0x80000000, lo32(offset), hi32(offset)), same key;
+ *     mirrored when bit 31 of r[0] is set.  No element reaches that counter (e >> 2 < 2^62).
+ *   Row b's noise and coin depend on (seed, offset, b, d) only, not on B.  tests/test_gpu_image_prep.py pins the layout.
+ * x: [B, d] contiguous;  bpp_term: [B] or NULL.  The row sum is taken in a fixed order without atomics: the same bits on
+ * every call.  Two kernels, chosen by the arguments, with BIT-IDENTICAL results: quads as one dword load + one float4 store
+ * when d % 4 == 0, data is dword-aligned, x and u are 16-byte aligned (and W % 4 == 0 unless flip_mode is 0); bytes and
+ * single floats otherwise.
+ * GNF_EINVAL: B < 0, C / H / W < 1, flip_mode outside 0..2, alpha outside [0, .5), and for B > 0 a NULL data or x,
+ * n_rows < 1, flip_mode 1 without flip, rows NULL with B > n_rows, a float / int32 pointer below dword alignment.
+ * GNF_ESHAPE: B >= 2^31.  B == 0: returns 0 without a launch; every batch-sized pointer may be NULL.
+ * (Added under ABI version 11: no existing symbol changed.) */
+int gnf_image_prep(const unsigned char* data, int64_t n_rows, const int32_t* rows, int flip_mode,
+                   const unsigned char* flip, int C, int H, int W, const float* u, uint64_t seed, uint64_t offset,
+                   float alpha, float* x, float* bpp_term, int64_t B, gnf_stream_t stream);
 
 /* ---- device-ceiling probes (measurement aids for bench.py) ---------------
  * gnf_probe_mfma_f32 launches `blocks` workgroups of 8 wavefronts that do nothing but
