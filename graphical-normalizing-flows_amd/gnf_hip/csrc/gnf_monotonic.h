@@ -2,12 +2,16 @@
 // the Monotonic-normalizer translation units (gnf_monotonic.hip, gnf_monotonic_wide.hip).
 #pragma once
 #include "gnf_common.h"
+#include <type_traits>
 
 namespace gnfmono {
 
 constexpr int kWaves = 4;          // wavefronts per workgroup
 constexpr int kMaxNH = GNF_MONO_MAX_LAYERS - 1;
 constexpr int kNarrowQ = 3 * 3 * (256 + 128);   // words of one bf16-split 48 x 48 block (MonoLayout::o_Wq)
+// LDS of a CU as both units' host halves plan it: what a workgroup may allocate, and what a resident weight image may take of it
+constexpr size_t kLdsBudget = 160 * 1024;
+constexpr size_t kLdsImage = 150 * 1024;
 
 // ---------------------------------------------------------------------------------------
 // Padded weight image ("pack"): every matrix row-major with leading dimension LD = pad+4
@@ -124,13 +128,27 @@ struct MonoArgs {
   float* SA[kMaxNH]; float* SD[kMaxNH]; float* Dsum; float* part;
   int64_t e0, ecount;                   // element chunk [e0, e0+ecount)
   int NK;                               // node slots per group (S+2 rounded up to even)
+  // ones, indw and f32only are HOST-ONLY: no kernel reads them (the variant is in the kernel's template arguments); they keep
+  // their place so that the argument block, and with it every kernel's code, stays what it was (written by mono_bwd_any)
   int ones;                             // backward: bias gradients of the hidden layers via a ones column (see mono_bwd_k)
-  int indw;                             // backward: weight gradients accumulated in the chain kernel (1, 2: narrow nets;
-                                        // 3: wide nets, gnf_monotonic_wide.hip)
+  int indw;                             // backward: weight gradients accumulated in the chain kernel.  0: staged; narrow nets:
+                                        // 1 one node per pass, 2 two (the pair kernels); 3: wide nets (gnf_monotonic_wide.hip)
   float* wpart;                         // [workgroups * kWaves][(NH-1) * HP * HP] accumulator rows of that variant
                                         // (indw = 3, or wcomb: one row per workgroup)
-  int wcomb;                            // mono_bwd_pair_x_k: the wavefronts' accumulator rows are added in LDS at the end
-  int f32only;                          // host side: keep the fp32-MFMA kernels (gnf_monotonic_fwd_f32 / _bwd_f32)
+  int wcomb;                            // mono_bwd_pair_x_k (device): the wavefronts' accumulator rows are added in LDS at the end
+  int f32only;                          // keep the fp32-MFMA kernels (gnf_monotonic_fwd_f32 / _bwd_f32)
+};
+
+// One kernel launch as the host halves decide it: every kernel of both units takes the argument block by value.
+typedef void (*MonoKernel)(MonoArgs);
+template <int N>
+using Int = std::integral_constant<int, N>;      // a template argument as a value, for the dispatchers' generic lambdas
+struct MonoLaunch {
+  MonoKernel kernel;                    // nullptr: the shape has no instantiation (GNF_ESHAPE)
+  unsigned grid, block;
+  size_t lds;                           // dynamic LDS bytes;  raise: they may exceed the default 64 KB (gnf_launch_lds)
+  bool raise;
+  const char* name;                     // the kernel family, for gnf_monotonic_fwd_kernel / _bwd_kernel
 };
 
 __device__ __forceinline__ void store_inverse(const MonoArgs& a, int64_t e, float v) {
@@ -167,11 +185,11 @@ __device__ __forceinline__ float elu_plus(float s) { return (s > 0.f ? s : expm1
 
 // gnf_monotonic_wide.hip: backward of wide integrand nets (H = 97..160) with the hidden state of a batch of (element, node)
 // pairs in LDS, the output units split over the wavefronts and every weight gradient accumulated in registers.
-// ok(): the net's shape has an instantiation and its LDS plan fits.  grid(): persistent workgroups (= rows of a.wpart).
+// ok(): the net's shape has an instantiation and its LDS plan fits.  route(): the launch for a call (a chunk) of n elements;
+// its grid = persistent workgroups = rows of a.wpart.  true_f32: the fp32-MFMA kernel even when the split-bf16 one is enabled.
 bool gnf_mono_bwd_wide_ok(const gnfmono::MonoLayout& L);
-unsigned gnf_mono_bwd_wide_grid(const gnfmono::MonoLayout& L, int64_t n);
-int gnf_mono_bwd_wide_launch(const gnfmono::MonoArgs& a, unsigned grid, hipStream_t s, bool true_f32, const char* volatile* kernel);
+gnfmono::MonoLaunch gnf_mono_bwd_wide_route(const gnfmono::MonoLayout& L, int64_t n, bool true_f32);
 // forward (z, jac) of the same nets in the same formulation, two workgroups per CU
 bool gnf_mono_fwd_wide_ok(const gnfmono::MonoLayout& L);
-// true_f32: the fp32-MFMA kernel even when the split-bf16 one is enabled.  *kernel: the family launched.
-int gnf_mono_fwd_wide_launch(const gnfmono::MonoArgs& a, hipStream_t s, bool true_f32, const char* volatile* kernel);
+gnfmono::MonoLaunch gnf_mono_fwd_wide_route(const gnfmono::MonoLayout& L, int64_t n, bool true_f32);
+// (both units ask gnf_gemm_split_enabled() of include/gnf_hip.h whether the split-bf16 forms run: 0 under GNF_TRUE_F32=1)

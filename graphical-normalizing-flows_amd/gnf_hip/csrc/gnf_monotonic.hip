@@ -32,7 +32,6 @@
 #include "gnf_monotonic.h"
 #include <cstdlib>
 
-extern "C" int gnf_gemm_split_enabled(void);
 // kernel family of the process' last forward / backward launch (gnf_monotonic_fwd_kernel / _bwd_kernel: reporting only; NOT
 // thread-local -- autograd runs the backward on its own thread and the caller asks from another)
 static const char* volatile g_fwd_kernel = "";
@@ -2220,8 +2219,6 @@ int pick_ht(const gnf_mono_net* net) {
   return -1;
 }
 
-constexpr int kLdsBudget = 160 * 1024;
-
 // layout of a net's pack + whether its kernels peel the leftover units of the last tile (all hidden widths H with
 // H / 16 == 3 and H mod 16 in {1, 2, 3}: the reference's default [50, 50, 50]).  (The A/B switches of rounds 3-5 --
 // GNF_MONO_PEEL, GNF_MONO_WIDE_EXP, GNF_MONO_ROWPEEL, GNF_MONO_KPERM, GNF_MONO_INV_EPG4, GNF_MONO_WIDE / _WIDE_FWD -- are gone with
@@ -2244,203 +2241,151 @@ MonoLayout net_layout(const gnf_mono_net* net, int HT) {
   return L;
 }
 
-// The launches of launch_fwd whose kernels differ only in template arguments.  wlds: the weight image is LDS-resident (more
-// than the 64 KB a kernel may have by default: gnf_launch_lds); otherwise the WM = 0 instantiation, a plain launch.
-template <int EX>     // mono_inv_ks_x_k of a peeled net with EX leftover units
-int launch_inv_ks(const MonoArgs& a, int epg, int ks_waves, unsigned gq, size_t lds_k, hipStream_t s) {
-  const dim3 grid(gq), block(64 * ks_waves);
-  if (epg == 2) {
-    if (ks_waves <= 8) return (int)gnf_launch_lds(mono_inv_ks_x_k<3, EX, 2, 8>, grid, block, lds_k, s, a);
-    return (int)gnf_launch_lds(mono_inv_ks_x_k<3, EX, 2, kSplitWavesX>, grid, block, lds_k, s, a);
-  }
-  if (ks_waves <= 8) return (int)gnf_launch_lds(mono_inv_ks_x_k<3, EX, 4, 8>, grid, block, lds_k, s, a);
-  return (int)gnf_launch_lds(mono_inv_ks_x_k<3, EX, 4, kSplitWavesX>, grid, block, lds_k, s, a);
+// What the entry points check alike, in this order: the net (GNF_ESHAPE; more than max_nh hidden layers likewise, after the
+// rest), the pointers every call needs (always_null: one of them is) and S / B / d (GNF_EINVAL), 16-byte alignment of the pack
+// (read in 16-byte pieces, some global -> LDS directly: glds16) and of the backward's staging arrays, the empty batch, the
+// batch-sized pointers (may be NULL for an empty batch).  -> 1: go on, *L is the net's layout;  0: empty batch;  < 0: the error.
+template <class... P>
+bool any_null(P... p) { return (... || (p == nullptr)); }
+int prologue(const gnf_mono_net* net, int max_nh, bool always_null, const void* pack, const void* ws, int S, int64_t B, int64_t d,
+             bool batch_null, MonoLayout* L) {
+  const int HT = pick_ht(net);
+  if (HT < 0) return GNF_ESHAPE;
+  if (!pack || always_null || S < 1 || B < 0 || d <= 0) return GNF_EINVAL;
+  if (((uintptr_t)pack | (uintptr_t)ws) & 15) return GNF_EINVAL;
+  if (net->nl - 1 > max_nh) return GNF_ESHAPE;
+  if (B == 0) return 0;
+  if (batch_null) return GNF_EINVAL;
+  *L = net_layout(net, HT);
+  return 1;
 }
-template <int EX, int EPG>
-int launch_inv_x(const MonoArgs& a, bool wlds, unsigned grid, int nw, size_t lds, hipStream_t s) {
-  if (wlds) return (int)gnf_launch_lds(mono_inv_split_x_k<3, EX, 1, EPG>, dim3(grid), dim3(64 * nw), lds, s, a);
-  hipLaunchKernelGGL((mono_inv_split_x_k<3, EX, 0, EPG>), dim3(grid), dim3(64 * nw), lds, s, a);
-  GNF_LAUNCH_CHECK();
-  return 0;
+
+// ---- one dispatcher per template axis: f(Int<..>{}) -> the kernel; nullptr where the axis has no such value
+template <class F>
+MonoKernel with_ht(int HT, F f) {        // 16-unit tiles of the widest hidden layer (pick_ht)
+  return HT == 2 ? f(Int<2>{}) : HT == 4 ? f(Int<4>{}) : HT == 7 ? f(Int<7>{}) : HT == 10 ? f(Int<10>{}) : HT == 16 ? f(Int<16>{}) : nullptr;
 }
-template <int HT, int EPG>
-int launch_inv_ht(const MonoArgs& a, bool wlds, unsigned grid, int nw, size_t lds, hipStream_t s) {
-  if (wlds) return (int)gnf_launch_lds(mono_inv_split_k<HT, 1, EPG>, dim3(grid), dim3(64 * nw), lds, s, a);
-  hipLaunchKernelGGL((mono_inv_split_k<HT, 0, EPG>), dim3(grid), dim3(64 * nw), lds, s, a);
-  GNF_LAUNCH_CHECK();
-  return 0;
+template <class F>
+MonoKernel with_nh(int NH, F f) {        // hidden layers of the backward's kernels
+  return NH == 1 ? f(Int<1>{}) : NH == 2 ? f(Int<2>{}) : NH == 3 ? f(Int<3>{}) : NH == 4 ? f(Int<4>{}) : nullptr;
 }
-template <int EPG>
-int launch_inv(const MonoArgs& a, bool wlds, unsigned grid, int nw, size_t lds, hipStream_t s) {
-  switch (a.L.HT) {
-    case 2: return launch_inv_ht<2, EPG>(a, wlds, grid, nw, lds, s);
-    case 4: return launch_inv_ht<4, EPG>(a, wlds, grid, nw, lds, s);
-    case 7: return launch_inv_ht<7, EPG>(a, wlds, grid, nw, lds, s);
-    case 10: return launch_inv_ht<10, EPG>(a, wlds, grid, nw, lds, s);
-    case 16: return launch_inv_ht<16, EPG>(a, wlds, grid, nw, lds, s);
-    default: return GNF_ESHAPE;
-  }
+template <class F>
+MonoKernel with_ex(int EX, F f) {        // peeled nets: one or two leftover units share the EX = 2 instantiation, three have their own
+  return EX <= 2 ? f(Int<2>{}) : f(Int<3>{});
 }
-template <int EX, bool INV>
-int launch_fwd_x(const MonoArgs& a, bool wlds, unsigned grid, size_t lds, hipStream_t s) {
-  if (wlds) return (int)gnf_launch_lds(mono_fwd_x_k<3, EX, 1, INV>, dim3(grid), dim3(64 * kWaves), lds, s, a);
-  hipLaunchKernelGGL((mono_fwd_x_k<3, EX, 0, INV>), dim3(grid), dim3(64 * kWaves), 0, s, a);
-  GNF_LAUNCH_CHECK();
-  return 0;
-}
-template <int HT, bool INV>
-int launch_fwd_ht(const MonoArgs& a, bool wlds, bool swap, unsigned grid, size_t lds, size_t lds_one, hipStream_t s) {
-  if (wlds) return (int)gnf_launch_lds(mono_fwd_k<HT, 1, INV>, dim3(grid), dim3(64 * kWaves), lds, s, a);
-  if (swap) return (int)gnf_launch_lds(mono_fwd_k<HT, 2, INV>, dim3(grid), dim3(64 * kWaves), lds_one, s, a);
-  hipLaunchKernelGGL((mono_fwd_k<HT, 0, INV>), dim3(grid), dim3(64 * kWaves), 0, s, a);
+#define GNF_INT(x) decltype(x)::value      // the template argument a dispatcher handed over
+
+// the launch of a route; raise: first lift the kernel's dynamic-LDS limit to r.lds (gnf_launch_lds)
+int launch(const MonoLaunch& r, const MonoArgs& a, hipStream_t s) {
+  if (!r.kernel) return GNF_ESHAPE;
+  if (r.raise) return (int)gnf_launch_lds(r.kernel, dim3(r.grid), dim3(r.block), r.lds, s, a);
+  hipLaunchKernelGGL(r.kernel, dim3(r.grid), dim3(r.block), r.lds, s, a);
   GNF_LAUNCH_CHECK();
   return 0;
 }
 
+// ---- LDS bytes of every plan, each a function of the layout alone
+constexpr size_t kF = sizeof(float);
+size_t lds_fwd_image(const MonoLayout& L) { return (size_t)L.fwd_floats * kF; }          // what forward / inverse read
+size_t lds_fwd_split(const MonoLayout& L) { return lds_fwd_image(L) + (size_t)(L.NH - 1) * kNarrowQ * 4; }   // + the bf16 planes
+size_t lds_one_matrix(const MonoLayout& L) { return (size_t)L.HP * L.LDW * kF; }
+size_t lds_hidden_matrices(const MonoLayout& L) { return lds_one_matrix(L) * (L.NH > 1 ? L.NH - 1 : 1); }
+size_t lds_whole_image(const MonoLayout& L) { return (size_t)L.total_floats * kF; }      // with the backward's transposes
+size_t lds_ones(const MonoLayout& L) { return (size_t)(L.fwd_floats + L.CP * L.LDW) * kF; }   // all but the transposed hidden matrices
+size_t lds_tiles(const MonoLayout& L, int per_wave) { return (size_t)kWaves * per_wave * 16 * kTS * kF; }   // element-major tiles
+size_t lds_indw(const MonoLayout& L) { return (size_t)(L.total_floats + 3) / 4 * 4 * kF + lds_tiles(L, L.NH); }
+size_t lds_pair(const MonoLayout& L) {       // two nodes per pass: image without W1h / W1h^T, 5 tiles per wavefront at NH = 3
+  return ((size_t)L.o_W1h + (size_t)(L.NH - 1) * (2 * L.HP * L.LDW + L.HP)) * kF + lds_tiles(L, 2 * (L.NH - 1) + 1);
+}
+size_t lds_pair_split(const MonoLayout& L) {
+  return ((size_t)L.o_W1h + (size_t)(L.NH - 1) * (8 * L.LDW + L.HP + 2 * kNarrowQ)) * kF + lds_tiles(L, 2 * (L.NH - 1) + 1);
+}
+size_t lds_wcomb(const MonoLayout& L) { return (size_t)kWaves * (L.NH - 1) * L.HP * L.HP * kF; }   // the wavefronts' dW rows
+
+// ---- forward and inverse
+// where the forward image lives: whole in LDS (wm 1), else one hidden matrix at a time (2), else L1 / L2 (0)
+struct FwdImage {
+  size_t lds, lds_one;
+  bool wlds, swap;
+  explicit FwdImage(const MonoLayout& L)
+      : lds(lds_fwd_image(L)), lds_one(lds_one_matrix(L)), wlds(lds <= kLdsImage), swap(!wlds && L.NH > 1 && lds_one <= kLdsImage) {}
+};
+
+// the persistent kernels: a wavefront per 16-element group.  The forward of every narrow net but the split form below, and the
+// inverse of what has too many groups (or too few nodes) to split the quadrature over wavefronts.
 template <bool INV>
-int launch_fwd(const MonoArgs& a, hipStream_t s) {
-  const int HT = a.L.HT;
-  const int64_t ngroups = (a.n + 15) / 16;
+MonoLaunch persistent_route(const MonoLayout& L, int64_t n, const FwdImage& im) {
+  const int64_t ngroups = (n + 15) / 16;
   int64_t grid = (ngroups + kWaves - 1) / kWaves;
-  const size_t lds = (size_t)a.L.fwd_floats * sizeof(float);
-  const size_t lds_one = (size_t)a.L.HP * a.L.LDW * sizeof(float);
-  const bool wlds = lds <= (size_t)150 * 1024;                       // whole forward image resident
-  const bool swap = !wlds && a.L.NH > 1 && lds_one <= (size_t)150 * 1024;   // else one matrix at a time, else L1/L2
-  if (INV && !swap && ngroups <= 512 && a.S >= 7) {
-    // fewer groups than a resident wave of workgroups: split the quadrature nodes over the workgroup's wavefronts
-    const int pairs = (a.S + 2) / 2;
-    const bool quarter = ngroups < 256;                               // groups of 4 elements x 4 node pairs (see above)
-    // level-sized problems on a peeled net: two bisection steps per round (mono_inv_ks_x_k) when the 3 (S + 1) evaluations of
-    // an element fit the workgroup's pair slots (S <= 31) and the weight image is LDS-resident; GNF_MONO_INV_PTS=1 keeps the
-    // one-step kernel (A/B and the bit-equality test)
-    static const bool one_pt = getenv("GNF_MONO_INV_PTS") && getenv("GNF_MONO_INV_PTS")[0] == '1';
-    const int epg = a.n <= 2 * 256 ? 2 : 4;                           // elements per workgroup (see mono_inv_ks_x_k)
-    const int ks_waves = ((3 * (a.S + 1) + 1) / 2 * epg + 15) / 16;   // node-pair columns / 16 per wavefront
-    if (a.L.EX > 0 && quarter && wlds && !one_pt && ks_waves <= kSplitWavesX && a.S <= 31) {   // (32 node slots per point)
-      const size_t lds_k = lds + (size_t)(2 * 32 + 2 * 3 * 32 * epg + 2 * 3 * epg) * sizeof(float);
-      const unsigned gq = (unsigned)((a.n + epg - 1) / epg);
-      return a.L.EX <= 2 ? launch_inv_ks<2>(a, epg, ks_waves, gq, lds_k, s) : launch_inv_ks<3>(a, epg, ks_waves, gq, lds_k, s);
-    }
-    if (a.L.EX > 0 && quarter) {
-      const int nwq = (pairs + 3) / 4 < kSplitWavesX ? (pairs + 3) / 4 : kSplitWavesX;
-      const size_t lds_q = (wlds ? lds : 0) + 2 * nwq * 16 * sizeof(float);
-      const unsigned gq = (unsigned)((a.n + 3) / 4);
-      return a.L.EX <= 2 ? launch_inv_x<2, 4>(a, wlds, gq, nwq, lds_q, s) : launch_inv_x<3, 4>(a, wlds, gq, nwq, lds_q, s);
-    }
-    if (a.L.EX > 0) {                                                 // peeled narrow net: up to 16 wavefronts per group
-      const int nwx = pairs < kSplitWavesX ? pairs : kSplitWavesX;
-      const size_t lds_x = (wlds ? lds : 0) + 2 * nwx * 16 * sizeof(float);
-      return a.L.EX <= 2 ? launch_inv_x<2, 16>(a, wlds, (unsigned)ngroups, nwx, lds_x, s)
-                         : launch_inv_x<3, 16>(a, wlds, (unsigned)ngroups, nwx, lds_x, s);
-    }
-    if (quarter) {
-      const int nwq = (pairs + 3) / 4 < kSplitWaves ? (pairs + 3) / 4 : kSplitWaves;
-      const size_t lds_q = (wlds ? lds : 0) + 2 * nwq * 16 * sizeof(float);
-      return launch_inv<4>(a, wlds, (unsigned)((a.n + 3) / 4), nwq, lds_q, s);
-    }
-    const int nw = pairs < kSplitWaves ? pairs : kSplitWaves;
-    const size_t lds_split = (wlds ? lds : 0) + 2 * nw * 16 * sizeof(float);
-    return launch_inv<16>(a, wlds, (unsigned)ngroups, nw, lds_split, s);
-  }
-  const int64_t per_cu = ((wlds && lds > (size_t)kLdsBudget / 2) || swap) ? 1 : 2;   // resident workgroups per CU
-  if (grid > 256 * per_cu) grid = 256 * per_cu;                      // persistent
-  if (a.L.EX > 0 && !swap) {                                          // peeled narrow net (HM = 3: H in {49, 50, 51})
-    if constexpr (!INV) {
-      const size_t lds_sp = lds + (size_t)(a.L.NH - 1) * kNarrowQ * 4;
-      if (wlds && a.L.NH > 1 && !a.f32only && gnf_gemm_split_enabled() && lds_sp <= (size_t)kLdsBudget / 2) {
-        g_fwd_kernel = "mono_fwd_x_k<split>";
-        const dim3 g((unsigned)grid), b(64 * kWaves);
-        return (int)(a.L.EX <= 2 ? gnf_launch_lds(mono_fwd_x_k<3, 2, 1, false, true>, g, b, lds_sp, s, a)
-                                 : gnf_launch_lds(mono_fwd_x_k<3, 3, 1, false, true>, g, b, lds_sp, s, a));
-      }
-    }
-    return a.L.EX <= 2 ? launch_fwd_x<2, INV>(a, wlds, (unsigned)grid, lds, s) : launch_fwd_x<3, INV>(a, wlds, (unsigned)grid, lds, s);
-  }
-  switch (HT) {
-    case 2: return launch_fwd_ht<2, INV>(a, wlds, swap, (unsigned)grid, lds, lds_one, s);
-    case 4: return launch_fwd_ht<4, INV>(a, wlds, swap, (unsigned)grid, lds, lds_one, s);
-    case 7: return launch_fwd_ht<7, INV>(a, wlds, swap, (unsigned)grid, lds, lds_one, s);
-    case 10: return launch_fwd_ht<10, INV>(a, wlds, swap, (unsigned)grid, lds, lds_one, s);
-    case 16: return launch_fwd_ht<16, INV>(a, wlds, swap, (unsigned)grid, lds, lds_one, s);
-    default: return GNF_ESHAPE;
-  }
+  const int64_t per_cu = ((im.wlds && im.lds > kLdsBudget / 2) || im.swap) ? 1 : 2;   // resident workgroups per CU
+  if (grid > 256 * per_cu) grid = 256 * per_cu;
+  const int wm = im.wlds ? 1 : im.swap ? 2 : 0;
+  MonoLaunch r{nullptr, (unsigned)grid, 64 * kWaves, wm == 1 ? im.lds : wm == 2 ? im.lds_one : 0, wm != 0, "mono_fwd_k"};
+  if (L.EX > 0 && !im.swap)                                           // peeled narrow net (HM = 3: H in {49, 50, 51})
+    r.kernel = with_ex(L.EX, [&](auto ex) -> MonoKernel {
+      return im.wlds ? mono_fwd_x_k<3, GNF_INT(ex), 1, INV> : mono_fwd_x_k<3, GNF_INT(ex), 0, INV>;
+    });
+  else
+    r.kernel = with_ht(L.HT, [&](auto ht) -> MonoKernel {
+      constexpr int HT = GNF_INT(ht);
+      return wm == 1 ? mono_fwd_k<HT, 1, INV> : wm == 2 ? mono_fwd_k<HT, 2, INV> : mono_fwd_k<HT, 0, INV>;
+    });
+  return r;
 }
 
-template <int HT, int NH>
-int launch_bwd_one(const MonoArgs& a, unsigned grid, hipStream_t s) {
-  const size_t lds_all = (size_t)a.L.total_floats * sizeof(float);
-  const size_t lds_one = (size_t)a.L.HP * a.L.LDW * sizeof(float);
-  const dim3 g(grid), b(64 * kWaves);
-  if constexpr (HT <= 4 && NH > 1) {
-    if (a.indw == 2) {                          // two nodes per pass, image without W1h / W1h^T, 5 tiles per wavefront
-      const size_t lds_pair = ((size_t)a.L.o_W1h + (size_t)(NH - 1) * (2 * a.L.HP * a.L.LDW + a.L.HP) +
-                               (size_t)kWaves * (2 * (NH - 1) + 1) * 16 * kTS) * sizeof(float);
-      if constexpr (HT == 4) {
-        if (a.L.EX > 0) {                       // peeled: 3 tiles on the MFMA, the H mod 16 leftover units on the VALU
-          // row peel (the weight gradient's fourth out tile on the VALU) where its partials fit the register file
-          constexpr bool kRP = NH <= 3;          // NH = 4: 122 registers spilled
-          if constexpr (NH <= 3) {               // the split-bf16 chain (SP): the reference's [H]^3 / [H]^2 nets
-            const size_t lds_sp = ((size_t)a.L.o_W1h + (size_t)(NH - 1) * (8 * a.L.LDW + a.L.HP + 2 * kNarrowQ) +
-                                   (size_t)kWaves * (2 * (NH - 1) + 1) * 16 * kTS) * sizeof(float);
-            const size_t lds_wcomb = (size_t)kWaves * (NH - 1) * a.L.HP * a.L.HP * sizeof(float);
-            if (!a.f32only && gnf_gemm_split_enabled() && lds_sp <= (size_t)kLdsBudget && (!a.wcomb || lds_wcomb <= lds_sp)) {
-              g_bwd_kernel = "mono_bwd_pair_x_k<split>";
-              if (a.L.EX <= 2) return (int)gnf_launch_lds(mono_bwd_pair_x_k<3, NH, 2, kRP, true>, g, b, lds_sp, s, a);
-              return (int)gnf_launch_lds(mono_bwd_pair_x_k<3, NH, 3, false, true>, g, b, lds_sp, s, a);
-            }
-          }
-          if (a.L.EX <= 2) return (int)gnf_launch_lds(mono_bwd_pair_x_k<3, NH, 2, kRP>, g, b, lds_pair, s, a);
-          return (int)gnf_launch_lds(mono_bwd_pair_x_k<3, NH, 3>, g, b, lds_pair, s, a);
-        }
-      }
-      return (int)gnf_launch_lds(mono_bwd_pair_k<HT, NH>, g, b, lds_pair, s, a);
-    }
-    if (a.indw) {                               // whole image + per-wavefront element-major tiles, one workgroup per CU
-      const size_t lds_in = ((size_t)(a.L.total_floats + 3) / 4 * 4 + (size_t)kWaves * NH * 16 * kTS) * sizeof(float);
-      if (lds_in > (size_t)kLdsBudget) return GNF_ESHAPE;
-      return (int)gnf_launch_lds(mono_bwd_k<HT, NH, 1, true, true>, g, b, lds_in, s, a);
-    }
-    if (a.ones) {                               // everything but the transposed hidden matrices resident, two workgroups per CU
-      const size_t lds_res = (size_t)(a.L.fwd_floats + a.L.CP * a.L.LDW) * sizeof(float);
-      return (int)gnf_launch_lds(mono_bwd_k<HT, NH, 4, true>, g, b, lds_res, s, a);
-    }
+MonoLaunch fwd_route(const MonoLayout& L, int64_t n, bool true_f32) {
+  if (gnf_mono_fwd_wide_ok(L)) return gnf_mono_fwd_wide_route(L, n, true_f32);
+  const FwdImage im(L);
+  MonoLaunch r = persistent_route<false>(L, n, im);
+  // peeled nets, image resident: the hidden layers on the bf16 matrix pipe where image + planes leave room for two workgroups per CU
+  if (L.EX > 0 && im.wlds && L.NH > 1 && !true_f32 && gnf_gemm_split_enabled() && lds_fwd_split(L) <= kLdsBudget / 2) {
+    r.lds = lds_fwd_split(L);
+    r.name = "mono_fwd_x_k<split>";
+    r.kernel = with_ex(L.EX, [](auto ex) -> MonoKernel { return mono_fwd_x_k<3, GNF_INT(ex), 1, false, true>; });
   }
-  if constexpr (HT <= 4) {                      // whole image resident
-    if (lds_all > (size_t)150 * 1024) return GNF_ESHAPE;
-    return (int)gnf_launch_lds(mono_bwd_k<HT, NH, 1>, g, b, lds_all, s, a);
-  } else if constexpr (HT <= 10) {
-    const size_t lds_res = lds_one * (NH > 1 ? NH - 1 : 1);
-    if (NH > 1 && lds_res <= (size_t)150 * 1024)            // all hidden->hidden matrices resident (H <= 112, 3 hidden layers)
-      return (int)gnf_launch_lds(mono_bwd_k<HT, NH, 3>, g, b, lds_res, s, a);
-    return (int)gnf_launch_lds(mono_bwd_k<HT, NH, 2>, g, b, lds_one, s, a);   // one matrix at a time
-  } else {
-    hipLaunchKernelGGL((mono_bwd_k<HT, NH, 0>), g, b, 0, s, a);
-    GNF_LAUNCH_CHECK();
-    return 0;
-  }
+  return r;
 }
 
-template <int HT>
-int launch_bwd_nh(const MonoArgs& a, unsigned grid, hipStream_t s) {
-  switch (a.L.NH) {
-    case 1: return launch_bwd_one<HT, 1>(a, grid, s);
-    case 2: return launch_bwd_one<HT, 2>(a, grid, s);
-    case 3: return launch_bwd_one<HT, 3>(a, grid, s);
-    case 4: return launch_bwd_one<HT, 4>(a, grid, s);
-    default: return GNF_ESHAPE;
+MonoLaunch inv_route(const MonoLayout& L, int64_t n, int S) {
+  const FwdImage im(L);
+  const int64_t ngroups = (n + 15) / 16;
+  if (im.swap || ngroups > 512 || S < 7) return persistent_route<true>(L, n, im);
+  // fewer groups than a resident wave of workgroups: split the quadrature nodes over the workgroup's wavefronts
+  const bool peeled = L.EX > 0;                                       // up to kSplitWavesX wavefronts per group, else kSplitWaves
+  const bool quarter = ngroups < 256;                                 // groups of 4 elements x 4 node pairs (see above)
+  // level-sized problems on a peeled net: two bisection steps per round (mono_inv_ks_x_k) when the 3 (S + 1) evaluations of
+  // an element fit the workgroup's pair slots (S <= 31: 32 node slots per point) and the weight image is LDS-resident;
+  // GNF_MONO_INV_PTS=1 (read once) keeps the one-step kernel (A/B and the bit-equality test)
+  static const bool one_step = getenv("GNF_MONO_INV_PTS") && getenv("GNF_MONO_INV_PTS")[0] == '1';
+  const int epg = n <= 2 * 256 ? 2 : 4;                               // elements per workgroup (see mono_inv_ks_x_k)
+  const int ks_waves = ((3 * (S + 1) + 1) / 2 * epg + 15) / 16;       // node-pair columns / 16 per wavefront
+  if (peeled && quarter && im.wlds && !one_step && ks_waves <= kSplitWavesX && S <= 31) {
+    MonoLaunch r{nullptr, (unsigned)((n + epg - 1) / epg), 64u * ks_waves,
+                 im.lds + (size_t)(2 * 32 + 2 * 3 * 32 * epg + 2 * 3 * epg) * kF, true, ""};
+    r.kernel = with_ex(L.EX, [&](auto ex) -> MonoKernel {
+      constexpr int EX = GNF_INT(ex);
+      if (epg == 2) return ks_waves <= 8 ? mono_inv_ks_x_k<3, EX, 2, 8> : mono_inv_ks_x_k<3, EX, 2, kSplitWavesX>;
+      return ks_waves <= 8 ? mono_inv_ks_x_k<3, EX, 4, 8> : mono_inv_ks_x_k<3, EX, 4, kSplitWavesX>;
+    });
+    return r;
   }
+  const int pairs = (S + 2) / 2, want = quarter ? (pairs + 3) / 4 : pairs, cap = peeled ? kSplitWavesX : kSplitWaves;
+  const int nw = want < cap ? want : cap;
+  MonoLaunch r{nullptr, (unsigned)(quarter ? (n + 3) / 4 : ngroups), 64u * nw, (im.wlds ? im.lds : 0) + 2 * nw * 16 * kF, im.wlds, ""};
+  auto pick = [&](auto epg_) -> MonoKernel {
+    constexpr int EPG = GNF_INT(epg_);
+    if (peeled)
+      return with_ex(L.EX, [&](auto ex) -> MonoKernel {
+        return im.wlds ? mono_inv_split_x_k<3, GNF_INT(ex), 1, EPG> : mono_inv_split_x_k<3, GNF_INT(ex), 0, EPG>;
+      });
+    return with_ht(L.HT, [&](auto ht) -> MonoKernel {
+      return im.wlds ? mono_inv_split_k<GNF_INT(ht), 1, EPG> : mono_inv_split_k<GNF_INT(ht), 0, EPG>;
+    });
+  };
+  r.kernel = quarter ? pick(Int<4>{}) : pick(Int<16>{});
+  return r;
 }
 
-int launch_bwd(const MonoArgs& a, unsigned grid, hipStream_t s) {
-  switch (a.L.HT) {
-    case 2: return launch_bwd_nh<2>(a, grid, s);
-    case 4: return launch_bwd_nh<4>(a, grid, s);
-    case 7: return launch_bwd_nh<7>(a, grid, s);
-    case 10: return launch_bwd_nh<10>(a, grid, s);
-    case 16: return launch_bwd_nh<16>(a, grid, s);
-    default: return GNF_ESHAPE;
-  }
-}
 
 // ---------------------------------------------------------------------------------------
 // Weight gradient of one hidden->hidden layer of a WIDE net from the staged rows:
@@ -2551,22 +2496,106 @@ struct BwdPlan {
   int64_t total_floats;
 };
 
-// narrow nets whose hidden widths leave a padding column (and whose image + tiles fit the LDS): the chain kernel
-// accumulates the hidden-layer weight gradients itself, nothing but Dsum is staged
-bool use_indw(const gnf_mono_net* net, const MonoLayout& L) {
-  if (L.HT > 4 || L.NH < 2) return false;
-  for (int l = 1; l < L.NH; ++l)
-    if (net->dims[l] >= L.HP) return false;
-  const size_t lds = ((size_t)(L.total_floats + 3) / 4 * 4 + (size_t)kWaves * L.NH * 16 * kTS) * sizeof(float);
-  static const bool off = getenv("GNF_MONO_INDW") && getenv("GNF_MONO_INDW")[0] == '0';     // A/B switch (measurement)
-  return lds <= (size_t)160 * 1024 && !off;
-}
 constexpr unsigned kInDwGrid = 256;           // one workgroup per CU (512 registers per wavefront)
 
-// indw: 0 staged weight gradients; 1 narrow in-kernel (one accumulator row per wavefront); 2 wide in-kernel
-// (gnf_monotonic_wide.hip: one accumulator row per workgroup)
-BwdPlan plan_bwd(const MonoLayout& L, int S, int64_t n, int64_t ws_floats, int indw = 0) {
+// ---- the backward's route: everything a call needs to know about its variant, decided once
+// The chain kernel's family.  Wide: gnf_monotonic_wide.hip (hidden state in LDS, weight gradients in registers).  Narrow nets
+// with in-kernel weight gradients: PairXSplit / PairX (peeled, two nodes per pass, hidden layers on the bf16 matrix pipe / fp32:
+// mono_bwd_pair_x_k), Pair (mono_bwd_pair_k), InDw (one node per pass, whole image + element-major tiles).  Staged rows,
+// mono_bwd_k<.., WMODE>: Ones (a ones column; all but the transposed hidden matrices resident, 4), Image (whole image, 1),
+// Resident / OneMatrix (HT 7 / 10: all hidden->hidden matrices resident, 3, or one at a time, 2), Streamed (HT 16: L1 / L2, 0).
+enum class BwdKernel { Wide, PairXSplit, PairX, Pair, InDw, Ones, Image, Resident, OneMatrix, Streamed };
+// what the workspace holds beside Dsum: the staged rows of every hidden layer, or the chain kernel's own weight-gradient
+// accumulator rows -- one per wavefront (narrow nets) or one per workgroup (wide nets)
+enum class BwdWs { Staged, RowPerWave, RowPerGroup };
+enum class InDwSwitch { Pair, Off, OneNode };     // GNF_MONO_INDW unset / 0 / 1 (A/B, measurement): read once
+InDwSwitch indw_switch() {
+  static const char* const e = getenv("GNF_MONO_INDW");
+  return !e ? InDwSwitch::Pair : e[0] == '0' ? InDwSwitch::Off : e[0] == '1' ? InDwSwitch::OneNode : InDwSwitch::Pair;
+}
+
+struct BwdRoute {
+  BwdKernel k;
+  BwdWs ws;
+  bool ones;               // bias gradients of the hidden layers sit in a ones column (the padding column every width leaves)
+  bool wcomb;              // the peeled pair kernel adds its wavefronts' accumulator rows in LDS: one row per workgroup
+  MonoLaunch l;            // kernel (nullptr: no LDS plan fits this net), grid, dynamic LDS, reporter string
+};
+
+MonoKernel bwd_kernel(BwdKernel k, const MonoLayout& L) {
+  return with_ht(L.HT, [&](auto ht) {
+    return with_nh(L.NH, [&](auto nh) -> MonoKernel {
+      constexpr int HT = GNF_INT(ht), NH = GNF_INT(nh);
+      if constexpr (HT <= 4 && NH > 1) {
+        if constexpr (HT == 4) {         // peeled: 3 tiles on the MFMA, the H mod 16 leftover units on the VALU
+          // row peel (the weight gradient's fourth out tile on the VALU) where its partials fit: NH = 4 spills 122 registers
+          constexpr bool kRP = NH <= 3;
+          if constexpr (NH <= 3)           // the split-bf16 chain: the reference's [H]^3 / [H]^2 nets
+            if (k == BwdKernel::PairXSplit)
+              return with_ex(L.EX, [](auto ex) -> MonoKernel {
+                return mono_bwd_pair_x_k<3, NH, GNF_INT(ex), kRP && GNF_INT(ex) == 2, true>;
+              });
+          if (k == BwdKernel::PairX)
+            return with_ex(L.EX, [](auto ex) -> MonoKernel { return mono_bwd_pair_x_k<3, NH, GNF_INT(ex), kRP && GNF_INT(ex) == 2>; });
+        }
+        if (k == BwdKernel::Pair) return mono_bwd_pair_k<HT, NH>;
+        if (k == BwdKernel::InDw) return mono_bwd_k<HT, NH, 1, true, true>;
+        if (k == BwdKernel::Ones) return mono_bwd_k<HT, NH, 4, true>;
+      }
+      if constexpr (HT <= 4) return k == BwdKernel::Image ? mono_bwd_k<HT, NH, 1> : nullptr;
+      else if constexpr (HT <= 10)
+        return k == BwdKernel::Resident ? mono_bwd_k<HT, NH, 3> : k == BwdKernel::OneMatrix ? mono_bwd_k<HT, NH, 2> : nullptr;
+      else return k == BwdKernel::Streamed ? mono_bwd_k<HT, NH, 0> : nullptr;
+    });
+  });
+}
+
+BwdRoute bwd_route(const gnf_mono_net* net, const MonoLayout& L, bool true_f32) {
+  BwdRoute r{BwdKernel::Streamed, BwdWs::Staged, false, false, MonoLaunch{nullptr, kBwdGrid, 64 * kWaves, 0, true, "mono_bwd_k"}};
+  if (gnf_mono_bwd_wide_ok(L)) {     // its launch depends on the chunk size the plan allows: gnf_mono_bwd_wide_route, by the caller
+    r.k = BwdKernel::Wide; r.ws = BwdWs::RowPerGroup;
+    return r;
+  }
+  // narrow nets whose hidden widths leave a padding column: the ones column, and (where image + tiles fit the LDS) the
+  // chain kernel accumulates the hidden-layer weight gradients itself, nothing but Dsum is staged
+  bool pad = L.HT <= 4 && L.NH > 1;
+  for (int l = 1; l < L.NH; ++l) pad = pad && net->dims[l] < L.HP;
+  r.ones = pad;      // (the two-role kernels of the wide nets carry the bias gradients in their partial vector rows)
+  if (pad && lds_indw(L) <= kLdsBudget && indw_switch() != InDwSwitch::Off) {
+    r.ws = BwdWs::RowPerWave;
+    r.l.grid = kInDwGrid;
+    r.k = BwdKernel::InDw; r.l.lds = lds_indw(L);
+    if (lds_pair(L) <= kLdsBudget && indw_switch() != InDwSwitch::OneNode) {      // the two-node kernel when its LDS plan fits
+      r.k = BwdKernel::Pair; r.l.lds = lds_pair(L);
+      if (L.HT == 4 && L.EX > 0) {
+        r.k = BwdKernel::PairX;
+        // it can add its wavefronts' weight-gradient rows in LDS when they fit its allocation
+        r.wcomb = lds_wcomb(L) <= lds_pair(L);
+        if (L.NH <= 3 && !true_f32 && gnf_gemm_split_enabled() && lds_pair_split(L) <= kLdsBudget &&
+            (!r.wcomb || lds_wcomb(L) <= lds_pair_split(L))) {
+          r.k = BwdKernel::PairXSplit; r.l.lds = lds_pair_split(L);
+          r.l.name = "mono_bwd_pair_x_k<split>";
+        }
+      }
+    }
+  } else if (pad) {
+    r.k = BwdKernel::Ones; r.l.lds = lds_ones(L);
+  } else if (L.HT <= 4) {
+    r.k = BwdKernel::Image; r.l.lds = lds_whole_image(L);
+  } else if (L.HT <= 10) {
+    const bool all = L.NH > 1 && lds_hidden_matrices(L) <= kLdsImage;     // (H <= 112, 3 hidden layers)
+    r.k = all ? BwdKernel::Resident : BwdKernel::OneMatrix;
+    r.l.lds = all ? lds_hidden_matrices(L) : lds_one_matrix(L);
+  } else {
+    r.l.raise = false;
+  }
+  if (r.k != BwdKernel::Image || r.l.lds <= kLdsImage) r.l.kernel = bwd_kernel(r.k, L);
+  return r;
+}
+
+BwdPlan plan_bwd(const MonoLayout& L, int S, int64_t n, int64_t ws_floats, BwdWs mode) {
   BwdPlan P;
+  const bool indw = mode != BwdWs::Staged;
   const int64_t HP = L.HP, NK = (S + 2 + 1) / 2 * 2;
   const int64_t vecw = (L.NH + 2) * HP + 4;
   int64_t fixed = 0;
@@ -2580,7 +2609,7 @@ BwdPlan plan_bwd(const MonoLayout& L, int S, int64_t n, int64_t ws_floats, int i
   P.o_vec = fixed; fixed += vecw;
   P.o_rs = fixed; fixed += (int64_t)kRowsumChunks * HP;     // scratch of the tall row-sums (bias gradients)
   P.o_wpart = fixed;
-  if (indw) fixed += (int64_t)kInDwGrid * (indw == 2 ? 1 : kWaves) * (L.NH - 1) * HP * HP;
+  if (indw) fixed += (int64_t)kInDwGrid * (mode == BwdWs::RowPerGroup ? 1 : kWaves) * (L.NH - 1) * HP * HP;
   const int64_t per_elem = indw ? HP : (int64_t)(L.NH - 1) * 2 * NK * HP + HP;     // SA+SD per hidden layer, Dsum
   int64_t ce = (n + 15) / 16 * 16;
   if (ws_floats > 0) {
@@ -2599,146 +2628,47 @@ BwdPlan plan_bwd(const MonoLayout& L, int S, int64_t n, int64_t ws_floats, int i
   return P;
 }
 
-}  // namespace
-
-extern "C" {
-
-int64_t gnf_monotonic_pack_floats(const gnf_mono_net* net) {
-  const int HT = pick_ht(net);
-  if (HT < 0) return GNF_ESHAPE;
-  return net_layout(net, HT).pack_floats;
-}
-
-int gnf_monotonic_pack(const gnf_mono_net* net, float* pack, gnf_stream_t stream) {
-  const int HT = pick_ht(net);
-  if (HT < 0) return GNF_ESHAPE;
-  if (!pack || ((uintptr_t)pack & 15)) return GNF_EINVAL;   // the consumers read it in 16-byte pieces, some straight to LDS
-  PackArgs a;
-  a.net = *net;
-  a.L = net_layout(net, HT);
-  hipLaunchKernelGGL(mono_pack_k, dim3((a.L.pack_floats + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, pack);
-  GNF_LAUNCH_CHECK();
-  return 0;
-}
-
-const char* gnf_monotonic_fwd_kernel(void) { return g_fwd_kernel; }
-
-static int mono_fwd_any(const float* pack, const gnf_mono_net* net, const float* x, const float* h, int64_t h_sb,
-                        int64_t h_sd, int64_t h_sc, const float* cc_w, const float* cc_t, int S, float* z,
-                        float* jac, int64_t B, int64_t d, gnf_stream_t stream, bool true_f32);
-
-int gnf_monotonic_fwd(const float* pack, const gnf_mono_net* net, const float* x, const float* h, int64_t h_sb,
-                      int64_t h_sd, int64_t h_sc, const float* cc_w, const float* cc_t, int S, float* z,
-                      float* jac, int64_t B, int64_t d, gnf_stream_t stream) {
-  return mono_fwd_any(pack, net, x, h, h_sb, h_sd, h_sc, cc_w, cc_t, S, z, jac, B, d, stream, false);
-}
-int gnf_monotonic_fwd_f32(const float* pack, const gnf_mono_net* net, const float* x, const float* h, int64_t h_sb,
-                          int64_t h_sd, int64_t h_sc, const float* cc_w, const float* cc_t, int S, float* z,
-                          float* jac, int64_t B, int64_t d, gnf_stream_t stream) {
-  return mono_fwd_any(pack, net, x, h, h_sb, h_sd, h_sc, cc_w, cc_t, S, z, jac, B, d, stream, true);
-}
-
-static int mono_fwd_any(const float* pack, const gnf_mono_net* net, const float* x, const float* h, int64_t h_sb,
-                        int64_t h_sd, int64_t h_sc, const float* cc_w, const float* cc_t, int S, float* z,
-                        float* jac, int64_t B, int64_t d, gnf_stream_t stream, bool true_f32) {
-  const int HT = pick_ht(net);
-  if (HT < 0) return GNF_ESHAPE;
-  if (!pack || !cc_w || !cc_t || S < 1 || B < 0 || d <= 0) return GNF_EINVAL;
-  if ((uintptr_t)pack & 15) return GNF_EINVAL;          // 16-byte pieces, some global -> LDS directly (glds16)
-  if (B == 0) return 0;                    // batch-sized arrays may be NULL for an empty batch
-  if (!x || !h || !z || !jac) return GNF_EINVAL;
+int mono_fwd_any(const float* pack, const gnf_mono_net* net, const float* x, const float* h, int64_t h_sb, int64_t h_sd,
+                 int64_t h_sc, const float* cc_w, const float* cc_t, int S, float* z, float* jac, int64_t B, int64_t d,
+                 gnf_stream_t stream, bool true_f32) {
   MonoArgs a{};
-  a.pack = pack; a.L = net_layout(net, HT);
+  const int go = prologue(net, kMaxNH, any_null(cc_w, cc_t), pack, nullptr, S, B, d, any_null(x, h, z, jac), &a.L);
+  if (go <= 0) return go;
+  a.pack = pack;
   a.x = x; a.h = h; a.h_sb = h_sb; a.h_sd = h_sd; a.h_sc = h_sc;
   a.ccw = cc_w; a.cct = cc_t; a.S = S; a.z = z; a.jac = jac; a.n = B * d; a.d = d;
   a.f32only = true_f32;
-  if (gnf_mono_fwd_wide_ok(a.L)) return gnf_mono_fwd_wide_launch(a, (hipStream_t)stream, true_f32, &g_fwd_kernel);
-  g_fwd_kernel = "mono_fwd_k";                        // (launch_fwd overrides it for the split form of the peeled nets)
-  return launch_fwd<false>(a, (hipStream_t)stream);
+  const MonoLaunch r = fwd_route(a.L, a.n, true_f32);
+  g_fwd_kernel = r.name;
+  return launch(r, a, (hipStream_t)stream);
 }
 
-int gnf_monotonic_inv_scatter(const float* pack, const gnf_mono_net* net, const float* z, const float* h, int64_t h_sb,
-                              int64_t h_sd, int64_t h_sc, const float* cc_w, const float* cc_t, int S, float* x,
-                              const int32_t* x_row_off, int64_t x_sd, int64_t B, int64_t d, gnf_stream_t stream) {
-  const int HT = pick_ht(net);
-  if (HT < 0) return GNF_ESHAPE;
-  if (!pack || !cc_w || !cc_t || S < 1 || B < 0 || d <= 0) return GNF_EINVAL;
-  if ((uintptr_t)pack & 15) return GNF_EINVAL;
-  if (B == 0) return 0;
-  if (!z || !h || !x) return GNF_EINVAL;
-  MonoArgs a{};
-  a.pack = pack; a.L = net_layout(net, HT);
-  a.h = h; a.h_sb = h_sb; a.h_sd = h_sd; a.h_sc = h_sc;
-  a.ccw = cc_w; a.cct = cc_t; a.S = S; a.zt = z; a.xo = x; a.n = B * d; a.d = d;
-  a.xo_row = x_row_off; a.xo_sd = x_sd;
-  return launch_fwd<true>(a, (hipStream_t)stream);
-}
-
-int gnf_monotonic_inv(const float* pack, const gnf_mono_net* net, const float* z, const float* h, int64_t h_sb,
-                      int64_t h_sd, int64_t h_sc, const float* cc_w, const float* cc_t, int S, float* x, int64_t B,
-                      int64_t d, gnf_stream_t stream) {
-  return gnf_monotonic_inv_scatter(pack, net, z, h, h_sb, h_sd, h_sc, cc_w, cc_t, S, x, nullptr, 0, B, d, stream);
-}
-
-int64_t gnf_monotonic_bwd_ws_bytes(const gnf_mono_net* net, int S, int64_t B, int64_t d) {
-  const int HT = pick_ht(net);
-  if (HT < 0) return GNF_ESHAPE;
-  const MonoLayout L = net_layout(net, HT);
-  const int indw = use_indw(net, L) ? 1 : (gnf_mono_bwd_wide_ok(L) ? 2 : 0);
-  if (B < 1) B = 1;                          // an empty batch needs no workspace; keep the plan arithmetic away from 0
-  const BwdPlan full = plan_bwd(L, S, B * d, 0, indw);
-  const int64_t want = full.total_floats * (int64_t)sizeof(float);
-  if (want <= kWsTarget) return want;
-  // bounded staging: at least one 16-element group per persistent wavefront
-  const BwdPlan fixed_only = plan_bwd(L, S, 16, 0, indw);
-  const int64_t min_bytes = fixed_only.total_floats * (int64_t)sizeof(float);
-  return kWsTarget > min_bytes ? kWsTarget : min_bytes;
-}
-
-static thread_local bool g_bwd_true_f32 = false;
-const char* gnf_monotonic_bwd_kernel(void) { return g_bwd_kernel; }
-
-int gnf_monotonic_bwd_f32(const float* pack, const gnf_mono_net* net, const float* x, const float* h, int64_t h_sb,
-                          int64_t h_sd, int64_t h_sc, const float* cc_w, const float* cc_t, int S, const float* gz,
-                          const float* gjac, float* gx, float* gh, int64_t g_sb, int64_t g_sd, int64_t g_sc,
-                          float* const* gW, float* const* gb, void* ws, int64_t ws_bytes, int64_t B, int64_t d,
-                          gnf_stream_t stream) {
-  g_bwd_true_f32 = true;
-  const int rc = gnf_monotonic_bwd(pack, net, x, h, h_sb, h_sd, h_sc, cc_w, cc_t, S, gz, gjac, gx, gh, g_sb, g_sd, g_sc, gW, gb, ws,
-                                   ws_bytes, B, d, stream);
-  g_bwd_true_f32 = false;
-  return rc;
-}
-
-int gnf_monotonic_bwd(const float* pack, const gnf_mono_net* net, const float* x, const float* h, int64_t h_sb,
-                      int64_t h_sd, int64_t h_sc, const float* cc_w, const float* cc_t, int S, const float* gz,
-                      const float* gjac, float* gx, float* gh, int64_t g_sb, int64_t g_sd, int64_t g_sc,
-                      float* const* gW, float* const* gb, void* ws, int64_t ws_bytes, int64_t B, int64_t d,
-                      gnf_stream_t stream) {
-  const int HT = pick_ht(net);
-  if (HT < 0) return GNF_ESHAPE;
-  if (!pack || !cc_w || !cc_t || !gW || !gb || S < 1 || B < 0 || d <= 0) return GNF_EINVAL;
-  if (((uintptr_t)pack | (uintptr_t)ws) & 15) return GNF_EINVAL;   // the weight image and the staging arrays: 16-byte pieces
+int mono_bwd_any(const float* pack, const gnf_mono_net* net, const float* x, const float* h, int64_t h_sb, int64_t h_sd,
+                 int64_t h_sc, const float* cc_w, const float* cc_t, int S, const float* gz, const float* gjac, float* gx,
+                 float* gh, int64_t g_sb, int64_t g_sd, int64_t g_sc, float* const* gW, float* const* gb, void* ws,
+                 int64_t ws_bytes, int64_t B, int64_t d, gnf_stream_t stream, bool true_f32) {
+  hipStream_t s = (hipStream_t)stream;
+  MonoLayout L;
+  const int go = prologue(net, 4, any_null(cc_w, cc_t, gW, gb), pack, ws, S, B, d, any_null(x, h, gz, gh, ws), &L);
+  if (go < 0) return go;
   const int NH = net->nl - 1;
-  if (NH > 4) return GNF_ESHAPE;
-  if (B == 0) {                              // empty batch: zero parameter gradients, nothing else to write
+  if (go == 0) {                             // empty batch: zero parameter gradients, nothing else to write
     for (int l = 0; l <= NH; ++l) {
       if (!gW[l] || !gb[l]) return GNF_EINVAL;
-      if (hipMemsetAsync(gW[l], 0, sizeof(float) * net->dims[l] * net->dims[l + 1], (hipStream_t)stream) != hipSuccess ||
-          hipMemsetAsync(gb[l], 0, sizeof(float) * net->dims[l + 1], (hipStream_t)stream) != hipSuccess)
+      if (hipMemsetAsync(gW[l], 0, sizeof(float) * net->dims[l] * net->dims[l + 1], s) != hipSuccess ||
+          hipMemsetAsync(gb[l], 0, sizeof(float) * net->dims[l + 1], s) != hipSuccess)
         return GNF_EINVAL;
     }
     return 0;
   }
-  if (!x || !h || !gz || !gh || !ws) return GNF_EINVAL;
   if (h_sb != d * h_sd) return GNF_ESHAPE;   // element stride must collapse (caller makes h contiguous)
-  hipStream_t s = (hipStream_t)stream;
-  const MonoLayout L = net_layout(net, HT);
+  const int HT = L.HT;
   const int64_t n = B * d;
-  const bool wide = gnf_mono_bwd_wide_ok(L);       // wide nets: hidden state in LDS, weight gradients in registers
-  const bool indw = use_indw(net, L) || wide;
-  const BwdPlan P = plan_bwd(L, S, n, ws_bytes / (int64_t)sizeof(float), wide ? 2 : (indw ? 1 : 0));
+  BwdRoute r = bwd_route(net, L, true_f32);
+  const BwdPlan P = plan_bwd(L, S, n, ws_bytes / (int64_t)sizeof(float), r.ws);
   if (P.chunk_elems < 16) return GNF_EWS;
+  const bool wide = r.k == BwdKernel::Wide, indw = r.ws != BwdWs::Staged;
+  if (wide) r.l = gnf_mono_bwd_wide_route(L, n < P.chunk_elems ? n : P.chunk_elems, true_f32);
   float* w = (float*)ws;
   const int64_t HP = L.HP, NK = (S + 2 + 1) / 2 * 2;
   const int64_t vecw = (NH + 2) * HP + 4;
@@ -2749,40 +2679,26 @@ int gnf_monotonic_bwd(const float* pack, const gnf_mono_net* net, const float* x
   a.gz = gz; a.gjac = gjac; a.gx = gx; a.gh = gh; a.g_sb = g_sb; a.g_sd = g_sd; a.g_sc = g_sc;
   for (int l = 1; l < NH; ++l) { a.SA[l] = w + P.o_SA[l]; a.SD[l] = w + P.o_SD[l]; }
   a.Dsum = w + P.o_Dsum; a.part = w + P.o_part; a.NK = (int)NK;
-  a.ones = HT <= 4 && NH > 1 && !wide;       // (the two-role kernels carry the bias gradients in their partial vector rows)
-  for (int l = 1; l < NH; ++l) a.ones = a.ones && net->dims[l] < HP;
-  a.indw = wide ? 3 : (int)indw;
-  a.f32only = g_bwd_true_f32;
-  if (indw && !wide) {                            // the two-node kernel when its LDS plan fits (A/B: GNF_MONO_INDW=1 keeps one node)
-    const size_t lds_pair = ((size_t)L.o_W1h + (size_t)(NH - 1) * (2 * L.HP * L.LDW + L.HP) +
-                             (size_t)kWaves * (2 * (NH - 1) + 1) * 16 * kTS) * sizeof(float);
-    static const bool one = getenv("GNF_MONO_INDW") && getenv("GNF_MONO_INDW")[0] == '1';
-    if (lds_pair <= (size_t)160 * 1024 && !one) a.indw = 2;
-    // the peeled two-node kernel can add its wavefronts' weight-gradient rows in LDS when they fit its allocation
-    a.wcomb = a.indw == 2 && HT == 4 && L.EX > 0 && (size_t)kWaves * (NH - 1) * HP * HP * sizeof(float) <= lds_pair;
-  }
+  // the argument block's copy of the route: host-only but for wcomb (gnf_monotonic.h)
+  a.ones = r.ones; a.indw = wide ? 3 : !indw ? 0 : r.k == BwdKernel::InDw ? 1 : 2; a.wcomb = r.wcomb; a.f32only = true_f32;
   a.wpart = w + P.o_wpart;
-  const unsigned bwd_grid = wide ? gnf_mono_bwd_wide_grid(L, n < P.chunk_elems ? n : P.chunk_elems)
-                                 : (indw ? kInDwGrid : kBwdGrid);
+  const unsigned bwd_grid = r.l.grid;
 
   auto rowsum = [&](const float* src, float* out, int64_t Pn, int64_t N, int acc) -> int {
     return gnf_rowsum_launch(src, out, Pn, N, acc, s);
   };
   const int64_t nchunks = (n + P.chunk_elems - 1) / P.chunk_elems;
   const int64_t part_rows = (int64_t)bwd_grid * kWaves;
-  const int64_t wpart_rows = (wide || a.wcomb) ? (int64_t)bwd_grid : part_rows;
+  const int64_t wpart_rows = (wide || r.wcomb) ? (int64_t)bwd_grid : part_rows;
   int64_t nsp_w = 1, nsp_h = 1;
   int rc = 0;
   for (int64_t ck = 0; ck < nchunks; ++ck) {
     a.e0 = ck * P.chunk_elems;
     a.ecount = n - a.e0 < P.chunk_elems ? n - a.e0 : P.chunk_elems;
-    if (wide) {                        // its wavefronts write only their own half of the partial rows
-      if (hipMemsetAsync(a.part, 0, sizeof(float) * part_rows * vecw, s) != hipSuccess) return GNF_EINVAL;
-      if ((rc = gnf_mono_bwd_wide_launch(a, bwd_grid, s, g_bwd_true_f32, &g_bwd_kernel))) return rc;
-    } else {
-      g_bwd_kernel = "mono_bwd_k";
-      if ((rc = launch_bwd(a, bwd_grid, s))) return rc;
-    }
+    // (the wide kernel's wavefronts write only their own half of the partial rows)
+    if (wide && hipMemsetAsync(a.part, 0, sizeof(float) * part_rows * vecw, s) != hipSuccess) return GNF_EINVAL;
+    g_bwd_kernel = r.l.name;
+    if ((rc = launch(r.l, a, s))) return rc;
     const int64_t groups = (a.ecount + 15) / 16;
     const int64_t rows = groups * NK * 16;
     const int accum = ck > 0 ? GNF_GEMM_ACCUM : 0;     // chunk 0 is the largest: it defines the split count
@@ -2813,6 +2729,7 @@ int gnf_monotonic_bwd(const float* pack, const gnf_mono_net* net, const float* x
     // reductions on contiguous conditioner outputs instead of a split-K tiled GEMM, its reduction and a two-stage column
     // sum (cfg4: 17 + 5 + 13 us; cfg5, where Dsum is 2 GB: 3.6 + 0.8 ms at 0.7 TB/s)
     const bool tall_w1 = nchunks == 1 && h_sc == 1 && gnf_linear_tall_wgrad_ok(a.ecount, HP < 64 ? HP : 64, L.c, HP, h_sd);
+    const bool db1_staged = HT > 4 || r.ones || wide;   // first-layer bias gradient (and wide nets' others): column sums of staged arrays
     if (!tall_w1) {  // d W1[:,1:] (+)= Dsum^T * h
       GemmArgs g{};
       g.A = a.Dsum; g.sam = 1; g.sak = HP;
@@ -2832,11 +2749,11 @@ int gnf_monotonic_bwd(const float* pack, const gnf_mono_net* net, const float* x
       for (int64_t u0 = 0; u0 < HP; u0 += 64) {
         const int64_t nu = HP - u0 < 64 ? HP - u0 : 64;
         if ((rc = gnf_linear_tall_wgrad(a.Dsum + u0, HP, h + a.e0 * h_sd, h_sd, w + P.o_dW1h + u0 * L.c,
-                                        (HT > 4 || a.ones || wide) ? w + P.o_vec + 2 * HP + u0 : nullptr, 1, a.ecount, nu, L.c,
+                                        db1_staged ? w + P.o_vec + 2 * HP + u0 : nullptr, 1, a.ecount, nu, L.c,
                                         w + P.o_hpart, w + P.o_rs, s)))
           return rc;
       }
-    } else if (HT > 4 || a.ones || wide) {     // first-layer bias gradient (and wide nets' others): column sums of staged arrays
+    } else if (db1_staged) {
       if ((rc = gnf_rowsum_tall_launch(a.Dsum, w + P.o_vec + 2 * HP, groups * 16, HP, 1, w + P.o_rs, s))) return rc;
     }
     // widest nets (H = 161..256): bias gradients of the hidden->hidden layers = column sums of the staged dpre rows --
@@ -2856,10 +2773,97 @@ int gnf_monotonic_bwd(const float* pack, const gnf_mono_net* net, const float* x
     u.dWpad[l] = w + P.o_dW[l];
   }
   if (nsp_h > 0 && (rc = rowsum(w + P.o_hpart, w + P.o_dW1h, nsp_h, HP * L.c, 0))) return rc;
-  u.dW1h = w + P.o_dW1h; u.vec = w + P.o_vec; u.ones = a.ones;
+  u.dW1h = w + P.o_dW1h; u.vec = w + P.o_vec; u.ones = r.ones;
   hipLaunchKernelGGL(mono_unpack_k, dim3(64), dim3(256), 0, s, u);
   GNF_LAUNCH_CHECK();
   return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t gnf_monotonic_pack_floats(const gnf_mono_net* net) {
+  const int HT = pick_ht(net);
+  if (HT < 0) return GNF_ESHAPE;
+  return net_layout(net, HT).pack_floats;
+}
+
+int gnf_monotonic_pack(const gnf_mono_net* net, float* pack, gnf_stream_t stream) {
+  const int HT = pick_ht(net);
+  if (HT < 0) return GNF_ESHAPE;
+  if (!pack || ((uintptr_t)pack & 15)) return GNF_EINVAL;   // the consumers read it in 16-byte pieces, some straight to LDS
+  PackArgs a;
+  a.net = *net;
+  a.L = net_layout(net, HT);
+  hipLaunchKernelGGL(mono_pack_k, dim3((a.L.pack_floats + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, pack);
+  GNF_LAUNCH_CHECK();
+  return 0;
+}
+
+const char* gnf_monotonic_fwd_kernel(void) { return g_fwd_kernel; }
+const char* gnf_monotonic_bwd_kernel(void) { return g_bwd_kernel; }
+
+int gnf_monotonic_fwd(const float* pack, const gnf_mono_net* net, const float* x, const float* h, int64_t h_sb,
+                      int64_t h_sd, int64_t h_sc, const float* cc_w, const float* cc_t, int S, float* z,
+                      float* jac, int64_t B, int64_t d, gnf_stream_t stream) {
+  return mono_fwd_any(pack, net, x, h, h_sb, h_sd, h_sc, cc_w, cc_t, S, z, jac, B, d, stream, false);
+}
+int gnf_monotonic_fwd_f32(const float* pack, const gnf_mono_net* net, const float* x, const float* h, int64_t h_sb,
+                          int64_t h_sd, int64_t h_sc, const float* cc_w, const float* cc_t, int S, float* z,
+                          float* jac, int64_t B, int64_t d, gnf_stream_t stream) {
+  return mono_fwd_any(pack, net, x, h, h_sb, h_sd, h_sc, cc_w, cc_t, S, z, jac, B, d, stream, true);
+}
+
+int gnf_monotonic_inv_scatter(const float* pack, const gnf_mono_net* net, const float* z, const float* h, int64_t h_sb,
+                              int64_t h_sd, int64_t h_sc, const float* cc_w, const float* cc_t, int S, float* x,
+                              const int32_t* x_row_off, int64_t x_sd, int64_t B, int64_t d, gnf_stream_t stream) {
+  MonoArgs a{};
+  const int go = prologue(net, kMaxNH, any_null(cc_w, cc_t), pack, nullptr, S, B, d, any_null(z, h, x), &a.L);
+  if (go <= 0) return go;
+  a.pack = pack;
+  a.h = h; a.h_sb = h_sb; a.h_sd = h_sd; a.h_sc = h_sc;
+  a.ccw = cc_w; a.cct = cc_t; a.S = S; a.zt = z; a.xo = x; a.n = B * d; a.d = d;
+  a.xo_row = x_row_off; a.xo_sd = x_sd;
+  return launch(inv_route(a.L, a.n, S), a, (hipStream_t)stream);      // (leaves the forward's reporter alone)
+}
+
+int gnf_monotonic_inv(const float* pack, const gnf_mono_net* net, const float* z, const float* h, int64_t h_sb,
+                      int64_t h_sd, int64_t h_sc, const float* cc_w, const float* cc_t, int S, float* x, int64_t B,
+                      int64_t d, gnf_stream_t stream) {
+  return gnf_monotonic_inv_scatter(pack, net, z, h, h_sb, h_sd, h_sc, cc_w, cc_t, S, x, nullptr, 0, B, d, stream);
+}
+
+int64_t gnf_monotonic_bwd_ws_bytes(const gnf_mono_net* net, int S, int64_t B, int64_t d) {
+  const int HT = pick_ht(net);
+  if (HT < 0) return GNF_ESHAPE;
+  const MonoLayout L = net_layout(net, HT);
+  const BwdWs mode = bwd_route(net, L, false).ws;      // (the workspace mode does not depend on true_f32)
+  if (B < 1) B = 1;                          // an empty batch needs no workspace; keep the plan arithmetic away from 0
+  const BwdPlan full = plan_bwd(L, S, B * d, 0, mode);
+  const int64_t want = full.total_floats * (int64_t)sizeof(float);
+  if (want <= kWsTarget) return want;
+  // bounded staging: at least one 16-element group per persistent wavefront
+  const BwdPlan fixed_only = plan_bwd(L, S, 16, 0, mode);
+  const int64_t min_bytes = fixed_only.total_floats * (int64_t)sizeof(float);
+  return kWsTarget > min_bytes ? kWsTarget : min_bytes;
+}
+
+int gnf_monotonic_bwd(const float* pack, const gnf_mono_net* net, const float* x, const float* h, int64_t h_sb,
+                      int64_t h_sd, int64_t h_sc, const float* cc_w, const float* cc_t, int S, const float* gz,
+                      const float* gjac, float* gx, float* gh, int64_t g_sb, int64_t g_sd, int64_t g_sc,
+                      float* const* gW, float* const* gb, void* ws, int64_t ws_bytes, int64_t B, int64_t d,
+                      gnf_stream_t stream) {
+  return mono_bwd_any(pack, net, x, h, h_sb, h_sd, h_sc, cc_w, cc_t, S, gz, gjac, gx, gh, g_sb, g_sd, g_sc, gW, gb, ws, ws_bytes, B,
+                      d, stream, false);
+}
+int gnf_monotonic_bwd_f32(const float* pack, const gnf_mono_net* net, const float* x, const float* h, int64_t h_sb,
+                          int64_t h_sd, int64_t h_sc, const float* cc_w, const float* cc_t, int S, const float* gz,
+                          const float* gjac, float* gx, float* gh, int64_t g_sb, int64_t g_sd, int64_t g_sc,
+                          float* const* gW, float* const* gb, void* ws, int64_t ws_bytes, int64_t B, int64_t d,
+                          gnf_stream_t stream) {
+  return mono_bwd_any(pack, net, x, h, h_sb, h_sd, h_sc, cc_w, cc_t, S, gz, gjac, gx, gh, g_sb, g_sd, g_sc, gW, gb, ws, ws_bytes, B,
+                      d, stream, true);
 }
 
 }  // extern "C"

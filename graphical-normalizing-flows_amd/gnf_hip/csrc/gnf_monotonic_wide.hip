@@ -1317,45 +1317,36 @@ __global__ __launch_bounds__(64 * kWaves, 2) void mono_fwd_wide_split_k(MonoArgs
   }
 }
 
-template <int HT, int NH>
-int launch_wide_fwd_split(const MonoArgs& a, hipStream_t s) {
-  const size_t lds = (size_t)WidePlanS<HT, NH>::total_bytes;
-  const int64_t groups = (a.n + kGE - 1) / kGE;
-  const unsigned grid = (unsigned)(groups < 512 ? groups : 512);        // persistent, two workgroups per CU
-  return (int)gnf_launch_lds(mono_fwd_wide_split_k<HT, NH>, dim3(grid), dim3(64 * kWaves), lds, s, a);
+// ---------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------
+// The (HT, NH) this unit instantiates.  Forward: H = 97..160 with two to four hidden layers.  Backward: the same without
+// (10, 4), whose plan exceeds the LDS.  Its split-bf16 chain: HT = 10 only -- H = 97..112 stays fp32: its contraction pads 112
+// to 128 and the in-register splits cost what the matrix pipe saves (tools/bench_mono_split.py, cfg2: 1.74 ms against 1.59).
+constexpr bool wide_fwd_has(int HT, int NH) { return (HT == 7 || HT == 10) && NH >= 2 && NH <= 4; }
+constexpr bool wide_bwd_has(int HT, int NH) { return wide_fwd_has(HT, NH) && !(HT == 10 && NH == 4); }
+constexpr bool wide_bwd_split_has(int HT, int NH) { return wide_bwd_has(HT, NH) && HT == 10; }
+
+// f(Int<HT>{}, Int<NH>{}) for a pair of wide_fwd_has (f narrows it with the predicates above); R{} for any other shape
+template <class F>
+auto with_wide(int HT, int NH, F f) {
+  using R = decltype(f(Int<7>{}, Int<2>{}));
+  auto nh = [&](auto ht) -> R {
+    return NH == 2 ? f(ht, Int<2>{}) : NH == 3 ? f(ht, Int<3>{}) : NH == 4 ? f(ht, Int<4>{}) : R{};
+  };
+  return HT == 7 ? nh(Int<7>{}) : HT == 10 ? nh(Int<10>{}) : R{};
 }
 
-template <int HT, int NH>
-int launch_wide_fwd(const MonoArgs& a, hipStream_t s) {
-  const size_t lds = (size_t)WidePlanF<HT, NH>::total * sizeof(float);
-  const int64_t groups = (a.n + kGE - 1) / kGE;
-  const int per_cu = lds * 3 <= (size_t)160 * 1024 ? 3 : 2;          // workgroups per CU (140 registers: up to 3 per SIMD)
-  const unsigned grid = (unsigned)(groups < 256 * per_cu ? groups : 256 * per_cu);   // persistent
-  return (int)gnf_launch_lds(mono_fwd_wide_k<HT, NH>, dim3(grid), dim3(64 * kWaves), lds, s, a);
-}
-
-template <int HT, int NH, bool SPLIT>
-int launch_wide(const MonoArgs& a, unsigned grid, hipStream_t s) {
-  const size_t lds = (size_t)WidePlan<HT, NH>::total * sizeof(float);
-  return (int)gnf_launch_lds(mono_bwd_wide_k<HT, NH, SPLIT>, dim3(grid), dim3(64 * kWideWaves), lds, s, a);
-}
-
-constexpr size_t kLds = 160 * 1024;
+unsigned persistent(int64_t groups, int64_t cap) { return (unsigned)(groups < cap ? groups : cap); }
 
 }  // namespace
 
 bool gnf_mono_bwd_wide_ok(const gnfmono::MonoLayout& L) {
-  if (L.c > 32) return false;
-#define GNF_WIDE_CASE(HT_, NH_) \
-  if (L.HT == HT_ && L.NH == NH_) return WidePlan<HT_, NH_>::total * sizeof(float) <= kLds;
-  GNF_WIDE_CASE(7, 2) GNF_WIDE_CASE(7, 3) GNF_WIDE_CASE(7, 4) GNF_WIDE_CASE(10, 2) GNF_WIDE_CASE(10, 3)
-#undef GNF_WIDE_CASE
-  return false;
-}
-
-unsigned gnf_mono_bwd_wide_grid(const gnfmono::MonoLayout&, int64_t n) {
-  const int64_t groups = (n + kGE - 1) / kGE;
-  return (unsigned)(groups < 256 ? groups : 256);     // one workgroup per CU, persistent
+  return L.c <= 32 && with_wide(L.HT, L.NH, [](auto ht, auto nh) {
+    constexpr int HT = decltype(ht)::value, NH = decltype(nh)::value;
+    if constexpr (wide_bwd_has(HT, NH)) return WidePlan<HT, NH>::total * sizeof(float) <= kLdsBudget;
+    else return false;
+  });
 }
 
 #ifdef GNF_WIDE_TIMING
@@ -1365,47 +1356,40 @@ extern "C" int gnf_debug_wide_stamps(unsigned long long* host, int enable) {
 }
 #endif
 
-extern "C" int gnf_gemm_split_enabled(void);
-
-int gnf_mono_bwd_wide_launch(const gnfmono::MonoArgs& a, unsigned grid, hipStream_t s, bool true_f32, const char* volatile* kernel) {
-  *kernel = "mono_bwd_wide_k<f32>";
-  if (!true_f32 && gnf_gemm_split_enabled()) {
-    *kernel = "mono_bwd_wide_k<split>";
-#define GNF_WIDE_CASE(HT_, NH_) \
-  if (a.L.HT == HT_ && a.L.NH == NH_) return launch_wide<HT_, NH_, true>(a, grid, s);
-    // H = 97..112 stays fp32: its contraction pads 112 to 128 and the in-register splits cost what the matrix pipe saves
-    // (tools/bench_mono_split.py, cfg2: 1.74 ms against 1.59)
-    GNF_WIDE_CASE(10, 2) GNF_WIDE_CASE(10, 3)
-#undef GNF_WIDE_CASE
-    *kernel = "mono_bwd_wide_k<f32>";
-  }
-#define GNF_WIDE_CASE(HT_, NH_) \
-  if (a.L.HT == HT_ && a.L.NH == NH_) return launch_wide<HT_, NH_, false>(a, grid, s);
-  GNF_WIDE_CASE(7, 2) GNF_WIDE_CASE(7, 3) GNF_WIDE_CASE(7, 4) GNF_WIDE_CASE(10, 2) GNF_WIDE_CASE(10, 3)
-#undef GNF_WIDE_CASE
-  return GNF_ESHAPE;
+gnfmono::MonoLaunch gnf_mono_bwd_wide_route(const gnfmono::MonoLayout& L, int64_t n, bool true_f32) {
+  const bool split = !true_f32 && gnf_gemm_split_enabled() && wide_bwd_split_has(L.HT, L.NH);
+  MonoLaunch r{nullptr, persistent((n + kGE - 1) / kGE, 256), 64 * kWideWaves, 0, true,      // one workgroup per CU
+               split ? "mono_bwd_wide_k<split>" : "mono_bwd_wide_k<f32>"};
+  r.kernel = with_wide(L.HT, L.NH, [&](auto ht, auto nh) -> MonoKernel {
+    constexpr int HT = decltype(ht)::value, NH = decltype(nh)::value;
+    if constexpr (wide_bwd_has(HT, NH)) {
+      r.lds = (size_t)WidePlan<HT, NH>::total * sizeof(float);
+      if constexpr (wide_bwd_split_has(HT, NH))
+        if (split) return mono_bwd_wide_k<HT, NH, true>;
+      return mono_bwd_wide_k<HT, NH, false>;
+    }
+    return nullptr;
+  });
+  return r;
 }
 
-bool gnf_mono_fwd_wide_ok(const gnfmono::MonoLayout& L) {
-  if (L.c > 32 || L.NH < 2 || L.NH > 4) return false;
-  return L.HT == 7 || L.HT == 10;
-}
+bool gnf_mono_fwd_wide_ok(const gnfmono::MonoLayout& L) { return L.c <= 32 && wide_fwd_has(L.HT, L.NH); }
 
-extern "C" int gnf_gemm_split_enabled(void);
-
-int gnf_mono_fwd_wide_launch(const gnfmono::MonoArgs& a, hipStream_t s, bool true_f32, const char* volatile* kernel) {
-  *kernel = "mono_fwd_wide_k";
-  if (!true_f32 && gnf_gemm_split_enabled()) {
-    *kernel = "mono_fwd_wide_split_k";                     // bf16 matrix pipe, exact 3 x bf16 splits (GNF_TRUE_F32=1: fp32 MFMA)
-#define GNF_WIDE_CASE(HT_, NH_) \
-  if (a.L.HT == HT_ && a.L.NH == NH_) return launch_wide_fwd_split<HT_, NH_>(a, s);
-    GNF_WIDE_CASE(7, 2) GNF_WIDE_CASE(7, 3) GNF_WIDE_CASE(7, 4) GNF_WIDE_CASE(10, 2) GNF_WIDE_CASE(10, 3) GNF_WIDE_CASE(10, 4)
-#undef GNF_WIDE_CASE
-    *kernel = "mono_fwd_wide_k";
-  }
-#define GNF_WIDE_CASE(HT_, NH_) \
-  if (a.L.HT == HT_ && a.L.NH == NH_) return launch_wide_fwd<HT_, NH_>(a, s);
-  GNF_WIDE_CASE(7, 2) GNF_WIDE_CASE(7, 3) GNF_WIDE_CASE(7, 4) GNF_WIDE_CASE(10, 2) GNF_WIDE_CASE(10, 3) GNF_WIDE_CASE(10, 4)
-#undef GNF_WIDE_CASE
-  return GNF_ESHAPE;
+gnfmono::MonoLaunch gnf_mono_fwd_wide_route(const gnfmono::MonoLayout& L, int64_t n, bool true_f32) {
+  // bf16 matrix pipe, exact 3 x bf16 splits (GNF_TRUE_F32=1: fp32 MFMA)
+  const bool split = !true_f32 && gnf_gemm_split_enabled();
+  const int64_t groups = (n + kGE - 1) / kGE;
+  MonoLaunch r{nullptr, 0, 64 * kWaves, 0, true, split ? "mono_fwd_wide_split_k" : "mono_fwd_wide_k"};
+  r.kernel = with_wide(L.HT, L.NH, [&](auto ht, auto nh) -> MonoKernel {
+    constexpr int HT = decltype(ht)::value, NH = decltype(nh)::value;
+    if (split) {
+      r.lds = (size_t)WidePlanS<HT, NH>::total_bytes;
+      r.grid = persistent(groups, 512);                            // two workgroups per CU
+      return mono_fwd_wide_split_k<HT, NH>;
+    }
+    r.lds = (size_t)WidePlanF<HT, NH>::total * sizeof(float);
+    r.grid = persistent(groups, 256 * (r.lds * 3 <= kLdsBudget ? 3 : 2));     // (140 registers: up to 3 workgroups per SIMD)
+    return mono_fwd_wide_k<HT, NH>;
+  });
+  return r;
 }

@@ -154,7 +154,8 @@ def test_split_forward_ragged_sizes_and_strided_h():
         assert torch.allclose(zs, zf, rtol=2e-6, atol=2e-6) and torch.allclose(js, jf, rtol=2e-6, atol=2e-6), (B, d)
 
 
-def _bwd(entry, params, x, h, S, gz, gjac):
+def _bwd(entry, params, x, h, S, gz, gjac, ws_bytes=None):
+    """ws_bytes: the workspace handed to the entry point (default: what gnf_monotonic_bwd_ws_bytes asks for this problem)"""
     from gnf_hip import abi, ops
     from gnf_hip.abi import call, ptr, stream
     net = ops._mono_net(params)
@@ -166,7 +167,7 @@ def _bwd(entry, params, x, h, S, gz, gjac):
     nl = net.nl
     gW = (ctypes.c_void_p * nl)(*[gp[2 * l].data_ptr() for l in range(nl)])
     gb = (ctypes.c_void_p * nl)(*[gp[2 * l + 1].data_ptr() for l in range(nl)])
-    nbytes = abi.load().gnf_monotonic_bwd_ws_bytes(ctypes.byref(net), S, B, d)
+    nbytes = abi.load().gnf_monotonic_bwd_ws_bytes(ctypes.byref(net), S, B, d) if ws_bytes is None else ws_bytes
     ws = torch.empty(max(nbytes // 4, 1), device=x.device)
     call(entry, ptr(pack), ctypes.byref(net), ptr(x), ptr(h), h.stride(0), h.stride(1), h.stride(2), ptr(w), ptr(t), S, ptr(gz), ptr(gjac),
          ptr(gx), ptr(gh), gh.stride(0), gh.stride(1), gh.stride(2), gW, gb, ctypes.c_void_p(ws.data_ptr()), ws.numel() * 4, B, d, stream())
@@ -305,6 +306,49 @@ def test_split_backward_ragged_sizes():
             num, den = float((a - b).double().pow(2).sum().sqrt()), float(b.double().pow(2).sum().sqrt())
             mx = float((a - b).abs().max()) / (float(b.abs().max()) + 1e-30)
             assert num <= 2e-3 * den + 1e-7 and mx <= 2e-2, (B, d, nm, num / (den + 1e-30), mx)
+
+
+# one net per backward family, each the smallest that reaches it: peeled pair kernel (in-kernel dW), pair kernel, ones column
+# (staged dW through the split-K GEMM, GNF_GEMM_ACCUM across chunks), whole image, wide, HT 7 outside the wide kernel
+# (mono_dw_k with acc), HT 16 (tall row-sums of staged rows)
+CHUNKED = [([50, 50, 50], 30, "gnf_monotonic_bwd"), ([20, 20], 5, "gnf_monotonic_bwd"), ([48, 50, 50, 50], 5, "gnf_monotonic_bwd"),
+           ([40, 64, 24], 5, "gnf_monotonic_bwd"), ([150, 150, 150], 30, "gnf_monotonic_bwd"),
+           ([150, 150, 150], 30, "gnf_monotonic_bwd_f32"), ([100, 100], 33, "gnf_monotonic_bwd"), ([200, 200], 8, "gnf_monotonic_bwd")]
+
+
+@pytest.mark.parametrize("hidden,c,entry", CHUNKED)
+def test_chunked_backward_vs_fp64_and_full_workspace(hidden, c, entry):
+    """a workspace that holds one 16-element chunk: n = 40 runs as chunks of 16, 16 and 8 (the last one ragged), every staged
+    product and partial row accumulated across them.  Against fp64 the chunked evaluation is held to what
+    test_split_backward_vs_fp64_and_fp32_mfma asks of two evaluation orders: per tensor within 2x of the one-chunk run's
+    error plus one epsilon.  The same kernel family runs either way."""
+    from gnf_hip import abi, ops
+    B, d, S = 5, 8, 20
+    params = _params(hidden, c, seed=sum(hidden) + c, scale=1.3)
+    g = torch.Generator().manual_seed(len(hidden) + c)
+    x = (torch.randn(B, d, generator=g) * 2.).to(DEV)
+    h = torch.randn(B, d, c, generator=g).to(DEV)
+    gz, gjac = torch.randn(B, d, generator=g).to(DEV), torch.randn(B, d, generator=g).to(DEV)
+    net = ops._mono_net(params)
+    one_chunk = abi.load().gnf_monotonic_bwd_ws_bytes(ctypes.byref(net), S, 1, 1)
+    assert 0 < one_chunk < abi.load().gnf_monotonic_bwd_ws_bytes(ctypes.byref(net), S, B, d)
+    gf, kf = _bwd(entry, params, x, h, S, gz, gjac)
+    gc, kc = _bwd(entry, params, x, h, S, gz, gjac, ws_bytes=one_chunk)
+    assert kc == kf, (kc, kf)
+    g64 = _bwd64(params, x, h, S, gz, gjac)
+    names = ["gx", "gh"] + ["gW%d" % (i // 2) if i % 2 == 0 else "gb%d" % (i // 2) for i in range(len(params))]
+    rows = []
+    for nm, a, b, r in zip(names, gc, gf, g64):
+        scale = float(r.abs().max()) + 1e-30
+        es, ef = float((a.double() - r).abs().max()) / scale, float((b.double() - r).abs().max()) / scale
+        rs = float(((a.double() - r).pow(2).mean() / (r.pow(2).mean() + 1e-60)).sqrt())
+        rf = float(((b.double() - r).pow(2).mean() / (r.pow(2).mean() + 1e-60)).sqrt())
+        rows.append((nm, es, ef, rs, rf))
+    print("\n[mono chunked bwd %s c=%d %s] %s; max rel. error chunked | full (rms chunked | full): " % (hidden, c, entry, kc)
+          + ", ".join("%s %.1e|%.1e (%.1e|%.1e)" % r_ for r_ in rows))
+    for nm, es, ef, rs, rf in rows:
+        assert rs <= 2. * rf + 1.2e-7, (nm, es, ef, rs, rf)
+        assert es <= 2. * ef + 2.4e-7, (nm, es, ef, rs, rf)
 
 
 def test_true_f32_switch_selects_the_fp32_kernel():

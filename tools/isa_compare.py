@@ -5,7 +5,8 @@
 
 Every unit of gnf_hip/build.py's SOURCES is compiled to device assembly with that tree's own FLAGS / EXTRA_FLAGS; comments
 and the per-compile __hip_cuid_ symbol are dropped, the function ordinal in local labels is removed.  Per kernel: `same`, or the resources and instruction count of both sides.
-Exit status 1 if anything differs."""
+Kernels that only changed their order in the unit (templates instantiated in another order) count as the same and are
+reported as `reordered`.  Exit status 1 if anything differs."""
 import os
 import re
 import runpy
@@ -74,7 +75,7 @@ def main():
                 differs = True
                 continue
             (fa, ma, ra), (fb, mb, rb) = split(la), split(lb)
-            print("%s: %d functions, %s" % (u, len(fb), "identical" if la == lb else "DIFFERS"))
+            print("%s: %d functions, %s" % (u, len(fb), "identical" if la == lb else "not identical, kernel by kernel:"))
             for k in sorted(set(fa) | set(fb)):
                 if fa.get(k) == fb.get(k) and ma.get(k) == mb.get(k):
                     print("  same     %s" % k)
@@ -83,9 +84,11 @@ def main():
                 print("  DIFFERS  %s" % k)
                 for side, f, m in (("A", fa, ma), ("B", fb, mb)):
                     print("    %s: %s" % (side, describe(f[k], m.get(k, {})) if k in f else "absent"))
-            if ra != rb:                 # descriptors, metadata, data: reported once per unit
+            if sorted(ra) != sorted(rb):   # descriptors, metadata, data: reported once per unit
                 differs = True
                 print("  DIFFERS  (outside the function bodies)")
+            elif ra != rb:               # the same lines: templates instantiated in another order move whole kernels (each in its
+                print("  reordered  (outside the function bodies: the same lines in another order)")    # own section, 256-B aligned)
     return 1 if differs else 0
 
 
