@@ -149,6 +149,14 @@ SIGNATURES = {
     "gnf_lenet_rows_bwd": (c_int, [c_f, c_f, c_i64, ctypes.c_void_p, c_i64, c_int, c_int, c_int, c_int, c_f, c_f, c_f, c_f,
                                    ctypes.c_void_p, c_f, c_int, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p, c_i64, c_i64,
                                    c_stream]),
+    "gnf_dagmlp_supported": (c_int, [c_i64, c_i64]),
+    "gnf_dagmlp_gated_fwd": (c_int, [c_f, c_f, c_f, c_int, c_int, c_float, c_float, c_f, c_f, c_u64, c_u64, c_f, c_i64, c_f,
+                                     c_int, c_int, c_f, c_i64, c_i64, c_i64, c_stream]),
+    "gnf_dagmlp_gated_bwd_ws_bytes": (c_i64, [c_i64, c_i64, c_i64]),
+    "gnf_dagmlp_gated_bwd": (c_int, [c_f, c_f, c_int, c_int, c_float, c_f, c_f, c_u64, c_u64, c_f, c_i64, c_int, c_f, c_f,
+                                     c_f, c_int, c_f, c_i64, c_f, ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_stream]),
+    "gnf_dagmlp_rows_fwd": (c_int, [c_f, c_f, c_i64, ctypes.c_void_p, c_i64, c_f, c_i64, c_f, c_int, c_int, c_f, c_int,
+                                    c_i64, c_i64, c_i64, c_stream]),
     "gnf_mnistcnn_sparse_ws_bytes": (c_i64, [c_i64, c_i64]),
     "gnf_mnistcnn_sparse_fwd": (c_int, [c_f, c_i64, c_f, ctypes.c_void_p, c_i64, ctypes.c_void_p, c_i64, c_f, c_f, c_f,
                                         c_f, c_f, c_f, c_i64, c_f, c_f, ctypes.c_void_p, ctypes.c_void_p, c_i64,

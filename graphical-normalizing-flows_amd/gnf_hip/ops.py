@@ -1067,6 +1067,100 @@ def dag_lenet_front(x, A, imp_mode, gate_mode, h_thresh, temperature, u1, u2, se
                                  size_img, k, torch.is_grad_enabled())
 
 
+# ----------------------------------------------------------------------------- DAGMLP first layer behind the gate
+def dagmlp_supported(d, H):
+    """the shapes gnf_dagmlp_* takes (1 <= d <= 64, H >= 1)"""
+    return bool(abi.load().gnf_dagmlp_supported(int(d), int(H)))
+
+
+def _first_layer(W1, b1, d, hot):
+    """W1, b1 of the first Linear as the kernels want them: rows of unit stride, (2 d | d) columns"""
+    if W1.dim() != 2 or W1.shape[1] != (2 * d if hot else d) or tuple(b1.shape) != (W1.shape[0],):
+        raise abi.GnfError("the fused DAGMLP front needs W1 [H, %d] and b1 [H]" % (2 * d if hot else d))
+    return W1.contiguous(), b1.contiguous()
+
+
+class DagMlpFrontFn(torch.autograd.Function):
+    """act(Linear_1(e)) on the masked copies e[b*d+i, :] = (x[b, :] * gate(importance(A[i, :])) | one-hot(i)) as ONE autograd
+    node whose kernels build each copy in LDS (csrc/gnf_dagmlp.hip, gnf_dagmlp_gated_*): DagGateFn and the first layer of
+    MLPFn without e [B*d, 2d] or its cotangent in memory; the one-hot half of the layer is column d+i of W1.  act = ReLU
+    (relu) -- the consumer (MLPFn with relu_in) then returns the cotangent already multiplied by [a1 > 0] -- or the identity.
+    Saved: x, A, (u1, u2), W1, b1 and the gate table; the noise is regenerated.  Differentiable w.r.t. x, A, W1, b1."""
+
+    @staticmethod
+    def forward(ctx, x, A, imp_mode, gate_mode, h_thresh, temperature, u1, u2, seed, offset, W1, b1, hot, relu):
+        x, A = x.contiguous(), A.contiguous()
+        B, d = x.shape
+        if tuple(A.shape) != (d, d):
+            raise abi.GnfError("the fused DAGMLP front needs x [B, %d] and A [%d, %d]" % (d, d, d))
+        W1c, b1c = _first_layer(W1, b1, d, hot)
+        H = W1c.shape[0]
+        u1 = u1.contiguous() if u1 is not None else None
+        u2 = u2.contiguous() if u2 is not None else None
+        tab = torch.empty(max(int(abi.load().gnf_dag_gate_fwd_ws_bytes(d)) // 4, 1), dtype=torch.float32, device=x.device)
+        a1 = _empty((B * d, H), x)
+        call("gnf_dagmlp_gated_fwd", ptr(x), ptr(A), ptr(tab), imp_mode, gate_mode, float(h_thresh), float(temperature),
+             ptr(u1), ptr(u2), seed, offset, ptr(W1c), W1c.stride(0), ptr(b1c), int(bool(hot)), int(bool(relu)), ptr(a1), B,
+             d, H, stream())
+        ctx.save_for_backward(x, A, u1, u2, tab, W1c, b1c)
+        ctx.cfg = (imp_mode, gate_mode, float(temperature), seed, offset, bool(hot))
+        return a1
+
+    @staticmethod
+    def backward(ctx, g):
+        x, A, u1, u2, tab, W1, b1 = ctx.saved_tensors
+        imp_mode, gate_mode, temperature, seed, offset, hot = ctx.cfg
+        B, d = x.shape
+        H = W1.shape[0]
+        g = g.contiguous()
+        gx = _empty((B, d), x) if ctx.needs_input_grad[0] else None
+        gA, finish_A, acc = grad_out_shared(A, accumulate_ok=True) if ctx.needs_input_grad[1] else (None, None, False)
+        gW1 = grad_out(W1) if ctx.needs_input_grad[10] else None
+        gb1 = grad_out(b1) if ctx.needs_input_grad[11] else None
+        nws = abi.load().gnf_dagmlp_gated_bwd_ws_bytes(B, d, H)
+        ws = _ws(nws, x)
+        call("gnf_dagmlp_gated_bwd", ptr(x), ptr(tab), imp_mode, gate_mode, temperature, ptr(u1), ptr(u2), seed, offset,
+             ptr(W1), W1.stride(0), int(hot), ptr(g), ptr(gx), ptr(gA), int(acc), ptr(gW1),
+             gW1.stride(0) if gW1 is not None else 0, ptr(gb1), abi.rawptr(ws), nws, B, d, H, stream())
+        return (gx, (finish_A(gA) if gA is not None else None), None, None, None, None, None, None, None, None, gW1, gb1,
+                None, None)
+
+
+def dag_mlp_front(x, A, imp_mode, gate_mode, h_thresh, temperature, u1, u2, seed, offset, W1, b1, hot, relu):
+    """a1 [B*d, H] = act(first DAGMLP layer) of the masked copies of x (DagMlpFrontFn); feed the rest of the chain with
+    mlp(a1, layers[1:], relu_in=True)"""
+    return DagMlpFrontFn.apply(x, A, imp_mode, gate_mode, h_thresh, temperature, u1, u2, seed, offset, W1, b1, bool(hot),
+                               bool(relu))
+
+
+def dag_mlp_rows(x, P, rows32, W1, b1, hot, relu, variable_major=False):
+    """act(first DAGMLP layer) on the copies (x[b] * P[rows32[r]] | one-hot(rows32[r])) of a deterministic gate (rows32: int32
+    device indices, None = all d rows in order): [B*R, H] in the row order b*R + r, or r*B + b when variable_major.  The
+    copies are built in LDS (gnf_dagmlp_rows_fwd).  Evaluation only: a plain function, no autograd node."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, P, W1, b1)):
+        raise abi.GnfError("dag_mlp_rows has no backward: call it under torch.no_grad() or on operands without requires_grad")
+    x = x.contiguous()
+    B, d = x.shape
+    if tuple(P.shape) != (d, d):
+        raise abi.GnfError("dag_mlp_rows needs x [B, %d] and P [%d, %d]" % (d, d, d))
+    if P.stride(1) != 1 or P.stride(0) < d:
+        P = P.contiguous()
+    if rows32 is None:
+        R = d
+    else:
+        if rows32.dtype != torch.int32 or rows32.device != x.device:
+            raise abi.GnfError("dag_mlp_rows: rows32 must be an int32 tensor on the device of x")
+        rows32 = rows32.contiguous()
+        R = rows32.numel()
+    W1c, b1c = _first_layer(W1.detach(), b1.detach(), d, hot)
+    H = W1c.shape[0]
+    a1 = _empty((B * R, H), x)
+    call("gnf_dagmlp_rows_fwd", ptr(x), ptr(P), P.stride(0), abi.rawptr(rows32) if rows32 is not None and R else None, R,
+         ptr(W1c), W1c.stride(0), ptr(b1c), int(bool(hot)), int(bool(relu)), ptr(a1), int(bool(variable_major)), B, d, H,
+         stream())
+    return a1
+
+
 # ----------------------------------------------------------------------------- Monotonic (UMNN) normalizer
 _CC = {}
 

@@ -7,8 +7,17 @@ from gnf_hip import ops
 from .Conditioner import Conditioner, linear_pairs, no_context
 
 
+# DAGMLP.gated_front of a new net; the measurement behind the value: profiles/dagmlp_gated_ab.txt
+DAGMLP_GATED_FRONT_DEFAULT = False
+
+
 class DAGMLP(nn.Module):
-    """Parameter container, same layout/keys as reference DAGConditioner.py:7-20."""
+    """Parameter container, same layout/keys as reference DAGConditioner.py:7-20.  `gated_front = True` lets a DAG
+    conditioner hand over x, A and its gate (or, for a deterministic gate without autograd, the importance matrix and row
+    indices) instead of the masked copies: the first layer's kernels build each copy in LDS and add the one-hot half of the
+    layer as a column of the weight (gnf_hip.ops.DagMlpFrontFn / dag_mlp_rows), the rest of the chain is ops.mlp."""
+
+    accepts_hot = True                  # forward_gated / forward_rows take the conditioner's hot_encoding flag
 
     def __init__(self, in_size, hidden, out_size, cond_in=0):
         super(DAGMLP, self).__init__()
@@ -19,9 +28,44 @@ class DAGMLP(nn.Module):
             layers += [nn.Linear(h1, h2), nn.ReLU()]
         layers.pop()
         self.net = nn.Sequential(*layers)
+        self.gated_front = DAGMLP_GATED_FRONT_DEFAULT
 
     def forward(self, x):
         return ops.mlp(x, linear_pairs(self.net))
+
+    def _front_fits(self, x, hot):
+        if not getattr(self, "gated_front", False) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2:
+            return False
+        W1 = linear_pairs(self.net)[0][0]
+        d = x.shape[1]
+        return (W1.is_cuda and W1.dtype == torch.float32 and W1.shape[1] == (2 * d if hot else d)
+                and ops.dagmlp_supported(d, W1.shape[0]))
+
+    def supports_gated(self, x, hot):
+        """the gate of a DAG conditioner + the first layer as one autograd node (gnf_hip.ops.DagMlpFrontFn): a [B, d] fp32
+        batch on the GPU, d <= 64, the first Linear [H, d] (hot: [H, 2 d])"""
+        return self._front_fits(x, hot)
+
+    def forward_gated(self, x, A, imp_mode, gate_mode, h_thresh, temperature, u1, u2, seed, offset, hot):
+        """net(e) for e[b*d+i] = (x[b] * gate(importance(A[i])) | one-hot(i)) without e in memory: [B*d, out]"""
+        layers = linear_pairs(self.net)
+        a1 = ops.dag_mlp_front(x, A, imp_mode, gate_mode, h_thresh, temperature, u1, u2, seed, offset, layers[0][0],
+                               layers[0][1], hot, len(layers) > 1)
+        return ops.mlp(a1, layers[1:], relu_in=True) if len(layers) > 1 else a1
+
+    def supports_rows(self, x, hot):
+        """the copies x[b] * P[i] of a deterministic gate built inside the first layer (gnf_hip.ops.dag_mlp_rows);
+        evaluation only, the caller checks that autograd is off"""
+        return self._front_fits(x, hot)
+
+    def forward_rows(self, x, P, rows32, variable_major=False, hot=False):
+        """net((x[b] * P[rows32[r]] | one-hot)) (rows32 None: every row of P) without the copies in memory: [B, R, out], or
+        [R, B, out] when variable_major -- written in that order"""
+        layers = linear_pairs(self.net)
+        B, R = x.shape[0], (x.shape[1] if rows32 is None else rows32.numel())
+        a1 = ops.dag_mlp_rows(x, P, rows32, layers[0][0], layers[0][1], hot, len(layers) > 1, variable_major)
+        out = ops.mlp(a1, layers[1:], relu_in=True) if len(layers) > 1 else a1
+        return out.view(R, B, out.shape[-1]) if variable_major else out.view(B, R, out.shape[-1])
 
 
 def _digraph(adj):
@@ -204,12 +248,19 @@ class DAGConditioner(Conditioner):
         autograd on only behind a frozen gate -- P needs no gradient -- and when the net offers the training form
         (`rows_train_front`: gradients for the net's parameters and for x)"""
         net = self.embedding_net
-        if (self.hot_encoding or self.cond_in or not hasattr(net, "supports_rows") or x.dim() != 2
+        takes_hot = getattr(net, "accepts_hot", False)       # only DAGMLP builds the one-hot half itself
+        if ((self.hot_encoding and not takes_hot) or self.cond_in or not hasattr(net, "supports_rows") or x.dim() != 2
                 or x.shape[1] != self.in_size):
             return False
         if not torch.is_grad_enabled():
-            return net.supports_rows(x)
+            return net.supports_rows(x, bool(self.hot_encoding)) if takes_hot else net.supports_rows(x)
         return not P.requires_grad and hasattr(net, "supports_rows_train") and net.supports_rows_train(x)
+
+    def _net_rows(self, x, P, rows32, variable_major):
+        net = self.embedding_net
+        if getattr(net, "accepts_hot", False):
+            return net.forward_rows(x, P, rows32, variable_major, bool(self.hot_encoding))
+        return net.forward_rows(x, P, rows32, variable_major)
 
     def forward(self, x, context=None):
         no_context(context, self.cond_in)
@@ -219,14 +270,16 @@ class DAGConditioner(Conditioner):
             if plan is not None:
                 return self.embedding_net.sparse_rows(x, P, plan)
             if self._rows_front(x, P):
-                return self.embedding_net.forward_rows(x, P, None, False)      # all d rows, neither e nor a gate table
+                return self._net_rows(x, P, None, False)                       # all d rows, neither e nor a gate table
         if hasattr(self.embedding_net, "exact_pool_ties"):
             # deterministic gate on the dense kernels (trainable A, or a gradient wanted for x): the masked copies
             # have exactly-constant regions, so the embedding net must break pool ties the way torch does
             self.embedding_net.exact_pool_ties = P is not None
         net = self.embedding_net
-        if (getattr(self, "fused_front", True) and not self.hot_encoding and not self.cond_in and hasattr(net, "forward_gated")
-                and x.shape[1] == self.in_size and net.supports_gated(x)):
+        takes_hot = getattr(net, "accepts_hot", False)
+        if (getattr(self, "fused_front", True) and (not self.hot_encoding or takes_hot) and not self.cond_in
+                and hasattr(net, "forward_gated") and x.dim() == 2 and x.shape[1] == self.in_size
+                and (net.supports_gated(x, bool(self.hot_encoding)) if takes_hot else net.supports_gated(x))):
             imp, gate = self._modes()
             if gate != ops.GATE_GUMBEL or self.gumble:
                 # gate + conv front as ONE autograd node: with x frozen its backward skips the entries of dL/de that
@@ -236,7 +289,7 @@ class DAGConditioner(Conditioner):
                     u1, u2 = self.gate_noise
                 self._gate_calls += 1
                 h = net.forward_gated(x, self.A, imp, gate, float(self.h_thresh), float(self.gumble_T), u1, u2,
-                                      self.gate_seed, self._gate_calls)
+                                      self.gate_seed, self._gate_calls, *((bool(self.hot_encoding),) if takes_hot else ()))
                 return h.view(x.shape[0], self.in_size, -1)
         e = self.masked_inputs(x)
         return self.embedding_net(e).view(x.shape[0], self.in_size, -1)
@@ -441,7 +494,7 @@ class DAGConditioner(Conditioner):
         if plan is not None:
             return self.embedding_net.sparse_rows(x, P, plan, variable_major=variable_major)
         if self._rows_front(x, P):
-            return self.embedding_net.forward_rows(x, P, rows.to(torch.int32) if rows32 is None else rows32, variable_major)
+            return self._net_rows(x, P, rows.to(torch.int32) if rows32 is None else rows32, variable_major)
         if variable_major:
             return self.forward_rows(x, rows, P, host_rows).permute(1, 0, 2)
         if hasattr(self.embedding_net, "exact_pool_ties"):

@@ -187,6 +187,7 @@ class NormalizingFlowStep(NormalizingFlow):
         # (values may change freely; a re-bound or moved tensor must not be read through a stale pointer)
         key = (tuple(z.shape), int(getattr(self.normalizer, "nb_steps", 0)), bool(getattr(cond, "sparse_front", False)),
                bool(getattr(getattr(cond, "embedding_net", None), "rows_front", False)),
+               bool(getattr(getattr(cond, "embedding_net", None), "gated_front", False)),
                tuple(t.data_ptr() for t in self.parameters()), tuple(t.data_ptr() for t in self.buffers()))
         graphs = _INV_GRAPHS.setdefault(self, {})
         entry = graphs.get(key)

@@ -67,7 +67,12 @@ def build(args, dim):
     if norm_t is MonotonicNormalizer:
         nargs = {"integrand_net": args.int_net, "cond_size": args.emb_net[-1], "nb_steps": args.nb_steps,
                  "solver": args.solver}
-    return buildFCNormalizingFlow(args.nb_flow, cond_t, cargs, norm_t, nargs), cond_t, norm_t
+    model = buildFCNormalizingFlow(args.nb_flow, cond_t, cargs, norm_t, nargs)
+    if getattr(args, "gated_front", False):      # DAG gate and one-hot built inside the first DAGMLP layer (csrc/gnf_dagmlp.hip)
+        for c in model.getConditioners():
+            if hasattr(getattr(c, "embedding_net", None), "gated_front"):
+                c.embedding_net.gated_front = True
+    return model, cond_t, norm_t
 
 
 @torch.no_grad()
@@ -214,6 +219,8 @@ def parse(argv=None):
     ap.add_argument("-int_net", default=[100, 100, 100, 100], nargs="+", type=int)
     ap.add_argument("-nb_steps", default=20, type=int)
     ap.add_argument("-solver", default="CC", type=str, choices=["CC", "CCParallel"])
+    ap.add_argument("-gated_front", default=False, action="store_true",
+                    help="DAGMLP.gated_front = True on every DAG conditioner: gate and one-hot fused into the first layer")
     args = ap.parse_args(argv)
     if args.load_config is not None:                         # a named entry of the yml overrides the command line
         with open(args.config_file) as f:

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-/* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_* and gnf_image_prep were ADDED under this number (no existing symbol
+/* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_*, gnf_image_prep and gnf_dagmlp_* were ADDED under this number (no existing symbol
  * changed; a binding written against the earlier 11 keeps working, and tests/test_cifar_factory.py pins the value) */
 #define GNF_ABI_VERSION 11
 #define GNF_EINVAL (-1)   /* bad argument (null pointer, negative size, ...)          */
@@ -523,6 +523,49 @@ int gnf_lenet_rows_bwd(const float* x, const float* P, int64_t ld_p, const int32
                        const unsigned char* argmax2, const float* g_feat, int variable_major,
                        float* gx, float* gW1, float* gb1, float* gW2, float* gb2,
                        void* ws, int64_t ws_bytes, int64_t B, gnf_stream_t stream);
+
+/* ---- DAG gate and one-hot fused into the first layer of a DAGMLP (DAGConditioner.py:7-20, 94-169) ---------------
+ * The tabular DAG flows feed the masked copies e[b*d + i, :] = (x[b, :] * gate(b, i, :) | one-hot(i)) to a Linear/ReLU
+ * chain.  These entry points compute the first layer on copies built in LDS,
+ *   a1[b*d + i, n] = act( b1[n] + [hot] W1[n, d + i] + sum_{j<d} W1[n, j] * x[b, j] * gate(b, i, j) ),
+ * act = ReLU (relu != 0) or the identity: neither e nor its cotangent exists in memory, and the one-hot half of the layer
+ * is a column of W1 added in the epilogue.  Gate settings, the injected uniforms u1, u2 ([B*d, d]) and the Philox counter
+ * ((b*d + i) * ceil(d/4) + j/4) are those of gnf_dag_gate_fwd: the copies have the bits that entry point writes.
+ * Domain: 1 <= d <= 64, 1 <= H <= 2^20 (gnf_dagmlp_supported; GNF_ESHAPE from every entry point outside it, nothing is
+ * launched), B >= 0.  x [B, d] contiguous; A [d, d] contiguous; W1 [H, >= d (hot: 2 d)] rows of pitch ld_w; b1 [H];
+ * a1 and g [B*d, H] contiguous.  tab: caller-owned, gnf_dag_gate_fwd_ws_bytes(d) bytes; the forward fills it from A, the
+ * backward reads it.  Any dword address for every array (16-byte alignment selects the 16-byte loads and stores, the
+ * summation order is the same).  B == 0: batch-sized pointers may be NULL, no tile kernel is launched (the forward still
+ * fills tab), and the backward writes zero parameter gradients. */
+int gnf_dagmlp_supported(int64_t d, int64_t H);
+int gnf_dagmlp_gated_fwd(const float* x, const float* A, float* tab, int imp_mode, int gate_mode,
+                         float h_thresh, float temperature, const float* u1, const float* u2,
+                         uint64_t seed, uint64_t offset, const float* W1, int64_t ld_w, const float* b1,
+                         int hot, int relu, float* a1, int64_t B, int64_t d, int64_t H, gnf_stream_t stream);
+/* Backward: g = dL/da1, ALREADY multiplied by [a1 > 0] when the forward applied the ReLU.  Every output may be NULL:
+ *   gx  [B, d]      gx[b, j] = sum_i de[b*d+i, j] * d e / d x  (the gate; P for the deterministic and the noise gate),
+ *                   de = g W1[:, :d] kept on chip;
+ *   gA  [d, d]      dP/dA * sum_b de * d e / d p   (accumulate != 0: added to what gA holds; B == 0 then leaves it alone);
+ *   gW1 [H, ..]     rows of pitch ld_gw: columns [0, d) = g^T e and, with hot, [d, 2 d) = sum_b g[b*d+i, :]; columns behind
+ *                   them are not touched;
+ *   gb1 [H]         column sums of g.
+ * The noise is regenerated; nothing but tab is kept from the forward.  Per-workgroup partial sums go through ws
+ * (>= gnf_dagmlp_gated_bwd_ws_bytes(B, d, H) bytes, else GNF_EWS) and are added in workgroup order: no float atomics, the
+ * same call returns the same bits. */
+int64_t gnf_dagmlp_gated_bwd_ws_bytes(int64_t B, int64_t d, int64_t H);
+int gnf_dagmlp_gated_bwd(const float* x, const float* tab, int imp_mode, int gate_mode, float temperature,
+                         const float* u1, const float* u2, uint64_t seed, uint64_t offset,
+                         const float* W1, int64_t ld_w, int hot, const float* g,
+                         float* gx, float* gA, int accumulate, float* gW1, int64_t ld_gw, float* gb1,
+                         void* ws, int64_t ws_bytes, int64_t B, int64_t d, int64_t H, gnf_stream_t stream);
+/* The same first layer on rows of a DETERMINISTIC gate (inversion by levels, evaluation): copy (b, r) is
+ * x[b, :] * P[i, :], i = rows[r] (rows == NULL: i = r, R <= d), one fp32 product per element; with hot the epilogue adds
+ * W1[n, d + i].  P [d, d] rows of pitch ld_p; rows: R int32 device indices in [0, d), repeats allowed, not checked.
+ * a1: row b*R + r, or r*B + b when variable_major != 0 (64-bit offsets), pitch H.  Forward only, no table.
+ * B == 0 or R == 0: returns 0 without a launch. */
+int gnf_dagmlp_rows_fwd(const float* x, const float* P, int64_t ld_p, const int32_t* rows, int64_t R,
+                        const float* W1, int64_t ld_w, const float* b1, int hot, int relu, float* a1,
+                        int variable_major, int64_t B, int64_t d, int64_t H, gnf_stream_t stream);
 
 /* ---- sparse masked-image front for a DETERMINISTIC DAG gate ---------------
  * Replaces, for evaluation / sampling, the chain  e = x * P[i]  (DAGConditioner.py:142-153, deterministic branches)
