@@ -23,6 +23,7 @@ MONO_MAX_LAYERS = 8
 MADE_MAX_HIDDEN = 8       # GNF_MADE_MAX_HIDDEN
 MADE_NORM_NONE, MADE_NORM_AFFINE = 0, 1
 DAG_PLAN_KC = 32          # GNF_DAG_PLAN_KC
+DAG_ELEM_F32, DAG_ELEM_U8 = 0, 1      # GNF_DAG_ELEM_*
 ABI_VERSION = 11          # GNF_ABI_VERSION of include/gnf_hip.h this binding was written against
 
 
@@ -186,6 +187,10 @@ SIGNATURES = {
                                   ctypes.c_void_p, c_int, c_stream]),
     "gnf_image_prep": (c_int, [ctypes.c_void_p, c_i64, ctypes.c_void_p, c_int, ctypes.c_void_p, c_int, c_int, c_int, c_f, c_u64,
                                c_u64, c_float, c_f, c_f, c_i64, c_stream]),
+    "gnf_dag_levels_supported": (c_int, [c_i64]),
+    "gnf_dag_levels_ws_bytes": (c_i64, [c_i64, c_i64]),
+    "gnf_dag_levels": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_f, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                               c_i64, c_i64, c_i64, c_stream]),
     "gnf_probe_mfma_f32": (c_i64, [c_f, c_int, c_int, c_stream]),
     "gnf_probe_copy": (c_int, [c_f, c_f, c_i64, c_stream]),
     "gnf_probe_empty": (c_int, [c_i64, c_int, c_stream]),

@@ -1407,6 +1407,54 @@ def image_prep(data_u8, rows, flip, u, seed, offset, alpha, size_img, want_bpp):
     return x, term
 
 
+# ----------------------------------------------------------------------------- graph queries of the DAG conditioner
+def dag_levels_supported(d):
+    """the sizes gnf_dag_levels takes (1 <= d <= 4096)"""
+    return bool(abi.load().gnf_dag_levels_supported(int(d)))
+
+
+def dag_levels(M, thresholds=None):
+    """Topological levels of the graphs `j -> i where pred(M[.., i, j])` in two launches (csrc/gnf_dag_graph.hip):
+    -> (level int32, info int32).  level[.., i] = length of the longest parent chain of node i, -1 on or behind a cycle;
+    info[..] = (n_levelled, n_levels): acyclic iff n_levelled == d, and the depth is then n_levels - 1.
+    M: [d, d] or [G, d, d] on the GPU, fp32 or bool / uint8, any row stride (a view of a flat parameter buffer).
+    thresholds None: the predicate is M != 0 (a NaN is an edge).  thresholds = G floats (a sequence or an fp32 tensor; fp32 M
+    only): M > thresholds[g], compared in fp32 like torch's `tensor > python_float`; with a [d, d] matrix they all share it.
+    Shapes: [d] and [2] for a [d, d] matrix without thresholds, else [G, d] and [G, 2].  Integers: no autograd node."""
+    if not M.is_cuda:
+        raise abi.GnfError("gnf_hip kernels run on the MI355X only: got a %s tensor (no CPU fallback)" % M.device)
+    M = M.detach()
+    if M.dtype == torch.bool:
+        M = M.view(torch.uint8)
+    if M.dtype not in (torch.float32, torch.uint8):
+        raise abi.GnfError("dag_levels takes fp32 or bool / uint8: got %s" % M.dtype)
+    if M.dim() not in (2, 3) or M.shape[-1] != M.shape[-2]:
+        raise abi.GnfError("dag_levels needs [d, d] or [G, d, d]: got %s" % (tuple(M.shape),))
+    d = M.shape[-1]
+    if thresholds is not None:
+        if M.dtype != torch.float32:
+            raise abi.GnfError("dag_levels: thresholds need an fp32 matrix")
+        if not torch.is_tensor(thresholds):
+            thresholds = torch.tensor([float(t) for t in thresholds], dtype=torch.float32)     # RNE, as torch rounds a scalar
+        thresholds = thresholds.to(device=M.device, dtype=torch.float32).contiguous().view(-1)
+    squeeze = M.dim() == 2 and thresholds is None
+    G = M.shape[0] if M.dim() == 3 else (1 if thresholds is None else thresholds.numel())
+    if thresholds is not None and thresholds.numel() != G:
+        raise abi.GnfError("dag_levels: %d thresholds for %d graphs" % (thresholds.numel(), G))
+    if d > 1 and (M.stride(-1) != 1 or M.stride(-2) < d):
+        M = M.contiguous()
+    level = torch.empty((G, d), dtype=torch.int32, device=M.device)
+    info = torch.empty((G, 2), dtype=torch.int32, device=M.device)
+    nws = abi.load().gnf_dag_levels_ws_bytes(G, d)
+    abi.check(min(nws, 0), "gnf_dag_levels_ws_bytes")
+    ws = _ws(nws + 8, M)
+    off = (-ws.data_ptr()) % 8                                   # the words are 64-bit: 8-byte aligned whatever the allocator gave
+    call("gnf_dag_levels", abi.rawptr(M) if G else None, abi.DAG_ELEM_F32 if M.dtype == torch.float32 else abi.DAG_ELEM_U8,
+         (M.stride(0) if G > 1 else 0) if M.dim() == 3 else 0, M.stride(-2) if d > 1 else d, ptr(thresholds) if G else None,
+         abi.rawptr(level) if G else None, abi.rawptr(info), ctypes.c_void_p(ws.data_ptr() + off), nws, G, d, stream())
+    return (level[0], info[0]) if squeeze else (level, info)
+
+
 # ----------------------------------------------------------------------------- Adam on a flat buffer
 def adam_step(p, g, m, v, step, lr=1e-3, betas=(.9, .999), eps=1e-8, weight_decay=0., grad_scale=1.):
     call("gnf_adam_step", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, betas[0], betas[1], eps, weight_decay,

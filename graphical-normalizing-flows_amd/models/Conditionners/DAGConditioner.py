@@ -73,6 +73,28 @@ def _digraph(adj):
     return nx.from_numpy_array(adj, create_using=nx.DiGraph)
 
 
+# DAGConditioner.device_graph of a new conditioner with in_size >= DEVICE_GRAPH_MIN_D: levels / depth / acyclicity from
+# gnf_hip.ops.dag_levels instead of a copy of the d x d matrix to the host and a networkx / Python walk there (identical
+# integers).  The measurement behind the values: profiles/dag_graph_ab.txt -- the device arm wins every pair of every query
+# at d = 43, 63, 784 and 3072 (levels() 0.72 vs 0.99 ms at d = 43, 1.6 vs 39 ms to 15 vs 427 ms at d = 3072) and loses
+# pairs at d = 6, 8 and 21, where two launches and a read-back meet a Python walk of a few hundred microseconds.  A smaller
+# conditioner takes the device path when `device_graph` is set by hand.
+DEVICE_GRAPH_DEFAULT = True
+DEVICE_GRAPH_MIN_D = 43
+
+
+def threshold_candidates():
+    """The thresholds post_process() tries, as the doubles its search loop produces (.1, then `+= .05` in Python): the list
+    ends with the first one whose fp32 rounding reaches 1 -- soft-thresholded values never exceed 1.0, so that graph is empty
+    and the search cannot go past it."""
+    out, th = [], .1
+    while True:
+        out.append(th)
+        if np.float32(th) >= 1:
+            return out
+        th += .05
+
+
 class DAGConditioner(Conditioner):
     """Graphical conditioner (reference DAGConditioner.py:23-293): a learned adjacency A gates
     which inputs each dimension's embedding may see; an acyclicity constraint with dual
@@ -125,6 +147,8 @@ class DAGConditioner(Conditioner):
         self.is_invertible = False
         self.sparse_front = True        # deterministic gate + windowed, frozen A: sparse embedding front
         self.fused_front = True         # gate + MNISTCNN conv front as one autograd node (False: DagGateFn + MnistConvFn)
+        # levels / depth / acyclicity on the device (False: host networkx)
+        self.device_graph = DEVICE_GRAPH_DEFAULT and in_size >= DEVICE_GRAPH_MIN_D
         self._sparse_outside = None     # 1 outside the 5x5 pixel windows (device mask, built on first use)
         self._sparse_checked = (None, False)
         self._off_key, self._off = None, False
@@ -360,10 +384,21 @@ class DAGConditioner(Conditioner):
         return self.dag_const * (self.lambd * lag_const + self.c / 2 * lag_const ** 2) \
             + self.l1_weight * self.A.abs().mean()
 
+    def _device_graph(self):
+        """True when the graph queries run on the device (gnf_hip.ops.dag_levels): switched on, A on the GPU, d in the
+        kernel's domain.  Otherwise every call site runs the host statements of the reference."""
+        return bool(getattr(self, "device_graph", False)) and self.A.is_cuda and ops.dag_levels_supported(self.in_size)
+
     def post_process(self, zero_threshold=None):
         def adj(th):
             return (self.soft_thresholded_A().data.clone().abs() > th).float().detach().cpu().numpy()
-        if zero_threshold is None:
+        if zero_threshold is None and self._device_graph():
+            # every candidate of the search below in ONE call over one matrix, one read-back of 2 ints per candidate
+            cands = threshold_candidates()
+            _, info = ops.dag_levels(self.soft_thresholded_A().data.abs(), cands)
+            acyclic = (info[:, 0] == self.in_size).tolist()
+            zero_threshold = cands[acyclic.index(True)]          # the last candidate's graph is empty
+        elif zero_threshold is None:
             zero_threshold = .1
             while not nx.is_directed_acyclic_graph(_digraph(adj(zero_threshold))):
                 zero_threshold += .05
@@ -433,16 +468,30 @@ class DAGConditioner(Conditioner):
                     self._set("dag_const", 0.)
                     self._set("l1_weight", 0.)
             else:
-                G = _digraph(self.A.detach().cpu().numpy() ** 2)
-                try:
-                    nx.find_cycle(G)
+                if self._device_graph():
+                    A = self.A.detach()
+                    cyclic = int(ops.dag_levels(A * A)[1][0]) < self.in_size
+                else:
+                    G = _digraph(self.A.detach().cpu().numpy() ** 2)
+                    try:
+                        nx.find_cycle(G)
+                        cyclic = True
+                    except nx.NetworkXNoCycle:
+                        cyclic = False
+                if cyclic:
                     self._reopen()
                     self._set("dag_const", 1.)
-                except nx.NetworkXNoCycle:
+                else:
                     self.is_invertible = True
         return lag_const
 
     def depth(self):
+        if self._device_graph():
+            n_levelled, n_levels = ops.dag_levels(self.A.detach() > 0)[1].tolist()
+            if n_levelled == self.in_size:
+                return n_levels - 1
+            if not self.is_invertible:
+                return 0                                         # (is_invertible on a cyclic graph: the statements below raise)
         G = _digraph((self.A.detach() > 0).float().cpu().numpy())
         if self.is_invertible or nx.is_directed_acyclic_graph(G):
             return int(nx.dag_longest_path_length(G))
@@ -451,7 +500,26 @@ class DAGConditioner(Conditioner):
     def levels(self, P=None, with_host=False):
         """Topological generations of the dependency graph (edge j -> i where the importance P[i, j] != 0; default: the
         graph depth() measures, A[i, j] > 0): level k holds the variables whose longest parent chain has length k.
-        None if the graph has a cycle."""
+        None if the graph has a cycle.  Each level is a LongTensor on A's device, ascending inside the level (with_host: a
+        pair of it and the same indices as a tuple of ints)."""
+        if self._device_graph():
+            # two launches, a stable sort and ONE copy of d + (d + 1) + 2 integers; the levels are slices of the sorted order
+            d = self.in_size
+            level, info = ops.dag_levels((self.A.detach() > 0) if P is None else P.detach() if P.dtype == torch.float32
+                                         else (P.detach() != 0))
+            lv = level.long()
+            order = torch.sort(lv, stable=True).indices          # stable: ascending node index inside a level
+            counts = torch.zeros(d + 1, dtype=torch.long, device=lv.device).scatter_add_(0, lv + 1, torch.ones_like(lv))
+            host = torch.cat((info.long(), counts, order)).tolist()
+            if host[0] < d:
+                return None
+            out, start = [], 0
+            for k in range(host[1]):
+                n = host[3 + k]                                  # counts[0] (the -1 entries) is 0 here
+                rows = order[start:start + n]
+                out.append((rows, tuple(host[d + 3 + start:d + 3 + start + n])) if with_host else rows)
+                start += n
+            return out
         adj = ((self.A.detach() > 0) if P is None else (P.detach() != 0)).cpu().numpy()
         d = adj.shape[0]
         indeg = adj.sum(1).astype(np.int64)                 # number of parents of i

@@ -96,8 +96,10 @@ class NormalizingFlowStep(NormalizingFlow):
     # -- inversion ----------------------------------------------------------------------------------------------
     def _levels(self, importance):
         """the level schedule of the current gate, recomputed only when A (storage or version counter) or the gate's
-        thresholds changed: DAGConditioner.levels() copies the 784 x 784 adjacency to the host and walks it in Python
-        (a few ms per call, a host synchronisation in front of every sampling pass otherwise)"""
+        thresholds changed: DAGConditioner.levels() is a host synchronisation in front of every sampling pass otherwise.
+        With `device_graph` it is two launches (gnf_hip.ops.dag_levels), a sort and one copy of 2 d + 3 integers; without
+        it the d x d adjacency goes to the host and is walked in Python (5 ms against 0.9 at 784 x 784, 39 .. 427 ms
+        against 1.6 .. 15 at d = 3072: profiles/dag_graph_ab.txt)"""
         cond = self.conditioner
         # A trainable A is rewritten by the optimiser through a raw pointer (gnf_hip.dp: fused Adam on the flat buffer, a
         # replayed hipGraph), which moves neither its version counter nor its address: nothing is cached for it.  A frozen

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-/* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_*, gnf_image_prep and gnf_dagmlp_* were ADDED under this number (no existing symbol
+/* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_*, gnf_image_prep, gnf_dagmlp_* and gnf_dag_levels* were ADDED under this number (no existing symbol
  * changed; a binding written against the earlier 11 keeps working, and tests/test_cifar_factory.py pins the value) */
 #define GNF_ABI_VERSION 11
 #define GNF_EINVAL (-1)   /* bad argument (null pointer, negative size, ...)          */
@@ -702,6 +702,37 @@ int gnf_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n,
 int gnf_image_prep(const unsigned char* data, int64_t n_rows, const int32_t* rows, int flip_mode,
                    const unsigned char* flip, int C, int H, int W, const float* u, uint64_t seed, uint64_t offset,
                    float alpha, float* x, float* bpp_term, int64_t B, gnf_stream_t stream);
+
+/* ---- graph queries of the DAG conditioner (DAGConditioner.py:76-85, 240-254, 262-266) ---------------------------------
+ * Topological levels, depth and acyclicity of G directed graphs on d nodes each; what the reference asks networkx on the
+ * host (is_directed_acyclic_graph, find_cycle, dag_longest_path_length) after copying a d x d matrix there.
+ * M: element (g, i, j) at M + g*stride_g + i*ld + j (strides in elements), ld >= d; stride_g == 0: ONE matrix shared by
+ *   all graphs (G thresholds over it).  Node j is a parent of node i in graph g when pred_g(M[g, i, j]) holds:
+ *     elem_type GNF_DAG_ELEM_F32, thresholds == NULL:  m != 0            (a NaN is an edge, as `P != 0` in torch)
+ *     elem_type GNF_DAG_ELEM_F32, thresholds [G] fp32: m > thresholds[g]  compared in fp32 (a NaN is no edge)
+ *     elem_type GNF_DAG_ELEM_U8 (torch's bool storage): m != 0;  thresholds must be NULL.
+ *   A diagonal entry that satisfies the predicate is a self loop, i.e. a cycle.
+ * level [G, d] int32: the length of the longest parent chain of node i (roots: 0); -1 for every node on or behind a cycle.
+ * info [G, 2] int32: (n_levelled, n_levels).  Graph g is acyclic iff n_levelled == d; its depth (the number of edges of its
+ *   longest path) is then n_levels - 1.  Every entry of level and info is written.
+ * ws: >= gnf_dag_levels_ws_bytes(G, d) bytes (G * (ceil(d/64) + 1) * d * 8: the predicate as bits, and per row the mask of its
+ *   nonzero words), else GNF_EWS; 8-BYTE aligned (it is written as 64-bit words), else GNF_EINVAL.
+ * Alignment: dword for an fp32 M, thresholds, level and info; any byte address for a uint8 M.
+ * Domain: 1 <= d <= 4096 (gnf_dag_levels_supported; outside it GNF_ESHAPE from gnf_dag_levels and gnf_dag_levels_ws_bytes,
+ *   nothing is touched), G >= 0 and G * ceil(d/4) < 2^31.  G == 0: returns 0 without a launch.
+ * GNF_EINVAL: G < 0, an unknown elem_type, and for G > 0 a NULL M / level / info / ws, ld < d, stride_g < 0, thresholds with a
+ *   uint8 M, an operand below its alignment.  Checked before any launch.
+ * Two launches: a pack kernel (one wavefront per row, 64 columns -> one word by __ballot) and a peel kernel with exactly one
+ * workgroup per graph, a counted loop of at most d + 1 rounds and integer LDS atomics only: the same call returns the same
+ * integers, and they are those of a Kahn walk on the host.
+ * (Added under ABI version 11: no existing symbol changed.) */
+#define GNF_DAG_ELEM_F32 0
+#define GNF_DAG_ELEM_U8  1
+int gnf_dag_levels_supported(int64_t d);
+int64_t gnf_dag_levels_ws_bytes(int64_t G, int64_t d);
+int gnf_dag_levels(const void* M, int elem_type, int64_t stride_g, int64_t ld, const float* thresholds,
+                   int32_t* level, int32_t* info, void* ws, int64_t ws_bytes, int64_t G, int64_t d,
+                   gnf_stream_t stream);
 
 /* ---- device-ceiling probes (measurement aids for bench.py) ---------------
  * gnf_probe_mfma_f32 launches `blocks` workgroups of 8 wavefronts that do nothing but
