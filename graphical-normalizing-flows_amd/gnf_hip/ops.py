@@ -1407,6 +1407,93 @@ def image_prep(data_u8, rows, flip, u, seed, offset, alpha, size_img, want_bpp):
     return x, term
 
 
+# ----------------------------------------------------------------------------- toy-problem batches
+# the 2-D base problems of the reference's lib/toy_data.py, in the numbering of gnf_toy_sample (include/gnf_hip.h)
+TOY_KINDS = ("2igaussians", "2gaussians", "4gaussians", "8gaussians", "swissroll", "circles", "moons", "pinwheel", "2spirals",
+             "checkerboard", "line", "line-noisy", "cos", "joint_gaussian")
+TOY_MAX_BLOCKS = 8
+# lib/toy_data.py:42-43 (8-MIX; 7-MIX, :55-56, is its first fourteen entries)
+_TOY_MIX_STD = (1.604934, 1.584863, 2.0310535, 2.0305095, 1.337718, 1.4043778, 1.6944685, 1.6935346,
+                1.7434783, 1.0092416, 1.4860426, 1.485661, 2.3067558, 2.311637, 1.4430547, 1.4430547)
+# the composites as block lists (:16-59).  8-MIX in the order the reference concatenates (data1 .. data8, where `line` was
+# assigned to data5 and `moons` to data8); the `std` vector is then applied to those columns as it stands
+_TOY_COMPOSITES = {
+    "2spirals-8gaussians": (("2spirals", "8gaussians"), None),
+    "4-2spirals-8gaussians": (("2spirals", "8gaussians") * 2, None),
+    "8-2spirals-8gaussians": (("2spirals", "8gaussians") * 4, None),
+    "7-MIX": (("2spirals", "8gaussians", "swissroll", "circles", "moons", "pinwheel", "checkerboard"), _TOY_MIX_STD[:14]),
+    "8-MIX": (("2spirals", "8gaussians", "swissroll", "circles", "line", "pinwheel", "checkerboard", "moons"), _TOY_MIX_STD),
+}
+TOY_DATASETS = TOY_KINDS + tuple(_TOY_COMPOSITES)      # the nineteen names of the toy driver's `datasets` list
+
+
+def toy_blocks(name):
+    """(block list as a tuple of TOY_KINDS indices, col_scale as a float32 numpy vector [2P] or None) of a data set of the toy
+    driver: a base problem is one block; the MIX sets carry the reciprocals of the reference's `std` vector."""
+    if name in _TOY_COMPOSITES:
+        names, std = _TOY_COMPOSITES[name]
+        scale = None if std is None else (np.float32(1.) / np.asarray(std, dtype=np.float32))
+        return tuple(TOY_KINDS.index(n) for n in names), scale
+    if name in TOY_KINDS:
+        return (TOY_KINDS.index(name),), None
+    raise abi.GnfError("unknown toy data set %r (one of %s)" % (name, ", ".join(TOY_DATASETS)))
+
+
+def toy_sample(names_or_kinds, B, seed, offset, device, u=None, out=None, col_scale=None):
+    """One launch of gnf_toy_sample (csrc/gnf_toy_data.hip): x [B, 2P] fp32 on `device`, block p a draw of a 2-D base problem.
+    names_or_kinds: a data set name (base or composite: toy_blocks supplies blocks and column scale), or a sequence of base
+    names / TOY_KINDS indices, at most eight, with an optional col_scale [2P].  (seed, offset): Philox key and call counter;
+    row b of block p depends on (seed, offset, b, p, kind) only.  u: explicit uniforms [B, P, 8] (parity tests) or None.
+    out: a [B, 2P] fp32 view to fill (unit column stride; its row stride is the kernel's ldx) -- returned.  No autograd node."""
+    if isinstance(names_or_kinds, str):
+        kinds, scale = toy_blocks(names_or_kinds)
+        if col_scale is not None:
+            raise abi.GnfError("toy_sample: a data set name brings its own column scale")
+    else:
+        kinds, scale = [], col_scale
+        for k in names_or_kinds:
+            if isinstance(k, str):
+                if k not in TOY_KINDS:
+                    raise abi.GnfError("toy_sample: %r is not a base problem (%s)" % (k, ", ".join(TOY_KINDS)))
+                k = TOY_KINDS.index(k)
+            if not isinstance(k, (int, np.integer)) or not 0 <= int(k) < len(TOY_KINDS):
+                raise abi.GnfError("toy_sample: block kind %r is outside 0..%d" % (k, len(TOY_KINDS) - 1))
+            kinds.append(int(k))
+    P = len(kinds)
+    if not 1 <= P <= TOY_MAX_BLOCKS:
+        raise abi.GnfError("toy_sample takes 1..%d blocks: got %d" % (TOY_MAX_BLOCKS, P))
+    B = int(B)
+    if not 0 <= B <= 1 << 32:
+        raise abi.GnfError("toy_sample: B = %d is outside 0..2^32" % B)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise abi.GnfError("gnf_hip kernels run on the MI355X only: got device %s (no CPU fallback)" % device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if scale is not None:
+        scale = np.ascontiguousarray(np.asarray(scale, dtype=np.float32))
+        if scale.shape != (2 * P,):
+            raise abi.GnfError("toy_sample: col_scale must have %d entries" % (2 * P))
+    if u is not None:
+        if u.device != device or u.dtype != torch.float32 or tuple(u.shape) != (B, P, 8):
+            raise abi.GnfError("toy_sample: explicit uniforms must be fp32 [%d, %d, 8] on %s: got %s %s on %s"
+                               % (B, P, device, u.dtype, tuple(u.shape), u.device))
+        u = u.contiguous()
+    if out is None:
+        out = torch.empty((B, 2 * P), dtype=torch.float32, device=device)
+    elif (out.device != device or out.dtype != torch.float32 or tuple(out.shape) != (B, 2 * P)
+          or (B > 0 and out.stride(1) != 1) or (B > 1 and out.stride(0) < 2 * P)):
+        raise abi.GnfError("toy_sample: out must be fp32 [%d, %d] on %s with unit column stride: got %s %s strides %s on %s"
+                           % (B, 2 * P, device, out.dtype, tuple(out.shape), tuple(out.stride()), out.device))
+    ldx = out.stride(0) if B > 1 else 2 * P
+    karr = (ctypes.c_int32 * P)(*kinds)
+    with torch.cuda.device(device):
+        call("gnf_toy_sample", ctypes.cast(karr, ctypes.c_void_p), P,
+             None if scale is None else ctypes.c_void_p(scale.ctypes.data), ptr(u) if B else None, int(seed), int(offset),
+             ptr(out) if B else None, ldx, B, stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- graph queries of the DAG conditioner
 def dag_levels_supported(d):
     """the sizes gnf_dag_levels takes (1 <= d <= 4096)"""

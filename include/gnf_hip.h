@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-/* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_*, gnf_image_prep, gnf_dagmlp_* and gnf_dag_levels* were ADDED under this number (no existing symbol
+/* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_*, gnf_image_prep, gnf_dagmlp_*, gnf_dag_levels* and gnf_toy_sample were ADDED under this number (no existing symbol
  * changed; a binding written against the earlier 11 keeps working, and tests/test_cifar_factory.py pins the value) */
 #define GNF_ABI_VERSION 11
 #define GNF_EINVAL (-1)   /* bad argument (null pointer, negative size, ...)          */
@@ -702,6 +702,32 @@ int gnf_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n,
 int gnf_image_prep(const unsigned char* data, int64_t n_rows, const int32_t* rows, int flip_mode,
                    const unsigned char* flip, int C, int H, int W, const float* u, uint64_t seed, uint64_t offset,
                    float alpha, float* x, float* bpp_term, int64_t B, gnf_stream_t stream);
+
+/* ---- training batches of the toy driver (train_toy.py; reference lib/toy_data.py:11-226) -----------------------------
+ * x[b, 2p], x[b, 2p + 1] for b < B, p < P: one draw of the 2-D base problem kinds[p], times col_scale[2p], col_scale[2p + 1].
+ * kinds: HOST array of P problem numbers, 1 <= P <= 8 (read during the call, packed into a kernel argument):
+ *    0 2igaussians   1 2gaussians   2 4gaussians   3 8gaussians   4 swissroll   5 circles   6 moons   7 pinwheel
+ *    8 2spirals      9 checkerboard 10 line        11 line-noisy  12 cos        13 joint_gaussian
+ *   The reference's composites are block lists: 2spirals-8gaussians = {8, 3}, 8-MIX = {8, 3, 4, 5, 10, 7, 9, 6} with the
+ *   reciprocals of its `std` vector as col_scale (gnf_hip.ops.toy_blocks).
+ * col_scale: HOST array of 2P factors or NULL (no scaling); passed by value as well.
+ * u: device [B, P, 8] explicit uniforms in (0, 1) (the parity hook, as u of gnf_image_prep), or NULL for Philox.
+ * Philox layout (seed = key, offset = the caller's call counter; philox4x32_10 and u01_open of csrc/gnf_common.h):
+ *   u_{4q + w} of (b, p) = u01_open(r[w]),  r = philox4x32_10(counter words (lo32(b), (p << 8) | q, lo32(offset), hi32(offset)),
+ *   key words (lo32(seed), hi32(seed))),  q = 0, 1.  Which uniform feeds which variate of a problem, and the arithmetic of each
+ *   problem: the table at the head of csrc/gnf_toy_data.hip; train_toy.toy_reference is the same arithmetic in torch.
+ *   A value depends on (seed, offset, b, p, kinds[p], col_scale[2p..2p+1]) only: not on B, P, ldx or the other blocks.
+ *   tests/test_gpu_toy_data.py pins the layout.
+ * x: device, element (b, c) at x + b*ldx + c, ldx >= 2P; columns >= 2P of a row are not touched.  Dword alignment suffices:
+ *   a pair is stored as one float2 when x is 8-byte aligned and ldx is even, as two floats otherwise -- the same bits.
+ * Per-batch counts the reference fixes (the two arms of 2spirals, the rings / moons, the five pinwheel classes) are fair
+ *   draws per sample here, and pinwheel returns all B rows (the reference 5 (B // 5)): DESIGN.md section 1.
+ * GNF_EINVAL: P outside 1..8, kinds NULL or an entry outside 0..13, B < 0, B > 2^32 (the sample index is one counter word),
+ *   ldx < 2P, and for B > 0 a NULL x or an x / u below dword alignment.  Checked before any launch.
+ * B == 0: returns 0 without a launch; x and u may be NULL.  One launch, one thread per (sample, block), no LDS, no workspace.
+ * (Added under ABI version 11: no existing symbol changed.) */
+int gnf_toy_sample(const int32_t* kinds, int P, const float* col_scale, const float* u, uint64_t seed, uint64_t offset,
+                   float* x, int64_t ldx, int64_t B, gnf_stream_t stream);
 
 /* ---- graph queries of the DAG conditioner (DAGConditioner.py:76-85, 240-254, 262-266) ---------------------------------
  * Topological levels, depth and acyclicity of G directed graphs on d nodes each; what the reference asks networkx on the
