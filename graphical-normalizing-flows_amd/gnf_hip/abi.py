@@ -188,6 +188,9 @@ SIGNATURES = {
     "gnf_image_prep": (c_int, [ctypes.c_void_p, c_i64, ctypes.c_void_p, c_int, ctypes.c_void_p, c_int, c_int, c_int, c_f, c_u64,
                                c_u64, c_float, c_f, c_f, c_i64, c_stream]),
     "gnf_toy_sample": (c_int, [ctypes.c_void_p, c_int, ctypes.c_void_p, c_f, c_u64, c_u64, c_f, c_i64, c_i64, c_stream]),
+    "gnf_shuffle_keys": (c_int, [c_u64, c_u64, c_i64, ctypes.c_void_p, c_stream]),
+    "gnf_tab_batch": (c_int, [c_f, c_i64, c_i64, c_i64, ctypes.c_void_p, c_i64, c_i64, c_i64, ctypes.c_void_p, c_f, c_i64,
+                              c_stream]),
     "gnf_dag_levels_supported": (c_int, [c_i64]),
     "gnf_dag_levels_ws_bytes": (c_i64, [c_i64, c_i64]),
     "gnf_dag_levels": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_f, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

@@ -291,7 +291,10 @@ class GraphedStep:
     from the captured one the step is re-captured (the dual variables themselves are device buffers updated in place,
     so a replay reads their current values).
 
-    Construction runs `warmup` real steps on x_example (they count as training steps), then captures."""
+    Construction runs `warmup` real steps on x_example (they count as training steps), then captures.
+
+    `steps(batches, K)` replays K consecutive steps from ONE graph: the batches then come from device memory as well
+    (DeviceBatches.gather_into reads a device cursor), see there."""
 
     MAX_GRAPHS = 16                      # captured variants kept (node-count jitter 20..29 of the drivers = 10)
 
@@ -306,11 +309,12 @@ class GraphedStep:
         self._state_keep = None if owned_by_state else state
         self.flow = flow
         self.lr, self.weight_decay = lr, weight_decay
-        self._step_buf = torch.zeros(2, dtype=torch.int32, device=x_example.device)    # {steps taken, ticket counter}
+        self._step_buf = torch.zeros(2, dtype=torch.int32, device=state.flat.device)   # {steps taken, ticket counter}
         self.step_dev = self._step_buf[:1]
         self.captures = 0
         self._graphs = {}                    # fingerprint -> (graph, loss tensor, input buffer)
-        self.loss = self._capture(x_example, max(warmup, 1))
+        # x_example = None: nothing is run or captured yet (a caller that only replays groups of steps, `steps`)
+        self.loss = self._capture(x_example, max(warmup, 1)) if x_example is not None else None
 
     @property
     def state(self):
@@ -340,15 +344,14 @@ class GraphedStep:
         fp.append(tuple(p.requires_grad for p in self.state.params))
         return tuple(fp)
 
-    def _capture(self, x, warmup):
-        """`warmup` eager steps on x (real, counted training steps; the loss of the last one is returned), then the
-        capture of one more step for this fingerprint"""
+    def _body(self, xbuf):
+        """-> the function that runs ONE optimisation step on the contents of xbuf (eagerly, or under a capture) and returns
+        its detached loss; the device-side step counter advances with it, state.t is the caller's"""
         from . import ops
         flow, state = self.flow, self.state
         if not self.graphable(flow):
             raise RuntimeError("a stochastic DAG gate draws its noise from a host-side counter: not graphable")
         lr, weight_decay = self.lr, self.weight_decay
-        xbuf = x.clone()
 
         # The captured step differentiates w.r.t. FRESH leaves aliasing the parameters (torch.func.functional_call), not
         # the nn.Parameters themselves: a Parameter's gradient accumulator remembers the stream it was created on and is
@@ -367,6 +370,7 @@ class GraphedStep:
         name_of = {id(p): n for n, p in wrapper.named_parameters()}
         names = [name_of[id(p)] for p in state.params]
         live = [i for i, p in enumerate(state.params) if p.requires_grad]     # a frozen A stays out of the backward
+        one = _one(xbuf)
 
         def body():
             leaves = [p.detach().requires_grad_(i in live) for i, p in enumerate(state.params)]
@@ -382,14 +386,20 @@ class GraphedStep:
                                   self._step_buf, lr=lr, weight_decay=weight_decay, advance=(k == len(runs) - 1))
             return loss.detach()
 
-        one = _one(xbuf)
+        return body
+
+    def _run_then_capture(self, fn, eager_runs, steps_per_run, key, keep):
+        """`eager_runs` eager calls of fn on a side stream (real, counted training steps: state.t advances by
+        steps_per_run each; the clone of the last result is returned), then the capture of one more call, filed under
+        `key` as (graph, fn's result, *keep)"""
+        state = self.state
         self.step_dev.fill_(state.t)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            for _ in range(warmup):
-                last = body().clone()
-                state.t += 1
+            for _ in range(eager_runs):
+                last = fn().clone()
+                state.t += steps_per_run
         torch.cuda.current_stream().wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         gc_was_on = gc.isenabled()
@@ -397,16 +407,29 @@ class GraphedStep:
         gc.disable()                            # no finaliser (of some older graph, event, ...) may run inside the capture
         try:
             with torch.cuda.graph(graph):
-                loss = body()
+                out = fn()
         finally:
             if gc_was_on:
                 gc.enable()
         if len(self._graphs) >= self.MAX_GRAPHS:
             self._graphs.pop(next(iter(self._graphs)))
-        self._graphs[self._fingerprint(x.shape)] = (graph, loss, xbuf)
+        self._graphs[key] = (graph, out) + tuple(keep)
         self.captures += 1
         self._dev_t = state.t                   # host mirror of step_dev (a capture itself executes nothing)
         return last
+
+    def _capture(self, x, warmup):
+        """`warmup` eager steps on x (real, counted training steps; the loss of the last one is returned), then the
+        capture of one more step for this fingerprint"""
+        xbuf = x.clone()
+        return self._run_then_capture(self._body(xbuf), warmup, 1, self._fingerprint(x.shape), (xbuf,))
+
+    def _sync_step_dev(self):
+        if getattr(self, "_dev_t", None) != self.state.t:
+            # eager steps in between (graph=False, a batch above GRAPH_MAX_ELEMS, a variant that was briefly not
+            # graphable) advanced state.t but not the device-side counter the replayed Adam launches read: re-sync it
+            # with a plain launch outside the graph, or the bias corrections lr/(1-b1^t), sqrt(1-b2^t) go stale
+            self.step_dev.fill_(self.state.t)
 
     def __call__(self, x):
         entry = self._graphs.get(self._fingerprint(x.shape))
@@ -417,13 +440,156 @@ class GraphedStep:
             return self.loss
         graph, loss, xbuf = entry
         xbuf.copy_(x, non_blocking=True)
-        if getattr(self, "_dev_t", None) != self.state.t:
-            # eager steps in between (graph=False, a batch above GRAPH_MAX_ELEMS, a variant that was briefly not
-            # graphable) advanced state.t but not the device-side counter the replayed Adam launches read: re-sync it
-            # with a plain launch outside the graph, or the bias corrections lr/(1-b1^t), sqrt(1-b2^t) go stale
-            self.step_dev.fill_(self.state.t)
+        self._sync_step_dev()
         graph.replay()
         self.state.t += 1
         self._dev_t = self.state.t
         self.loss = loss
         return loss
+
+    def steps(self, batches, K):
+        """K consecutive optimisation steps on the next K full batches of `batches` (a DeviceBatches) as ONE hipGraph
+        replay -> the device scalar sum of the K losses (reused by the next replay of this variant).  Each captured step
+        is batches.gather_into(the input buffer), the body of a single step, loss_sum += loss: a linear chain on one
+        stream in which nothing step-dependent is passed by value -- the batch position is the device cursor of
+        `batches`, Adam's step count the device counter.  One replay advances the cursor by K batches, the counter and
+        state.t by K.  The fingerprint is that of a single step plus K and the batch source (the object, and the
+        storage of its permutation, which start_epoch() rewrites in place).  A variant seen for the first time runs its
+        K steps eagerly (the same launches, uncaptured) and is captured behind them."""
+        K = int(K)
+        if K < 1 or batches.full_left() < K:
+            raise RuntimeError("steps(K = %d): %d full batches left in this epoch" % (K, batches.full_left()))
+        shape = (batches.rows_per_batch, batches.d)
+        key = self._fingerprint(shape) + (("steps", K, id(batches), batches.perm.data_ptr(), batches.cursor.data_ptr()),)
+        batches.sync_cursor()
+        entry = self._graphs.get(key)
+        if entry is None:
+            xbuf = torch.empty(shape, dtype=torch.float32, device=batches.X.device)
+            loss_sum = torch.zeros((), dtype=torch.float32, device=xbuf.device)
+            body = self._body(xbuf)
+
+            def group():
+                loss_sum.zero_()
+                for _ in range(K):
+                    batches.gather_into(xbuf)
+                    loss_sum.add_(body())
+                return loss_sum
+
+            # `batches` is kept by the entry: its id stays taken while the graph that reads its buffers lives
+            out = self._run_then_capture(group, 1, K, key, (xbuf, batches))
+        else:
+            self._sync_step_dev()
+            entry[0].replay()
+            self.state.t += K
+            self._dev_t = self.state.t
+            out = entry[1]
+        batches.advanced(K)
+        return out
+
+
+def steps_replayable(flow, batches=None):
+    """True when groups of steps may be replayed from one hipGraph (GraphedStep.steps): one process, a flow that
+    GraphedStep.graphable() admits, no Monotonic normalizer (the drivers jitter its node count `nb_steps` per batch, and a
+    group bakes ONE count in), and a batch small enough for train_step's own replay rule"""
+    if (dist.is_initialized() and dist.get_world_size() > 1) or collective_on() or not torch.is_grad_enabled():
+        return False
+    if not GraphedStep.graphable(flow) or any(hasattr(nrm, "nb_steps") for nrm in flow.getNormalizers()):
+        return False
+    return batches is None or (batches.world == 1 and batches.rows_per_batch * batches.d <= GRAPH_MAX_ELEMS)
+
+
+def train_steps(flow, state, batches, K, lr=1e-3, weight_decay=1e-5):
+    """K optimisation steps on the next K full batches of `batches` in one replay (GraphedStep.steps) -> the device sum of
+    their K losses.  The GraphedStep is the one train_step keeps in `state._graphed`: single steps and groups share its
+    device-side step counter.  The caller asks steps_replayable() first."""
+    if not steps_replayable(flow, batches):
+        raise RuntimeError("this flow / process group does not replay groups of steps: run single steps (train_step)")
+    gs = getattr(state, "_graphed", None)
+    if gs is None or gs.flow is not flow or (gs.lr, gs.weight_decay) != (lr, weight_decay):
+        state._graphed = gs = GraphedStep(flow, state, None, lr=lr, weight_decay=weight_decay, owned_by_state=True)
+    return gs.steps(batches, K)
+
+
+def batch_slices(n, b, rank, world):
+    """[(first, count)] of one epoch of n rows in global batches of b: for ANY permutation p of the rows,
+    p[first::world][:count] is this rank's share of a batch exactly as train_uci.shard_batches cuts it -- each global batch
+    trimmed to a multiple of `world` rows and dealt round-robin, batches that leave no row per rank skipped -- so every rank
+    gets the same number of steps of the same size."""
+    out = []
+    for i in range(0, n, b):
+        keep = min(b, n - i) // world * world
+        if keep:
+            out.append((i + rank, keep // world))
+    return out
+
+
+class DeviceBatches:
+    """The minibatches of one rank, gathered on the device: the epoch's permutation is the sort of gnf_shuffle_keys'
+    Philox keys (a pure function of (seed, epoch, n): identical on every rank without a broadcast and after a resume, no
+    generator state), a batch is ONE gnf_tab_batch launch.  X: fp32 [n, d] on the GPU; b: the GLOBAL batch size.
+
+    start_epoch(e) rewrites the SAME `perm` storage and zeroes the int32 device `cursor`, so a captured gather
+    (gather_into) keeps reading the current epoch.  next() passes the batch's first position by value; gather_into(out)
+    reads it from the cursor and advances the cursor by b with a separate in-place add behind the gather."""
+
+    def __init__(self, X, b, rank=0, world=1, seed=0):
+        if X.dim() != 2 or X.dtype != torch.float32 or not X.is_cuda:
+            raise ValueError("DeviceBatches needs an fp32 HIP tensor [n, d]")
+        self.X, self.b, self.rank, self.world, self.seed = X, int(b), int(rank), int(world), int(seed)
+        self.n, self.d = X.shape
+        self.rows_per_batch = self.b // self.world
+        self.keys = torch.empty(self.n, dtype=torch.int64, device=X.device)
+        self.perm = torch.zeros(max(self.n, 1), dtype=torch.int32, device=X.device)[:self.n]
+        self.cursor = torch.zeros(1, dtype=torch.int32, device=X.device)
+        self.slices = batch_slices(self.n, self.b, self.rank, self.world)
+        self.n_full = sum(1 for _, c in self.slices if c * self.world == self.b)     # they come first
+        self.i = len(self.slices)               # exhausted until start_epoch()
+        self.epoch = None
+        self._cursor_host = 0                   # host mirror of the cursor
+
+    def __len__(self):
+        return len(self.slices)
+
+    def start_epoch(self, e):
+        from . import ops
+        ops.shuffle_keys(self.seed, e, self.n, out=self.keys)
+        order = torch.sort(self.keys).values    # outside any graph: the sort allocates
+        order.bitwise_and_(0xffffffff)
+        self.perm.copy_(order)                  # int64 -> int32 into the storage captured gathers read
+        self.cursor.zero_()
+        self._cursor_host, self.i, self.epoch = 0, 0, int(e)
+
+    def left(self):
+        return len(self.slices) - self.i
+
+    def full_left(self):
+        return max(self.n_full - self.i, 0)
+
+    def next(self):
+        """the next batch [count, d] of this rank (a new tensor), its position passed by value"""
+        from . import ops
+        first, count = self.slices[self.i]
+        self.i += 1
+        return ops.tab_batch(self.X, self.perm, first, self.world, count)
+
+    def sync_cursor(self):
+        """device cursor <- the position of the next batch, when next() moved on without it"""
+        pos = self.i * self.b
+        if self._cursor_host != pos:
+            self.cursor.fill_(pos)
+            self._cursor_host = pos
+
+    def gather_into(self, out):
+        """The capturable form: out [b // world, d] <- the FULL batch at the device cursor, then cursor += b as a separate
+        stream-ordered add.  No allocation, no host state: replayed, it walks through the epoch.  Applies only while
+        every batch it will reach is full (full_left()); the caller accounts for replays with advanced()."""
+        from . import ops
+        ops.tab_batch(self.X, self.perm, self.rank, self.world, self.rows_per_batch, cursor=self.cursor, out=out)
+        self.cursor.add_(self.b)
+        return out
+
+    def advanced(self, k):
+        """k batches were taken through gather_into (executed eagerly or replayed)"""
+        self.i += k
+        self._cursor_host += k * self.b
+

@@ -1494,6 +1494,55 @@ def toy_sample(names_or_kinds, B, seed, offset, device, u=None, out=None, col_sc
     return out
 
 
+# ----------------------------------------------------------------------------- tabular batches from device memory
+def shuffle_keys(seed, offset, n, device=None, out=None):
+    """One launch of gnf_shuffle_keys (csrc/gnf_tab_batch.hip): int64 keys [n], keys[i] = (31 Philox bits << 32) | i, whose
+    ascending sort is the permutation of epoch `offset` under key `seed` (the layout: include/gnf_hip.h).
+    out: a contiguous int64 HIP tensor [n] to fill (returned), or None for a new one on `device`.  No autograd node."""
+    n = int(n)
+    if not 0 <= n < 1 << 31:
+        raise abi.GnfError("shuffle_keys: n = %d is outside 0..2^31-1" % n)
+    if out is None:
+        device = torch.device("cuda" if device is None else device)
+        if device.type != "cuda":
+            raise abi.GnfError("gnf_hip kernels run on the MI355X only: got device %s (no CPU fallback)" % device)
+        out = torch.empty((n,), dtype=torch.int64, device=device)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (n,) or not out.is_contiguous():
+        raise abi.GnfError("shuffle_keys: out must be a contiguous int64 tensor [%d]: got %s %s" % (n, out.dtype, tuple(out.shape)))
+    with torch.cuda.device(out.device):
+        call("gnf_shuffle_keys", int(seed) & (1 << 64) - 1, int(offset) & (1 << 64) - 1, n, abi.rawptr(out) if n else None,
+             stream())
+    return out
+
+
+def tab_batch(X, perm, first, stride, B, cursor=None, out=None):
+    """One launch of gnf_tab_batch (csrc/gnf_tab_batch.hip): x [B, d], row r = X[perm[pos + r*stride]], pos = first
+    (+ cursor[0] when `cursor`, a device int32 tensor, is given: the capturable form, nothing step-dependent by value).
+    X: fp32 [n, d] on the GPU with unit column stride (any row stride: a column slice of a wider table is not copied).
+    perm: int32 device tensor of row indices, or None for the identity.  Position and row index are clamped on the device;
+    without a cursor a batch that runs past the permutation is refused.  out: a contiguous [B, d] fp32 tensor to fill
+    (returned), or None for a new one.  The inputs are data: no autograd node."""
+    if X.dim() != 2 or X.dtype != torch.float32 or not X.is_cuda:
+        raise abi.GnfError("tab_batch needs an fp32 HIP tensor [n, d]: got %s %s on %s" % (X.dtype, tuple(X.shape), X.device))
+    n, d = X.shape
+    if d < 1 or (n > 0 and X.stride(1) != 1) or (n > 1 and X.stride(0) < d):
+        X = X.contiguous()
+    ldx = X.stride(0) if n > 1 else d
+    B = int(B)
+    for name, t in (("perm", perm), ("cursor", cursor)):
+        if t is not None and (t.dtype != torch.int32 or t.device != X.device or not t.is_contiguous() or t.numel() < 1):
+            raise abi.GnfError("tab_batch: %s must be a contiguous, non-empty int32 tensor on the device of the data" % name)
+    if out is None:
+        out = torch.empty((max(B, 0), d), dtype=torch.float32, device=X.device)
+    elif out.dtype != torch.float32 or out.device != X.device or tuple(out.shape) != (B, d) or not out.is_contiguous():
+        raise abi.GnfError("tab_batch: out must be a contiguous fp32 tensor [%d, %d] on %s: got %s %s on %s"
+                           % (B, d, X.device, out.dtype, tuple(out.shape), out.device))
+    call("gnf_tab_batch", ptr(X) if n else None, n, d, ldx, abi.rawptr(perm) if perm is not None else None,
+         perm.numel() if perm is not None else 0, int(first), int(stride),
+         abi.rawptr(cursor) if cursor is not None else None, ptr(out) if B > 0 else None, B, stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- graph queries of the DAG conditioner
 def dag_levels_supported(d):
     """the sizes gnf_dag_levels takes (1 <= d <= 4096)"""

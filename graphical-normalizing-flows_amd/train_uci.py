@@ -4,6 +4,10 @@ UCIExperimentsConfigurations.yml), re-hosted on one process per GPU (`torchrun -
 RCCL) with the fused step of gnf_hip.dp.  Datasets are not bundled: pass `-data file.npz` (arrays trn / val / tst,
 standardised as in the reference's loaders) or `-data synthetic` for N(0,1) data of the dataset's dimension.
 
+Opt-in: `-device_batches` gathers the training batches on the device through a Philox-keyed permutation per epoch
+(gnf_hip.dp.DeviceBatches; `-seed`), `-steps_per_replay K` replays K optimisation steps from one hipGraph, and
+`-threshold_sweep` adds the reference's validation at five hard thresholds every 10th epoch (:183-212).
+
 Checkpoints: `model.pt` is `state_dict()` with the reference's keys, `ADAM.pt` is in torch.optim.Adam's format, so
 either side can resume the other's run."""
 import argparse
@@ -76,13 +80,68 @@ def build(args, dim):
 
 
 @torch.no_grad()
-def mean_ll(model, X, b, gen):
-    tot, n = 0., 0
+def mean_ll(model, X, b, gen, on_device=False):
+    """mean over the batches of the batch means.  on_device (-device_batches): the means add up in a device scalar and
+    ONE read-back ends the pass, instead of one per batch"""
+    tot, n = torch.zeros((), device=X.device) if on_device else 0., 0
     for cur in batches(X, b, False, gen):
         z, jac = model(cur)
-        tot += (model.z_log_density(z) + jac).mean().item()
+        ll = (model.z_log_density(z) + jac).mean()
+        tot += ll if on_device else ll.item()
         n += 1
-    return tot / max(n, 1)
+    return float(tot) / max(n, 1)
+
+
+THRESHOLDS = (.95, .5, .1, .01, .0001)
+
+
+def threshold_sweep(model, val, b, gen, epoch, say, on_device=False):
+    """every 10th epoch (UCIExperiments.py:183-212): validation with the deterministic hard-thresholded adjacency at five
+    thresholds, the gate settings restored afterwards.  The mean is over the batch count (the reference divides by the
+    last batch INDEX, :202), and h_thresh returns to the value it had (the reference leaves the last threshold set)"""
+    conds = model.getConditioners()
+    saved = [(c.stoch_gate, c.noise_gate, c.s_thresh, c.h_thresh) for c in conds]
+    for c in conds:
+        c.stoch_gate, c.noise_gate, c.s_thresh = False, False, True
+    try:
+        for th in THRESHOLDS:
+            for c in conds:
+                c.h_thresh = th
+            ll = mean_ll(model, val, b, gen, on_device)
+            with torch.no_grad():
+                dagness = float(max(model.DAGness()))
+            say("epoch: %d - Threshold: %4f - Valid log-likelihood: %4f - <<DAGness>>: %4f" % (epoch, th, ll, dagness))
+    finally:
+        for c, (sg, ng, st, ht) in zip(conds, saved):
+            c.stoch_gate, c.noise_gate, c.s_thresh, c.h_thresh = sg, ng, st, ht
+
+
+def train_epoch(args, model, state, norm_t, trn, src, epoch_no, rank, world, gen):
+    """the optimisation steps of one epoch -> (device sum of the step losses, number of steps).  src = None: the batches
+    are slices of a host permutation drawn from `gen`, copied over; a dp.DeviceBatches: gathered on the device from the
+    permutation of epoch `epoch_no`"""
+    dev = trn.device
+    ll_tot, n = torch.zeros((), device=dev), 0
+    if src is not None:
+        group = int(getattr(args, "steps_per_replay", 1))
+        src.start_epoch(epoch_no)
+        # groups of -steps_per_replay full batches from one hipGraph replay each, while the flow admits it (asked every
+        # epoch: model.step() changes the gate flags); what is left over runs step by step below
+        while group > 1 and src.full_left() >= group and dp.steps_replayable(model, src):
+            ll_tot += dp.train_steps(model, state, src, group, lr=args.learning_rate, weight_decay=args.weight_decay)
+            n += group
+        feed = (src.next() for _ in range(src.left()))
+    else:
+        feed = (trn[rows.to(dev)] for rows in shard_batches(trn.shape[0], max(args.b_size, world), rank, world, gen))
+    for x in feed:
+        if norm_t is MonotonicNormalizer:                    # node-count jitter of the reference (:131-133)
+            k = args.nb_steps + int(torch.randint(0, 10, [1], generator=gen))
+            for nrm in model.getNormalizers():
+                nrm.nb_steps = k
+        loss = dp.train_step(model, state, x, lr=args.learning_rate, weight_decay=args.weight_decay)
+        ll_tot += loss.detach()
+        n += 1
+    return ll_tot, n
 
 
 def train(args):
@@ -119,6 +178,14 @@ def train(args):
     if args.load and os.path.isfile(adam_file):
         state.load_optimizer_state_dict(model, torch.load(adam_file, map_location=dev))
     gen = torch.Generator().manual_seed(1234)
+    on_dev = bool(getattr(args, "device_batches", False))
+    src, epoch0 = None, 0
+    if on_dev:
+        # batches gathered on the device through the sort of Philox keys (dp.DeviceBatches): the permutation of an epoch is a
+        # function of (-seed, the number of epochs trained so far, n) -- the count comes from the optimiser's step number, which
+        # ADAM.pt carries, so a resumed run goes on with the epochs a single run would have reached
+        src = dp.DeviceBatches(trn, max(args.b_size, world), rank, world, seed=args.seed)
+        epoch0 = state.t // max(len(src), 1)
     best = math.inf
     log = open(os.path.join(args.folder, "logs"), "a") if rank == 0 else None
 
@@ -135,17 +202,9 @@ def train(args):
             with torch.no_grad():
                 for c in model.getConditioners():
                     c.constrainA(zero_threshold=0.)
-        ll_tot, n = torch.zeros((), device=dev), 0
+        ll_tot = torch.zeros((), device=dev)
         if not args.test:
-            for rows in shard_batches(trn.shape[0], max(args.b_size, world), rank, world, gen):
-                if norm_t is MonotonicNormalizer:            # node-count jitter of the reference (:131-133)
-                    k = args.nb_steps + int(torch.randint(0, 10, [1], generator=gen))
-                    for nrm in model.getNormalizers():
-                        nrm.nb_steps = k
-                loss = dp.train_step(model, state, trn[rows.to(dev)], lr=args.learning_rate,
-                                     weight_decay=args.weight_decay)
-                ll_tot += loss.detach()
-                n += 1
+            ll_tot, n = train_epoch(args, model, state, norm_t, trn, src, epoch0 + epoch, rank, world, gen)
             ll_tot /= max(n, 1)
             if world > 1:
                 # model.step() decides the dual update / post-processing from this value (DAGConditioner.step): every
@@ -162,7 +221,7 @@ def train(args):
         if norm_t is MonotonicNormalizer:
             for nrm in model.getNormalizers():
                 nrm.nb_steps = args.nb_steps + 20
-        ll_val = mean_ll(model, val, args.b_size, gen)
+        ll_val = mean_ll(model, val, args.b_size, gen, on_dev)
         with torch.no_grad():
             dagness = float(max(model.DAGness()))
         say("epoch: %d - Train loss: %4f - Valid log-likelihood: %4f - <<DAGness>>: %4f - Elapsed time per epoch %4f "
@@ -172,7 +231,10 @@ def train(args):
                 best = -ll_val
                 torch.save(model.state_dict(), os.path.join(args.folder, "best_model.pt"))
                 say("epoch: %d - Test log-likelihood: %4f - <<DAGness>>: %4f"
-                    % (epoch, mean_ll(model, tst, args.b_size, gen), dagness))
+                    % (epoch, mean_ll(model, tst, args.b_size, gen, on_dev), dagness))
+        if getattr(args, "threshold_sweep", False) and epoch % 10 == 0 and cond_t is DAGConditioner:
+            threshold_sweep(model, val, args.b_size, gen, epoch, say, on_dev)      # every rank: same work, rank 0 logs
+        if rank == 0:
             torch.save(model.state_dict(), os.path.join(args.folder, "model.pt"))
             torch.save(state.optimizer_state_dict(model, args.learning_rate, args.weight_decay),
                        os.path.join(args.folder, "ADAM.pt"))
@@ -221,6 +283,13 @@ def parse(argv=None):
     ap.add_argument("-solver", default="CC", type=str, choices=["CC", "CCParallel"])
     ap.add_argument("-gated_front", default=False, action="store_true",
                     help="DAGMLP.gated_front = True on every DAG conditioner: gate and one-hot fused into the first layer")
+    ap.add_argument("-device_batches", default=False, action="store_true",
+                    help="training batches gathered on the device through a Philox-keyed permutation (gnf_tab_batch)")
+    ap.add_argument("-seed", default=0, type=int, help="Philox key of the -device_batches permutations")
+    ap.add_argument("-steps_per_replay", default=1, type=int,
+                    help="with -device_batches: optimisation steps captured into one hipGraph replay")
+    ap.add_argument("-threshold_sweep", default=False, action="store_true",
+                    help="DAG conditioners: validation at five hard thresholds every 10th epoch")
     args = ap.parse_args(argv)
     if args.load_config is not None:                         # a named entry of the yml overrides the command line
         with open(args.config_file) as f:
@@ -229,6 +298,10 @@ def parse(argv=None):
             setattr(args, k, _yml_number(v))
     if args.dataset is None:
         ap.error("-dataset (or a -load_config entry naming one) is required")
+    if args.steps_per_replay < 1:
+        ap.error("-steps_per_replay must be at least 1")
+    if args.steps_per_replay > 1 and not args.device_batches:
+        ap.error("-steps_per_replay needs -device_batches (a replayed group reads its batches from device memory)")
     if not args.folder:
         args.folder = os.path.join("runs", args.load_config or args.dataset)
     return args

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-/* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_*, gnf_image_prep, gnf_dagmlp_*, gnf_dag_levels* and gnf_toy_sample were ADDED under this number (no existing symbol
+/* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_*, gnf_image_prep, gnf_dagmlp_*, gnf_dag_levels*, gnf_toy_sample, gnf_shuffle_keys and gnf_tab_batch were ADDED under this number (no existing symbol
  * changed; a binding written against the earlier 11 keeps working, and tests/test_cifar_factory.py pins the value) */
 #define GNF_ABI_VERSION 11
 #define GNF_EINVAL (-1)   /* bad argument (null pointer, negative size, ...)          */
@@ -759,6 +759,47 @@ int64_t gnf_dag_levels_ws_bytes(int64_t G, int64_t d);
 int gnf_dag_levels(const void* M, int elem_type, int64_t stride_g, int64_t ld, const float* thresholds,
                    int32_t* level, int32_t* info, void* ws, int64_t ws_bytes, int64_t G, int64_t d,
                    gnf_stream_t stream);
+
+/* ---- training batches of the tabular driver from device memory (train_uci.py; reference UCIExperiments.py:120-135,
+ * datasets' batch_iter) ------------------------------------------------------------------------------------------------
+ * gnf_shuffle_keys writes the keys whose ascending sort is one epoch's permutation of n rows:
+ *   keys[i] = ((r[i & 3] >> 1) << 32) | i,  r = philox4x32_10(counter words (lo32(i >> 2), 0, lo32(offset), hi32(offset)),
+ *   key words (lo32(seed), hi32(seed)))  (philox4x32_10 of csrc/gnf_common.h; seed = key, offset = the epoch number).
+ * The high word holds 31 random bits, so every key is non-negative and a signed or unsigned sort, on the device or in numpy,
+ * orders them alike; the low word breaks ties, so (sorted keys) & 0xffffffff is a bijection of 0 .. n-1 by construction and
+ * a pure function of (seed, offset, n): the same on every rank without a broadcast, and after a resume.  The sort is the
+ * caller's (torch.sort); tests/test_uci_batches_host.py restates the layout in numpy, tests/test_gpu_tab_batch.py pins it.
+ * keys: device int64 [n], 8-byte aligned.  Domain 0 <= n < 2^31.
+ * GNF_EINVAL: n < 0, and for n > 0 a NULL keys or one below 8-byte alignment.  GNF_ESHAPE: n >= 2^31.
+ * n == 0: returns 0 without a launch; keys may be NULL.  One launch, one thread per four keys, no LDS, no workspace.
+ * (Added under ABI version 11: no existing symbol changed.) */
+int gnf_shuffle_keys(uint64_t seed, uint64_t offset, int64_t n, int64_t* keys, gnf_stream_t stream);
+
+/* One minibatch gathered out of a tabular data set: output row r < B is row perm[pos + r*stride] of X,
+ *   pos = first, plus cursor[0] when cursor != NULL.
+ * X: device fp32, element (i, j) at X + i*ldx + j, n_rows rows of d columns, ldx >= d (strides in elements).
+ * perm: device int32 [n_perm] row indices, any values (repeats allowed), or NULL for the identity over the rows: the position
+ *   is then the row index, n_perm is ignored and n_rows bounds the positions.
+ * first, stride: the batch is every stride-th position from `first` (stride = the number of ranks, first = the batch's start
+ *   plus the rank: the round-robin deal of train_uci.shard_batches).
+ * cursor: device int32*, or NULL.  The kernel only READS cursor[0]; advancing it is a separate stream-ordered operation of
+ *   the caller, so no workgroup can observe an advanced cursor.  Nothing step-dependent is then passed by value and a captured
+ *   launch can be replayed (gnf_hip.dp.DeviceBatches.gather_into).
+ * x: device [B, d] contiguous.
+ * The kernel CLAMPS the position into [0, n_perm) and the row index into [0, n_rows), as gnf_image_prep clamps its indices: a
+ *   wrong cursor or a perm entry outside the data set prepares a wrong row and never reads outside either array.  Without a
+ *   cursor the last position is known to the host: first + (B-1)*stride >= n_perm is GNF_EINVAL.
+ * Two kernels, chosen by the arguments, with BIT-IDENTICAL results (both only move floats): float4 units when d % 4 == 0,
+ *   ldx % 4 == 0 and X and x are 16-byte aligned; otherwise, at any dword address and any d, the d / 4 quads of a row as
+ *   dwordx4 accesses at dword alignment and its d % 4 last floats singly.  A row is moved by an aligned group of 1 .. 64 lanes
+ *   along the row; its perm entry is read once, by the group's first lane.
+ * GNF_EINVAL: B < 0, d < 1, ldx < d, stride < 1, first < 0, and for B > 0 a NULL X or x, n_rows < 1, perm given with
+ *   n_perm < 1, X / x / perm / cursor below dword alignment, the range check above.  Checked before any launch.
+ * GNF_ESHAPE: B*d >= 2^31.  B == 0: returns 0 without a launch; every pointer may be NULL.
+ * One launch, no LDS, no workspace.
+ * (Added under ABI version 11: no existing symbol changed.) */
+int gnf_tab_batch(const float* X, int64_t n_rows, int64_t d, int64_t ldx, const int32_t* perm, int64_t n_perm,
+                  int64_t first, int64_t stride, const int32_t* cursor, float* x, int64_t B, gnf_stream_t stream);
 
 /* ---- device-ceiling probes (measurement aids for bench.py) ---------------
  * gnf_probe_mfma_f32 launches `blocks` workgroups of 8 wavefronts that do nothing but
