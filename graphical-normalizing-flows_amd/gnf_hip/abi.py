@@ -195,6 +195,8 @@ SIGNATURES = {
     "gnf_dag_levels_ws_bytes": (c_i64, [c_i64, c_i64]),
     "gnf_dag_levels": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_f, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                c_i64, c_i64, c_i64, c_stream]),
+    "gnf_group_bias_fwd": (c_int, [c_f, c_f, c_f, c_int, c_i64, c_i64, c_i64, c_stream]),
+    "gnf_group_bias_bwd": (c_int, [c_f, c_f, c_f, c_f, c_i64, c_i64, c_i64, c_stream]),
     "gnf_probe_mfma_f32": (c_i64, [c_f, c_int, c_int, c_stream]),
     "gnf_probe_copy": (c_int, [c_f, c_f, c_i64, c_stream]),
     "gnf_probe_empty": (c_int, [c_i64, c_int, c_stream]),

@@ -223,15 +223,18 @@ GRAPH_MAX_ELEMS = 1 << 18               # auto-replay only steps small enough to
                                         # elements; cfg5's 3.1 M-element step is GPU-bound and stages GiBs per capture)
 
 
-def train_step(flow, state, x_shard, lr=1e-3, weight_decay=1e-5, optimizer=hip_adam, graph="auto"):
+def train_step(flow, state, x_shard, lr=1e-3, weight_decay=1e-5, optimizer=hip_adam, graph="auto", context=None):
     """fwd + log|det J| + NLL (+ constraints) + bwd on the local shard, one all-reduce, Adam.
     loss_rank = constraints - mean_local(log p); averaging over ranks gives the global mean.
 
     graph="auto": single-process steps of gate-free (graphable) flows on small batches are captured once per variant and
     replayed as a hipGraph (GraphedStep: cfg1 0.68 -> 0.16 ms, cfg3 0.72 -> 0.27 ms per step); graph=False forces the
-    launch-by-launch path.  The returned loss tensor of a replayed step is reused by the next replay."""
+    launch-by-launch path.  The returned loss tensor of a replayed step is reused by the next replay.
+
+    context: the [rows of x_shard, cond_in] context of a conditional flow.  Such a step always runs launch by launch: a
+    captured step has one input buffer, and no GraphedStep is built for it."""
     world = dist.get_world_size() if dist.is_initialized() else 1
-    if (graph and world == 1 and not collective_on() and optimizer is hip_adam and x_shard.is_cuda
+    if (graph and context is None and world == 1 and not collective_on() and optimizer is hip_adam and x_shard.is_cuda
             and x_shard.numel() <= GRAPH_MAX_ELEMS and torch.is_grad_enabled() and GraphedStep.graphable(flow)):
         gs = getattr(state, "_graphed", None)
         if gs is None or gs.flow is not flow or (gs.lr, gs.weight_decay) != (lr, weight_decay):
@@ -239,7 +242,7 @@ def train_step(flow, state, x_shard, lr=1e-3, weight_decay=1e-5, optimizer=hip_a
                                               owned_by_state=True)
             return gs.loss
         return gs(x_shard)
-    loss = accumulate(flow, x_shard)
+    loss = accumulate(flow, x_shard, context=context)
     apply_step(state, lr, weight_decay, optimizer)
     return loss
 
@@ -255,11 +258,12 @@ def _one(like):
     return _ONES[key]
 
 
-def accumulate(flow, x_shard, scale=1.):
+def accumulate(flow, x_shard, scale=1., context=None):
     """fwd + log|det J| + NLL (+ constraints) + bwd of ONE micro-batch; gradients add up in `.grad` until apply_step().
     The image driver's gradient accumulation (ImageExperiments.py:205-213: loss / batch_per_optim_step, backward on
-    every batch, optimiser every k-th) is k calls with scale = 1/k followed by one apply_step."""
-    z, logdet = flow(x_shard)
+    every batch, optimiser every k-th) is k calls with scale = 1/k followed by one apply_step.  context: the micro-batch's
+    rows of the context of a conditional flow (cond_in > 0)."""
+    z, logdet = flow(x_shard) if context is None else flow(x_shard, context)
     loss = flow.loss(z, logdet)
     if scale != 1.:
         loss = loss * scale
@@ -495,6 +499,8 @@ def steps_replayable(flow, batches=None):
         return False
     if not GraphedStep.graphable(flow) or any(hasattr(nrm, "nb_steps") for nrm in flow.getNormalizers()):
         return False
+    if any(getattr(c, "cond_in", 0) for c in flow.getConditioners()):
+        return False                                # a conditional flow: the captured step has no context buffer
     return batches is None or (batches.world == 1 and batches.rows_per_batch * batches.d <= GRAPH_MAX_ELEMS)
 
 

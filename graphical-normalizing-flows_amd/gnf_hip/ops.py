@@ -1161,6 +1161,80 @@ def dag_mlp_rows(x, P, rows32, W1, b1, hot, relu, variable_major=False):
     return a1
 
 
+# ----------------------------------------------------------------------------- DAGMLP first layer with a context
+def _group_rows(t, other, G, what):
+    if t.dim() == 2 and G >= 1 and t.shape[0] % G != 0:
+        abi.check(-2, what)                                          # GNF_ESHAPE, as the entry point itself answers
+    if t.dim() != 2 or other.dim() != 2 or other.shape[1] != t.shape[1] or G < 1 or other.shape[0] * G != t.shape[0]:
+        raise abi.GnfError("%s needs [M, H] rows and a [M / G, H] group array: got %s, %s, G = %d"
+                           % (what, tuple(t.shape), tuple(other.shape), G))
+
+
+def group_bias_fwd(y, cb, G, relu, out=None):
+    """out[r, :] = act(y[r, :] + cb[r // G, :]) (gnf_group_bias_fwd; act = ReLU or the identity).  y: [M, H], cb: [M / G, H],
+    both contiguous; out: None (a new tensor), y itself (in place) or another contiguous [M, H].  No autograd."""
+    G = int(G)
+    _group_rows(y, cb, G, "gnf_group_bias_fwd")
+    if not (y.is_contiguous() and cb.is_contiguous()):
+        raise abi.GnfError("gnf_group_bias_fwd needs contiguous operands")
+    if out is None:
+        out = torch.empty_like(y)
+    elif out.shape != y.shape or not out.is_contiguous():
+        raise abi.GnfError("gnf_group_bias_fwd: out must be a contiguous tensor of y's shape")
+    M, H = y.shape
+    call("gnf_group_bias_fwd", ptr(y), ptr(cb), ptr(out), int(bool(relu)), M, H, G, stream())
+    return out
+
+
+def group_bias_bwd(g, a, G, g_pre=None, g_cb=None):
+    """(g_pre, g_cb) of gnf_group_bias_bwd: g_pre = g * [a > 0] (a: the saved forward output; None for the identity, and g_pre
+    is then g itself unless a tensor is given), g_cb[b] = the sum of the G rows of g_pre of sample b, in ascending order.
+    g_pre: None (a new tensor), g (in place) or another contiguous [M, H]."""
+    G = int(G)
+    if g.dim() != 2 or G < 1 or not g.is_contiguous() or (a is not None and (a.shape != g.shape or not a.is_contiguous())):
+        raise abi.GnfError("gnf_group_bias_bwd needs contiguous [M, H] operands and G >= 1")
+    M, H = g.shape
+    if M % G != 0:
+        abi.check(-2, "gnf_group_bias_bwd")
+    if g_pre is None and a is not None:
+        g_pre = torch.empty_like(g)
+    if g_pre is not None and (g_pre.shape != g.shape or not g_pre.is_contiguous()):
+        raise abi.GnfError("gnf_group_bias_bwd: g_pre must be a contiguous tensor of g's shape")
+    if g_cb is None:
+        g_cb = _empty((M // G, H), g)
+    elif tuple(g_cb.shape) != (M // G, H) or not g_cb.is_contiguous():
+        raise abi.GnfError("gnf_group_bias_bwd: g_cb must be a contiguous [M / G, H] tensor")
+    call("gnf_group_bias_bwd", ptr(g), ptr(a), ptr(g_pre), ptr(g_cb), M, H, G, stream())
+    return (g if g_pre is None else g_pre), g_cb
+
+
+class GroupBiasFn(torch.autograd.Function):
+    """act(y + cb repeated over groups of G rows) (csrc/gnf_group_bias.hip): the context half of a DAGMLP's first layer
+    enters the [B*d, H] pre-activation as one bias row per sample.  act = ReLU (relu) -- the consumer (MLPFn with relu_in)
+    returns the cotangent already gated, and gating it again changes nothing -- or the identity.  The backward is ONE launch:
+    the cotangent of y (g * [out > 0]) and its sum over each group, the cotangent of cb."""
+
+    @staticmethod
+    def forward(ctx, y, cb, G, relu):
+        y, cb = y.contiguous(), cb.contiguous()
+        out = group_bias_fwd(y, cb, G, relu)
+        ctx.G, ctx.relu = int(G), bool(relu)
+        if ctx.relu:
+            ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        a = ctx.saved_tensors[0] if ctx.relu else None
+        g_pre, g_cb = group_bias_bwd(g.contiguous(), a, ctx.G)
+        return (g_pre if ctx.needs_input_grad[0] else None), (g_cb if ctx.needs_input_grad[1] else None), None, None
+
+
+def group_bias(y, cb, G, relu):
+    """act(y[r] + cb[r // G]) for y [M, H] and cb [M / G, H] with gradients for both (GroupBiasFn)"""
+    return GroupBiasFn.apply(y, cb, int(G), bool(relu))
+
+
 # ----------------------------------------------------------------------------- Monotonic (UMNN) normalizer
 _CC = {}
 

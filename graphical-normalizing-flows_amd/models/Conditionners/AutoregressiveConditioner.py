@@ -3,7 +3,7 @@ import torch
 import torch.nn as nn
 
 from gnf_hip import ops
-from .Conditioner import Conditioner, no_context
+from .Conditioner import Conditioner, checked_context
 
 
 class MaskedLinear(nn.Linear):
@@ -94,15 +94,16 @@ class MADE(nn.Module):
     mask is a degree rule deg_in <= deg_out (< for the output layer), so the small-batch kernels evaluate it from the two
     degree vectors whatever the ordering; output neurons are chunked component-major."""
 
-    def __init__(self, nin, hidden_sizes, nout, num_masks=1, natural_ordering=False, random=False, device="cpu"):
+    def __init__(self, nin, hidden_sizes, nout, num_masks=1, natural_ordering=False, random=False, device="cpu", cond_in=0):
         super().__init__()
         self.random = random
         self.nin = nin
         self.nout = nout
         self.hidden_sizes = hidden_sizes
+        self.cond_in = cond_in                           # context columns in FRONT of the nin variables in the first layer
         assert self.nout % self.nin == 0, "nout must be integer multiple of nin"
         net = []
-        hs = [nin] + hidden_sizes + [nout]
+        hs = [nin + cond_in] + hidden_sizes + [nout]
         for h0, h1 in zip(hs, hs[1:]):
             net.extend([MaskedLinear(h0, h1), nn.ReLU()])
         net.pop()
@@ -120,14 +121,19 @@ class MADE(nn.Module):
         rng = np.random.RandomState(self.seed)           # (drawn from even when unused, as the reference does)
         self.seed = (self.seed + 1) % self.num_masks
         self.m = made_degrees(self.nin, self.hidden_sizes, self.random, self.natural_ordering, rng)
-        masks = [self.m[l - 1][:, None] <= self.m[l][None, :] for l in range(L)]
-        masks.append(self.m[L - 1][:, None] < self.m[-1][None, :])
-        degs = [(self.m[l], self.m[l - 1], False) for l in range(L)]
+        # degrees of the columns of each layer: a context column has degree -1, below every variable's, so every unit of the
+        # first layer sees it -- under the strict rule of the output layer too (hidden_sizes == [])
+        din = {l: self.m[l] for l in range(-1, L)}
+        if self.cond_in:
+            din[-1] = np.concatenate([np.full(self.cond_in, -1, dtype=self.m[-1].dtype), self.m[-1]])
+        masks = [din[l - 1][:, None] <= self.m[l][None, :] for l in range(L)]
+        masks.append(din[L - 1][:, None] < self.m[-1][None, :])
+        degs = [(self.m[l], din[l - 1], False) for l in range(L)]
         deg_last = self.m[-1]
         if self.nout > self.nin:
             masks[-1] = np.concatenate([masks[-1]] * int(self.nout / self.nin), axis=1)
             deg_last = np.concatenate([deg_last] * int(self.nout / self.nin))
-        degs.append((deg_last, self.m[L - 1], True))
+        degs.append((deg_last, din[L - 1], True))
         for layer, mk, (do, di, strict) in zip(self.masked_layers(), masks, degs):
             layer.set_mask(mk, do, di, strict)
         # position of input dimension k in the sampled order (a public attribute of the reference's class, :99-101)
@@ -176,17 +182,27 @@ class MADE(nn.Module):
 
 
 class ConditionnalMADE(MADE):
-    """(sic) reference AutoregressiveConditioner.py:115-141; cond_in must be 0."""
+    """(sic) reference AutoregressiveConditioner.py:115-141, whose cond_in > 0 form cannot be constructed.  Here
+    it is a MADE over the nin variables whose first MaskedLinear is [H1, cond_in + nin] -- the context columns first, the
+    reference's cat((context, x), 1) -- with input degree -1 for the context columns: every hidden unit and, without hidden
+    layers, every output sees the context, the outputs of the first variable in the order included.  Degrees, orderings
+    (num_masks, random) and the output layout are those of MADE(nin, ...); cond_in == 0 IS that MADE.  With hidden layers
+    the outputs of the degree-0 variable read no hidden unit (all hidden degrees are >= 0, the output rule is strict): they
+    stay the output bias, as in the unconditional MADE, and only the other variables' outputs move with the context."""
 
     def __init__(self, nin, cond_in, hidden_sizes, nout, num_masks=1, natural_ordering=False, random=False,
                  device="cpu"):
-        super().__init__(nin + cond_in, hidden_sizes, nout, num_masks, natural_ordering, random, device)
+        super().__init__(nin, hidden_sizes, nout, num_masks, natural_ordering, random, device, cond_in=cond_in)
         self.nin_non_cond = nin
-        self.cond_in = cond_in
 
-    def forward(self, x, context):
-        no_context(context, self.cond_in)
-        return super().forward(x)
+    def forward(self, x, context=None):
+        context = checked_context(context, self.cond_in, x)
+        if context is None:
+            return super().forward(x)
+        ls = self.masked_layers()
+        y = ops.mlp(torch.cat((context, x), 1), [(l.weight, l.bias) for l in ls], [l.mask for l in ls],
+                    degs=[l.degree_spec() for l in ls])
+        return y.view(x.shape[0], -1, self.nin).permute(0, 2, 1)
 
 
 class AutoregressiveConditioner(Conditioner):
@@ -197,6 +213,7 @@ class AutoregressiveConditioner(Conditioner):
     def __init__(self, in_size, hidden, out_size, cond_in=0):
         super(AutoregressiveConditioner, self).__init__()
         self.in_size = in_size
+        self.cond_in = cond_in
         self.masked_autoregressive_net = ConditionnalMADE(in_size, cond_in=cond_in, hidden_sizes=hidden,
                                                           nout=out_size * in_size)
 

@@ -7,11 +7,27 @@ def linear_pairs(seq):
 
 
 def no_context(context, cond_in=0):
-    """`context` is dead in the reference: all three conditioners fail when cond_in > 0
-    (SURVEY.md 8b), so only context=None is supported."""
+    """The rule of a conditioner built WITHOUT a context input (cond_in == 0): only context=None is accepted.  (`context` is
+    dead in the reference, whose three conditioners fail when cond_in > 0; with cond_in > 0 the conditioners
+    here take one, see checked_context.)"""
     if context is not None or cond_in:
         raise NotImplementedError("context conditioning (cond_in > 0) is not supported "
                                   "(it raises in the reference as well)")
+
+
+def checked_context(context, cond_in, x):
+    """The context a conditioner built with `cond_in` evaluates x [B, ...] with: None for cond_in == 0 (where any context
+    still raises, as no_context does), else the fp32 [B, cond_in] tensor itself -- ValueError when it is missing or has
+    another shape.  The same tensor serves every step of a flow; normalizers ignore it (divergence table)."""
+    if not cond_in:
+        no_context(context, 0)
+        return None
+    if context is None:
+        raise ValueError("this conditioner was built with cond_in = %d: forward needs a [B, %d] context" % (cond_in, cond_in))
+    if context.dim() != 2 or context.shape[0] != x.shape[0] or context.shape[1] != cond_in:
+        raise ValueError("context must be [%d, %d] (batch of x, cond_in): got %s"
+                         % (x.shape[0], cond_in, tuple(context.shape)))
+    return context
 
 
 class Conditioner(nn.Module):

@@ -8,7 +8,7 @@ import torch
 import torch.nn as nn
 
 from gnf_hip import ops
-from .Conditioner import Conditioner, linear_pairs, no_context, relu_stack
+from .Conditioner import Conditioner, checked_context, linear_pairs, relu_stack
 
 
 def _split(in_size):
@@ -38,9 +38,12 @@ class CouplingConditioner(Conditioner):
         self.constants = nn.Parameter(torch.randn(self.indep_size, out_size))
 
     def forward(self, x, context=None):
-        no_context(context, self.cond_in)
+        context = checked_context(context, self.cond_in, x)
         batch = x.shape[0]
-        learned = self.embeding_net(x[:, :self.indep_size]).view(batch, self.cond_size, self.out_size)
+        first = x[:, :self.indep_size]
+        if context is not None:
+            first = torch.cat((first, context), 1)           # the first Linear is [H, indep + cond_in]; constants see no context
+        learned = self.embeding_net(first).view(batch, self.cond_size, self.out_size)
         return torch.cat((self.constants.expand(batch, self.indep_size, self.out_size), learned), dim=1)
 
     def depth(self):

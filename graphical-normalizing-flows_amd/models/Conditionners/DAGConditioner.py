@@ -4,11 +4,19 @@ import torch
 import torch.nn as nn
 
 from gnf_hip import ops
-from .Conditioner import Conditioner, linear_pairs, no_context
+from .Conditioner import Conditioner, checked_context, linear_pairs
 
 
 # DAGMLP.gated_front of a new net; the measurement behind the value: profiles/dagmlp_gated_ab.txt
 DAGMLP_GATED_FRONT_DEFAULT = False
+# DAGMLP.context_bias of a new net (the context half of the first layer as a bias per sample).  OFF: the bias form wins at
+# none of the tabular shapes measured (profiles/context_front_ab.txt: conditioner forward + backward takes 1.02 - 1.34 x the
+# concatenated form's time at eleven of the twelve (shape, cond_in) pairs over POWER, GAS, HEPMASS, MINIBOONE and BSDS300 with
+# cond_in = 1 and 8, and ties it, 0.995, at BSDS300 with cond_in = 8).
+# The difference is a constant 0.07 - 0.10 ms at every shape: the steps are 0.3 - 0.75 ms of short launches, and the bias form
+# adds about ten of them (two column-block copies of W1 and their scatter in the backward, the per-sample product forward and
+# backward, the two group-bias passes) to save B*d*cond_in floats of traffic that these shapes do not notice.
+DAGMLP_CONTEXT_BIAS_DEFAULT = False
 
 
 class DAGMLP(nn.Module):
@@ -29,9 +37,28 @@ class DAGMLP(nn.Module):
         layers.pop()
         self.net = nn.Sequential(*layers)
         self.gated_front = DAGMLP_GATED_FRONT_DEFAULT
+        self.context_bias = DAGMLP_CONTEXT_BIAS_DEFAULT
 
-    def forward(self, x):
-        return ops.mlp(x, linear_pairs(self.net))
+    def forward(self, e, context=None, group=None):
+        """net((e | context)): row r of e [B * group, in_net] is completed with row r // group of context [B, cond_in] (the
+        group = d masked copies of a sample share its context; columns [in_net, in_net + cond_in) of the first Linear).
+        `context_bias` (default: DAGMLP_CONTEXT_BIAS_DEFAULT) evaluates the context columns ONCE per sample,
+        cb = context W1[:, in_net:]^T + b1 as a [B, H] product, and adds cb to the group's rows of e W1[:, :in_net]^T in one
+        streaming pass (gnf_hip.ops.group_bias) instead of storing and contracting group copies of every context row;
+        False is the plain formulation, the concatenated rows through ops.mlp."""
+        layers = linear_pairs(self.net)
+        if context is None:
+            return ops.mlp(e, layers)
+        if group is None:
+            group = e.shape[0] // max(context.shape[0], 1)
+        if not getattr(self, "context_bias", False):
+            return ops.mlp(torch.cat((e, context.repeat_interleave(group, 0)), 1), layers)
+        W1, b1 = layers[0]
+        in_net = W1.shape[1] - context.shape[1]
+        y = ops.mlp(e, [(W1[:, :in_net], None)])                       # no bias here: b1 rides on the per-sample product
+        cb = ops.mlp(context, [(W1[:, in_net:], b1)])
+        a1 = ops.group_bias(y, cb, group, len(layers) > 1)
+        return ops.mlp(a1, layers[1:], relu_in=True) if len(layers) > 1 else a1
 
     def _front_fits(self, x, hot):
         if not getattr(self, "gated_front", False) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2:
@@ -121,6 +148,9 @@ class DAGConditioner(Conditioner):
         self.noise_gate = False
         in_net = in_size * 2 if hot_encoding else in_size
         if issubclass(type(hidden), nn.Module):
+            if cond_in:
+                raise NotImplementedError("only a DAGMLP embedding net takes a context: cond_in = %d with a %s as `hidden`"
+                                          % (cond_in, type(hidden).__name__))
             self.embedding_net = hidden
         else:
             self.embedding_net = DAGMLP(in_net, hidden, out_size, cond_in)
@@ -287,7 +317,12 @@ class DAGConditioner(Conditioner):
         return net.forward_rows(x, P, rows32, variable_major)
 
     def forward(self, x, context=None):
-        no_context(context, self.cond_in)
+        context = checked_context(context, self.cond_in, x)
+        if context is not None:
+            # the fused fronts (sparse, rows, gated) build the copies inside the first layer and know no context columns:
+            # the masked copies go to memory and the DAGMLP completes row b*d + i with context[b]
+            e = self.masked_inputs(x)
+            return self.embedding_net(e, context, self.in_size).view(x.shape[0], self.in_size, -1)
         P = self.deterministic_importance()
         if P is not None:
             plan = self._sparse_plan(x, None, P)

@@ -7,6 +7,8 @@ standardised as in the reference's loaders) or `-data synthetic` for N(0,1) data
 Opt-in: `-device_batches` gathers the training batches on the device through a Philox-keyed permutation per epoch
 (gnf_hip.dp.DeviceBatches; `-seed`), `-steps_per_replay K` replays K optimisation steps from one hipGraph, and
 `-threshold_sweep` adds the reference's validation at five hard thresholds every 10th epoch (:183-212).
+`-context_cols K` trains a CONDITIONAL flow p(first d - K columns | last K columns): the model is built with cond_in = K
+and every batch is split into (x, context) -- behind the gather when the batches come from the device.
 
 Checkpoints: `model.pt` is `state_dict()` with the reference's keys, `ADAM.pt` is in torch.optim.Adam's format, so
 either side can resume the other's run."""
@@ -65,6 +67,8 @@ def shard_batches(n, b, rank, world, gen):
 def build(args, dim):
     cond_t, norm_t = COND[args.conditioner], NORM[args.normalizer]
     cargs = {"in_size": dim, "hidden": args.emb_net[:-1], "out_size": args.emb_net[-1]}
+    if getattr(args, "context_cols", 0):      # `dim` counts the modelled columns only
+        cargs["cond_in"] = args.context_cols
     if cond_t is DAGConditioner:          # reference :83-88 (gumble_T is pinned to .5 there)
         cargs.update(l1=args.l1, gumble_T=.5, nb_epoch_update=args.nb_steps_dual, hot_encoding=True)
     nargs = {}
@@ -79,13 +83,21 @@ def build(args, dim):
     return model, cond_t, norm_t
 
 
+def split_context(rows, k):
+    """(x, context) of a batch of data rows: the last k columns are the context (-context_cols), None for k = 0"""
+    if not k:
+        return rows, None
+    return rows[:, :rows.shape[1] - k].contiguous(), rows[:, rows.shape[1] - k:].contiguous()
+
+
 @torch.no_grad()
-def mean_ll(model, X, b, gen, on_device=False):
+def mean_ll(model, X, b, gen, on_device=False, context_cols=0):
     """mean over the batches of the batch means.  on_device (-device_batches): the means add up in a device scalar and
     ONE read-back ends the pass, instead of one per batch"""
     tot, n = torch.zeros((), device=X.device) if on_device else 0., 0
     for cur in batches(X, b, False, gen):
-        z, jac = model(cur)
+        cur, ctx = split_context(cur, context_cols)
+        z, jac = model(cur) if ctx is None else model(cur, ctx)
         ll = (model.z_log_density(z) + jac).mean()
         tot += ll if on_device else ll.item()
         n += 1
@@ -95,7 +107,7 @@ def mean_ll(model, X, b, gen, on_device=False):
 THRESHOLDS = (.95, .5, .1, .01, .0001)
 
 
-def threshold_sweep(model, val, b, gen, epoch, say, on_device=False):
+def threshold_sweep(model, val, b, gen, epoch, say, on_device=False, context_cols=0):
     """every 10th epoch (UCIExperiments.py:183-212): validation with the deterministic hard-thresholded adjacency at five
     thresholds, the gate settings restored afterwards.  The mean is over the batch count (the reference divides by the
     last batch INDEX, :202), and h_thresh returns to the value it had (the reference leaves the last threshold set)"""
@@ -107,7 +119,8 @@ def threshold_sweep(model, val, b, gen, epoch, say, on_device=False):
         for th in THRESHOLDS:
             for c in conds:
                 c.h_thresh = th
-            ll = mean_ll(model, val, b, gen, on_device)
+            # (-context_cols 0 makes today's call: a mean_ll installed by a caller keeps its five arguments)
+            ll = mean_ll(model, val, b, gen, on_device, context_cols) if context_cols else mean_ll(model, val, b, gen, on_device)
             with torch.no_grad():
                 dagness = float(max(model.DAGness()))
             say("epoch: %d - Threshold: %4f - Valid log-likelihood: %4f - <<DAGness>>: %4f" % (epoch, th, ll, dagness))
@@ -122,8 +135,9 @@ def train_epoch(args, model, state, norm_t, trn, src, epoch_no, rank, world, gen
     permutation of epoch `epoch_no`"""
     dev = trn.device
     ll_tot, n = torch.zeros((), device=dev), 0
+    ctx_cols = int(getattr(args, "context_cols", 0))
     if src is not None:
-        group = int(getattr(args, "steps_per_replay", 1))
+        group = 1 if ctx_cols else int(getattr(args, "steps_per_replay", 1))     # a conditional step is never replayed
         src.start_epoch(epoch_no)
         # groups of -steps_per_replay full batches from one hipGraph replay each, while the flow admits it (asked every
         # epoch: model.step() changes the gate flags); what is left over runs step by step below
@@ -138,7 +152,11 @@ def train_epoch(args, model, state, norm_t, trn, src, epoch_no, rank, world, gen
             k = args.nb_steps + int(torch.randint(0, 10, [1], generator=gen))
             for nrm in model.getNormalizers():
                 nrm.nb_steps = k
-        loss = dp.train_step(model, state, x, lr=args.learning_rate, weight_decay=args.weight_decay)
+        if ctx_cols:                                         # (a gathered batch is split behind the gather)
+            x, ctx = split_context(x, ctx_cols)
+            loss = dp.train_step(model, state, x, lr=args.learning_rate, weight_decay=args.weight_decay, context=ctx)
+        else:
+            loss = dp.train_step(model, state, x, lr=args.learning_rate, weight_decay=args.weight_decay)
         ll_tot += loss.detach()
         n += 1
     return ll_tot, n
@@ -165,7 +183,10 @@ def train(args):
             dist.init_process_group(backend)
     trn, val, tst = [t.to(dev) for t in load_split(args.data, args.dataset)]
     torch.manual_seed(0)
-    model, cond_t, norm_t = build(args, trn.shape[1])
+    ctx_cols = int(getattr(args, "context_cols", 0))
+    if not 0 <= ctx_cols < trn.shape[1]:
+        raise SystemExit("-context_cols %d: the data has %d columns, at least one must be modelled" % (ctx_cols, trn.shape[1]))
+    model, cond_t, norm_t = build(args, trn.shape[1] - ctx_cols)
     os.makedirs(args.folder, exist_ok=True)
     tag = "_" + args.f_number if args.f_number is not None else ""
     if args.load:
@@ -196,6 +217,10 @@ def train(args):
             log.flush()
 
     say(str(vars(args)))
+    ctx_arg = (ctx_cols,) if ctx_cols else ()                # -context_cols 0 makes exactly today's calls
+    if ctx_cols and getattr(args, "steps_per_replay", 1) > 1:
+        say("-steps_per_replay %d is ignored with -context_cols: a step with a context runs launch by launch"
+            % args.steps_per_replay)
     for epoch in range(args.nb_epoch):
         t0 = time.perf_counter()
         if cond_t is DAGConditioner:
@@ -221,7 +246,7 @@ def train(args):
         if norm_t is MonotonicNormalizer:
             for nrm in model.getNormalizers():
                 nrm.nb_steps = args.nb_steps + 20
-        ll_val = mean_ll(model, val, args.b_size, gen, on_dev)
+        ll_val = mean_ll(model, val, args.b_size, gen, on_dev, *ctx_arg)
         with torch.no_grad():
             dagness = float(max(model.DAGness()))
         say("epoch: %d - Train loss: %4f - Valid log-likelihood: %4f - <<DAGness>>: %4f - Elapsed time per epoch %4f "
@@ -231,9 +256,9 @@ def train(args):
                 best = -ll_val
                 torch.save(model.state_dict(), os.path.join(args.folder, "best_model.pt"))
                 say("epoch: %d - Test log-likelihood: %4f - <<DAGness>>: %4f"
-                    % (epoch, mean_ll(model, tst, args.b_size, gen, on_dev), dagness))
+                    % (epoch, mean_ll(model, tst, args.b_size, gen, on_dev, *ctx_arg), dagness))
         if getattr(args, "threshold_sweep", False) and epoch % 10 == 0 and cond_t is DAGConditioner:
-            threshold_sweep(model, val, args.b_size, gen, epoch, say, on_dev)      # every rank: same work, rank 0 logs
+            threshold_sweep(model, val, args.b_size, gen, epoch, say, on_dev, *ctx_arg)   # every rank: same work, rank 0 logs
         if rank == 0:
             torch.save(model.state_dict(), os.path.join(args.folder, "model.pt"))
             torch.save(state.optimizer_state_dict(model, args.learning_rate, args.weight_decay),
@@ -290,6 +315,8 @@ def parse(argv=None):
                     help="with -device_batches: optimisation steps captured into one hipGraph replay")
     ap.add_argument("-threshold_sweep", default=False, action="store_true",
                     help="DAG conditioners: validation at five hard thresholds every 10th epoch")
+    ap.add_argument("-context_cols", default=0, type=int,
+                    help="the last K columns of the data are the context of a conditional flow over the others (cond_in = K)")
     args = ap.parse_args(argv)
     if args.load_config is not None:                         # a named entry of the yml overrides the command line
         with open(args.config_file) as f:
@@ -300,6 +327,8 @@ def parse(argv=None):
         ap.error("-dataset (or a -load_config entry naming one) is required")
     if args.steps_per_replay < 1:
         ap.error("-steps_per_replay must be at least 1")
+    if args.context_cols < 0:
+        ap.error("-context_cols must not be negative")
     if args.steps_per_replay > 1 and not args.device_batches:
         ap.error("-steps_per_replay needs -device_batches (a replayed group reads its batches from device memory)")
     if not args.folder:

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-/* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_*, gnf_image_prep, gnf_dagmlp_*, gnf_dag_levels*, gnf_toy_sample, gnf_shuffle_keys and gnf_tab_batch were ADDED under this number (no existing symbol
+/* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_*, gnf_image_prep, gnf_dagmlp_*, gnf_dag_levels*, gnf_toy_sample, gnf_shuffle_keys, gnf_tab_batch and gnf_group_bias_* were ADDED under this number (no existing symbol
  * changed; a binding written against the earlier 11 keeps working, and tests/test_cifar_factory.py pins the value) */
 #define GNF_ABI_VERSION 11
 #define GNF_EINVAL (-1)   /* bad argument (null pointer, negative size, ...)          */
@@ -800,6 +800,27 @@ int gnf_shuffle_keys(uint64_t seed, uint64_t offset, int64_t n, int64_t* keys, g
  * (Added under ABI version 11: no existing symbol changed.) */
 int gnf_tab_batch(const float* X, int64_t n_rows, int64_t d, int64_t ldx, const int32_t* perm, int64_t n_perm,
                   int64_t first, int64_t stride, const int32_t* cursor, float* x, int64_t B, gnf_stream_t stream);
+
+/* ---- a bias per group of G consecutive rows: the context half of a DAGMLP's first layer -------------------------------
+ * The d masked copies of a sample share one context row, so the context columns of the first Linear contribute
+ * cb = context W1[:, in_net:]^T, ONE row per sample, to the G = d rows of that sample (DAGMLP.forward with a context).
+ *   fwd:  out[r, n]   = act(y[r, n] + cb[r / G, n])      r < M, n < H;  relu != 0: act = ReLU, else the identity
+ *   bwd:  g_pre[r, n] = g[r, n] * [a[r, n] > 0]          a: the saved forward OUTPUT, or NULL for the identity (g_pre = g)
+ *         g_cb[b, n]  = sum_{i < G} g_pre[b*G + i, n]    accumulated in fp32 in ascending i
+ * y, out, g, a, g_pre: [M, H] contiguous;  cb, g_cb: [M / G, H] contiguous.  out may be y and g_pre may be g (in place: a
+ * thread reads an element before it writes it and is its only writer).  g_pre may be NULL when a is NULL.
+ * Every element of g_pre and g_cb has one writer that adds in a fixed order: no atomics, no partial sums, the same bits on
+ * every call and for every deal of the work to wavefronts.
+ * Two kernels each, chosen by the arguments, with BIT-IDENTICAL results: 16-byte accesses when H % 4 == 0 and every array is
+ * 16-byte aligned; single dwords at any dword address and any H otherwise.
+ * GNF_EINVAL: M < 0, H < 1, G < 1, and for M > 0 a NULL y / cb / out (g / g_cb; a without g_pre) or a pointer below dword
+ * alignment.  GNF_ESHAPE: M % G != 0.  M == 0: returns 0 without a launch; every pointer may be NULL.
+ * One launch, no LDS, no workspace.
+ * (Added under ABI version 11: no existing symbol changed.) */
+int gnf_group_bias_fwd(const float* y, const float* cb, float* out, int relu, int64_t M, int64_t H, int64_t G,
+                       gnf_stream_t stream);
+int gnf_group_bias_bwd(const float* g, const float* a, float* g_pre, float* g_cb, int64_t M, int64_t H, int64_t G,
+                       gnf_stream_t stream);
 
 /* ---- device-ceiling probes (measurement aids for bench.py) ---------------
  * gnf_probe_mfma_f32 launches `blocks` workgroups of 8 wavefronts that do nothing but
