@@ -16,7 +16,14 @@
 //   n >= 8 (and TB = 16): v_mfma_f32_16x16x4_f32, batch rows on M, the new units padded to 16 on N, K split over the four
 //           wavefronts in chunks of 16 and reduced through LDS in a fixed order;
 //   n <  8: plain dot products, 256 / TB lanes per batch row over K, reduced inside the lane group.
-// fp32 throughout, fp32 accumulation, a fixed summation order for a given (net, B).
+// fp32 throughout, fp32 accumulation, a fixed summation order for a given (net, cond_in, B).
+//
+// A conditional MADE (ConditionnalMADE, cond_in = c > 0) puts c context columns of input degree -1 in FRONT of the variables
+// in its first layer.  Degree -1 is known before step 0, so the context simply heads the activation row,
+// [context | x in degree order | hidden 0 | ...], and the first layer's prefix at step t is K = c + t.  Without hidden
+// layers the output layer is that first layer (K = c at step 0: the outputs of the degree-0 variable move with the
+// context); with hidden layers those outputs read no hidden unit and stay the output bias.  c = 0 is the unconditional
+// kernel, instruction for instruction on the arithmetic path.
 #include "gnf_common.h"
 
 namespace {
@@ -31,9 +38,10 @@ __host__ __device__ inline int round_up(int v, int m) { return (v + m - 1) / m *
 // what host and device agree on: the activation row and the packed parameter image
 struct MadeLayout {
   int nh, d, out;
-  int A;                        // floats per activation row: [x in degree order | hidden layer 0 | ... ], made odd
+  int c;                        // context columns (input degree -1) in front of the variables
+  int A;                        // floats per activation row: [context | x in degree order | hidden layer 0 | ... ], made odd
   int width[kMaxH];
-  int act_off[kMaxH];           // first column of hidden layer l in the activation row (the inputs start at 0)
+  int act_off[kMaxH];           // first column of hidden layer l in the activation row (context and inputs start at 0)
   int K[kMaxH + 1];             // in_features of layer l (l = nh: the output layer)
   int ldw[kMaxH + 1];           // K rounded up to 16: row pitch of the packed weights, the tail zero-filled
   int rows[kMaxH + 1];          // out_features
@@ -42,10 +50,13 @@ struct MadeLayout {
   int64_t pack_floats;
 };
 
-int make_layout(const gnf_made_net* net, MadeLayout* lay) {
-  if (!net || net->nh < 0 || net->nh > kMaxH || net->d <= 0 || net->out <= 0) return GNF_EINVAL;
-  lay->nh = net->nh; lay->d = net->d; lay->out = net->out;
-  int64_t A = net->d, off = 0;
+int make_layout(const gnf_made_net* net, int cond_in, MadeLayout* lay) {
+  if (!net || net->nh < 0 || net->nh > kMaxH || net->d <= 0 || net->out <= 0 || cond_in < 0) return GNF_EINVAL;
+  if (cond_in > (1 << 26)) return GNF_ESHAPE;          // the kernel indexes a tile's context, up to 16 * cond_in floats, with an int
+  lay->nh = net->nh; lay->d = net->d; lay->out = net->out; lay->c = cond_in;
+  const int64_t A0 = (int64_t)cond_in + net->d;
+  if (A0 > (1 << 30)) return GNF_ESHAPE;
+  int64_t A = A0, off = 0;
   for (int l = 0; l <= net->nh; ++l) {
     if (l < net->nh) {
       if (net->width[l] <= 0) return GNF_EINVAL;
@@ -53,7 +64,7 @@ int make_layout(const gnf_made_net* net, MadeLayout* lay) {
       lay->act_off[l] = (int)A;
       A += net->width[l];
     }
-    lay->K[l] = l == 0 ? net->d : net->width[l - 1];
+    lay->K[l] = l == 0 ? (int)A0 : net->width[l - 1];
     lay->rows[l] = l < net->nh ? net->width[l] : net->d * net->out;
     if ((int64_t)net->d * net->out > (1 << 30) || A > (1 << 30)) return GNF_ESHAPE;
     lay->ldw[l] = round_up(lay->K[l], 16);
@@ -76,8 +87,9 @@ struct PackArgs {
   const int32_t* var_of_step;
 };
 
-// hidden layer l: Wp[u'][k'] = W[order_l[u']][order_{l-1}[k']] (order_{-1} = var_of_step); output layer: row t * out + c is
-// output neuron c * d + var_of_step[t].  Columns K .. ldw-1 are zeros.
+// hidden layer l: Wp[u'][k'] = W[order_l[u']][order_{l-1}[k']]; the first layer's columns are [context | variables]:
+// column k < c is column k, column c + j is column c + var_of_step[j].  Output layer: row t * out + c is output neuron
+// c * d + var_of_step[t].  Columns K .. ldw-1 are zeros.
 __global__ void made_prefix_pack_k(PackArgs a, float* __restrict__ pack) {
   const MadeLayout& L = a.lay;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < L.pack_floats; e += (int64_t)gridDim.x * blockDim.x) {
@@ -89,7 +101,7 @@ __global__ void made_prefix_pack_k(PackArgs a, float* __restrict__ pack) {
       const int64_t i = e - L.w_off[l];
       const int r = (int)(i / L.ldw[l]), k = (int)(i - (int64_t)r * L.ldw[l]);
       const int src = l < L.nh ? a.order[l][r] : (r % L.out) * L.d + a.var_of_step[r / L.out];
-      if (k < L.K[l]) v = a.W[l][(int64_t)src * L.K[l] + in_order[k]];
+      if (k < L.K[l]) v = a.W[l][(int64_t)src * L.K[l] + (l > 0 ? in_order[k] : k < L.c ? k : L.c + in_order[k - L.c])];
     } else {
       const int r = (int)(e - L.b_off[l]);
       if (r < L.rows[l]) v = a.b[l][l < L.nh ? a.order[l][r] : (r % L.out) * L.d + a.var_of_step[r / L.out]];
@@ -175,8 +187,9 @@ __device__ __forceinline__ void layer_step(const float* __restrict__ W, int ldw,
 
 template <int TB, bool kLds>
 __global__ __launch_bounds__(kThreads) void made_prefix_k(StepArgs s, const float* __restrict__ pack,
-                                                          const float* __restrict__ z, float* x, float* __restrict__ h_out,
-                                                          int t0, int t1, int mode, float* ws, int64_t B) {
+                                                          const float* __restrict__ context, const float* __restrict__ z,
+                                                          float* x, float* __restrict__ h_out, int t0, int t1, int mode,
+                                                          float* ws, int64_t B) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const MadeLayout& L = s.lay;
   float* red = smem;
@@ -184,12 +197,18 @@ __global__ __launch_bounds__(kThreads) void made_prefix_k(StepArgs s, const floa
   const int tid = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.x * TB;
   const int nrows = (int)(B - row0 < TB ? B - row0 : TB);
-  const int A = L.A, d = L.d, out = L.out, nh = L.nh;
+  const int A = L.A, d = L.d, out = L.out, nh = L.nh, c = L.c;
   float* act = kLds ? hbuf + round_up(TB * out, 4) : ws + (size_t)row0 * A;
 
+  if (c > 0 && (kLds || t0 == 0)) {
+    // the context heads the tile's activation rows, once per inversion: later step launches find it in the workspace.
+    // One float per load: the caller's rows are dword-aligned, no more
+    for (int i = tid; i < nrows * c; i += kThreads) act[(size_t)(i / c) * A + i % c] = context[row0 * c + i];
+    __syncthreads();
+  }
   if (!kLds && t0 >= 1) {
     // the column the caller inverted since the previous launch: the newest input of this one
-    if (tid < nrows) act[(size_t)tid * A + t0 - 1] = x[(row0 + tid) * d + s.var_of_step[t0 - 1]];
+    if (tid < nrows) act[(size_t)tid * A + c + t0 - 1] = x[(row0 + tid) * d + s.var_of_step[t0 - 1]];
     __syncthreads();
   }
   for (int t = t0; t < t1; ++t) {
@@ -199,12 +218,12 @@ __global__ __launch_bounds__(kThreads) void made_prefix_k(StepArgs s, const floa
     if (t >= 1)
       for (int l = 0; l < nh; ++l) {
         const int n0 = s.off[l][t - 1], n1 = s.off[l][t];             // the units of degree t - 1
-        const int K = l == 0 ? t : s.off[l - 1][t];                    // inputs / units below of degree <= t - 1
+        const int K = l == 0 ? c + t : s.off[l - 1][t];                // context, inputs / units below of degree <= t - 1
         layer_step<TB>(pack + L.w_off[l] + (size_t)n0 * L.ldw[l], L.ldw[l], L.rows[l] - n0, pack + L.b_off[l] + n0,
                        n1 - n0, K, act + (l == 0 ? 0 : L.act_off[l - 1]), A, act + L.act_off[l] + n0, A, true, nrows, red);
       }
     {
-      const int K = nh == 0 ? t : s.off[nh - 1][t];                    // strict rule: degree < t
+      const int K = nh == 0 ? c + t : s.off[nh - 1][t];                // strict rule: degree < t (the context's is -1)
       const int n0 = t * out;
       layer_step<TB>(pack + L.w_off[nh] + (size_t)n0 * L.ldw[nh], L.ldw[nh], L.rows[nh] - n0, pack + L.b_off[nh] + n0,
                      out, K, act + (nh == 0 ? 0 : L.act_off[nh - 1]), A, hbuf, out, false, nrows, red);
@@ -217,7 +236,7 @@ __global__ __launch_bounds__(kThreads) void made_prefix_k(StepArgs s, const floa
       const float sg = expf(fminf(fmaxf(hbuf[tid * out + 1], -5.f), 2.f));
       const float xv = (zv - mu) / sg;
       x[(row0 + tid) * d + v] = xv;
-      act[(size_t)tid * A + t] = xv;
+      act[(size_t)tid * A + c + t] = xv;
     }
     __syncthreads();
   }
@@ -235,12 +254,12 @@ int64_t lds_bytes(const MadeLayout& lay, int TB, bool with_act) {
 }
 
 template <int TB>
-int launch(const StepArgs& s, bool lds, size_t smem, int64_t grid, hipStream_t st, const float* pack, const float* z,
-           float* x, float* h_out, int t0, int t1, int mode, float* ws, int64_t B) {
-  hipError_t e = lds ? gnf_launch_lds(made_prefix_k<TB, true>, dim3((unsigned)grid), dim3(kThreads), smem, st, s, pack, z, x,
-                                      h_out, t0, t1, mode, ws, B)
-                     : gnf_launch_lds(made_prefix_k<TB, false>, dim3((unsigned)grid), dim3(kThreads), smem, st, s, pack, z, x,
-                                      h_out, t0, t1, mode, ws, B);
+int launch(const StepArgs& s, bool lds, size_t smem, int64_t grid, hipStream_t st, const float* pack, const float* context,
+           const float* z, float* x, float* h_out, int t0, int t1, int mode, float* ws, int64_t B) {
+  hipError_t e = lds ? gnf_launch_lds(made_prefix_k<TB, true>, dim3((unsigned)grid), dim3(kThreads), smem, st, s, pack,
+                                      context, z, x, h_out, t0, t1, mode, ws, B)
+                     : gnf_launch_lds(made_prefix_k<TB, false>, dim3((unsigned)grid), dim3(kThreads), smem, st, s, pack,
+                                      context, z, x, h_out, t0, t1, mode, ws, B);
   return e == hipSuccess ? 0 : (int)e;
 }
 
@@ -248,15 +267,15 @@ int launch(const StepArgs& s, bool lds, size_t smem, int64_t grid, hipStream_t s
 
 extern "C" {
 
-int64_t gnf_made_prefix_pack_floats(const gnf_made_net* net) {
+int64_t gnf_made_prefix_ctx_pack_floats(const gnf_made_net* net, int cond_in) {
   MadeLayout lay;
-  const int rc = make_layout(net, &lay);
+  const int rc = make_layout(net, cond_in, &lay);
   return rc ? rc : lay.pack_floats;
 }
 
-int gnf_made_prefix_pack(const gnf_made_net* net, float* pack, gnf_stream_t stream) {
+int gnf_made_prefix_ctx_pack(const gnf_made_net* net, int cond_in, float* pack, gnf_stream_t stream) {
   PackArgs a;
-  const int rc = make_layout(net, &a.lay);
+  const int rc = make_layout(net, cond_in, &a.lay);
   if (rc) return rc;
   if (!pack || !net->var_of_step) return GNF_EINVAL;
   if ((uintptr_t)pack & 15) return GNF_EINVAL;          // the step kernel reads the image's rows as 16-byte quads
@@ -274,25 +293,26 @@ int gnf_made_prefix_pack(const gnf_made_net* net, float* pack, gnf_stream_t stre
   return 0;
 }
 
-int64_t gnf_made_prefix_ws_bytes(const gnf_made_net* net, int64_t B) {
+int64_t gnf_made_prefix_ctx_ws_bytes(const gnf_made_net* net, int cond_in, int64_t B) {
   MadeLayout lay;
-  const int rc = make_layout(net, &lay);
+  const int rc = make_layout(net, cond_in, &lay);
   if (rc) return rc;
   if (B < 0) return GNF_EINVAL;
   return 4 * B * lay.A;
 }
 
-int gnf_made_prefix(const gnf_made_net* net, const float* pack, const float* z, float* x, float* h_out, int t0, int t1,
-                    int normalizer_mode, int64_t B, void* ws, int64_t ws_bytes, gnf_stream_t stream) {
+int gnf_made_prefix_ctx(const gnf_made_net* net, int cond_in, const float* context, const float* pack, const float* z,
+                        float* x, float* h_out, int t0, int t1, int normalizer_mode, int64_t B, void* ws, int64_t ws_bytes,
+                        gnf_stream_t stream) {
   StepArgs s;
-  const int rc = make_layout(net, &s.lay);
+  const int rc = make_layout(net, cond_in, &s.lay);
   if (rc) return rc;
   if (B < 0 || t0 < 0 || t1 < t0 || t1 > net->d) return GNF_EINVAL;
   if (normalizer_mode != GNF_MADE_NORM_NONE && normalizer_mode != GNF_MADE_NORM_AFFINE) return GNF_EINVAL;
   if (normalizer_mode == GNF_MADE_NORM_NONE && t1 > t0 + 1) return GNF_EINVAL;
   if (normalizer_mode == GNF_MADE_NORM_AFFINE && net->out < 2) return GNF_ESHAPE;
   if (B == 0 || t1 == t0) return 0;
-  if (!pack || !x || !net->var_of_step) return GNF_EINVAL;
+  if (!pack || !x || !net->var_of_step || (cond_in > 0 && !context)) return GNF_EINVAL;
   if ((uintptr_t)pack & 15) return GNF_EINVAL;          // rows of the weight image are read as 16-byte quads (ld4)
   if (normalizer_mode == GNF_MADE_NORM_NONE ? !h_out : !z) return GNF_EINVAL;
   for (int l = 0; l < net->nh; ++l) {
@@ -309,11 +329,26 @@ int gnf_made_prefix(const gnf_made_net* net, const float* pack, const float* z, 
   if (!lds && (!ws || ws_bytes < 4 * B * s.lay.A)) return GNF_EWS;
   const size_t smem = (size_t)lds_bytes(s.lay, TB, lds);
   hipStream_t st = (hipStream_t)stream;
+  float* w = (float*)ws;
   switch (TB) {
-    case 4: return launch<4>(s, lds, smem, grid, st, pack, z, x, h_out, t0, t1, normalizer_mode, (float*)ws, B);
-    case 8: return launch<8>(s, lds, smem, grid, st, pack, z, x, h_out, t0, t1, normalizer_mode, (float*)ws, B);
-    default: return launch<16>(s, lds, smem, grid, st, pack, z, x, h_out, t0, t1, normalizer_mode, (float*)ws, B);
+    case 4: return launch<4>(s, lds, smem, grid, st, pack, context, z, x, h_out, t0, t1, normalizer_mode, w, B);
+    case 8: return launch<8>(s, lds, smem, grid, st, pack, context, z, x, h_out, t0, t1, normalizer_mode, w, B);
+    default: return launch<16>(s, lds, smem, grid, st, pack, context, z, x, h_out, t0, t1, normalizer_mode, w, B);
   }
+}
+
+// the unconditional entry points: cond_in = 0 of the same code
+int64_t gnf_made_prefix_pack_floats(const gnf_made_net* net) { return gnf_made_prefix_ctx_pack_floats(net, 0); }
+
+int gnf_made_prefix_pack(const gnf_made_net* net, float* pack, gnf_stream_t stream) {
+  return gnf_made_prefix_ctx_pack(net, 0, pack, stream);
+}
+
+int64_t gnf_made_prefix_ws_bytes(const gnf_made_net* net, int64_t B) { return gnf_made_prefix_ctx_ws_bytes(net, 0, B); }
+
+int gnf_made_prefix(const gnf_made_net* net, const float* pack, const float* z, float* x, float* h_out, int t0, int t1,
+                    int normalizer_mode, int64_t B, void* ws, int64_t ws_bytes, gnf_stream_t stream) {
+  return gnf_made_prefix_ctx(net, 0, nullptr, pack, z, x, h_out, t0, t1, normalizer_mode, B, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -165,14 +165,16 @@ MADE_NORM_NONE, MADE_NORM_AFFINE = abi.MADE_NORM_NONE, abi.MADE_NORM_AFFINE
 
 def _made_net(params, plan):
     """params: [W0, b0, ..., W_out, b_out] (nn.Linear layout) of a MADE; plan: MADE.prefix_plan() -> gnf_made_net.  The
-    returned struct holds raw pointers: the caller keeps params and plan alive while it is in use."""
+    returned struct holds raw pointers: the caller keeps params and plan alive while it is in use.  A conditional plan
+    (prefix_plan(with_context=True), plan["cond_in"] = c > 0) has the c context columns in front of the variables in the
+    first layer: W0 is [rows, c + d]."""
     nh = len(plan["widths"])
     if len(params) != 2 * (nh + 1) or nh > abi.MADE_MAX_HIDDEN:
         raise abi.GnfError("MADE prefix kernel: 0..%d hidden layers, one (weight, bias) pair per layer"
                            % abi.MADE_MAX_HIDDEN)
     net = abi.MadeNet()
     net.nh, net.d, net.out, net.max_new = nh, plan["d"], plan["out"], plan["max_new"]
-    fan_in = plan["d"]
+    fan_in = plan["d"] + _plan_cond_in(plan)
     for l in range(nh + 1):
         W, b = params[2 * l], params[2 * l + 1]
         rows = plan["widths"][l] if l < nh else plan["d"] * plan["out"]
@@ -188,17 +190,30 @@ def _made_net(params, plan):
     return net
 
 
+def _plan_cond_in(plan):
+    c = int(plan.get("cond_in", 0))
+    if c < 0:
+        raise abi.GnfError("MADE prefix kernel: cond_in = %d" % c)
+    return c
+
+
 @torch.no_grad()
 def made_prefix_pack(params, plan):
     """the prefix kernel's weight image (weights and biases in degree order): parameter-only, one launch; a caller that
     steps through an inversion builds it once (AutoregressiveConditioner.hold_prefix_pack)"""
     params = [p.detach() for p in params]
-    net = _made_net(params, plan)
-    nfl = abi.load().gnf_made_prefix_pack_floats(ctypes.byref(net))
+    net, c = _made_net(params, plan), _plan_cond_in(plan)
+    if c == 0:
+        nfl = abi.load().gnf_made_prefix_pack_floats(ctypes.byref(net))
+    else:
+        nfl = abi.load().gnf_made_prefix_ctx_pack_floats(ctypes.byref(net), c)
     if nfl < 0:
         abi.check(int(nfl), "gnf_made_prefix_pack_floats")
     pack = _empty((int(nfl),), params[0])
-    call("gnf_made_prefix_pack", ctypes.byref(net), ptr(pack), stream())
+    if c == 0:
+        call("gnf_made_prefix_pack", ctypes.byref(net), ptr(pack), stream())
+    else:
+        call("gnf_made_prefix_ctx_pack", ctypes.byref(net), c, ptr(pack), stream())
     return pack
 
 
@@ -206,40 +221,54 @@ def made_prefix_pack(params, plan):
 def made_prefix_workspace(params, plan, batch):
     """the activation workspace that carries an inversion of `batch` rows from one made_prefix_steps call to the next"""
     params = [p.detach() for p in params]
-    net = _made_net(params, plan)
-    nbytes = abi.load().gnf_made_prefix_ws_bytes(ctypes.byref(net), int(batch))
+    net, c = _made_net(params, plan), _plan_cond_in(plan)
+    if c == 0:
+        nbytes = abi.load().gnf_made_prefix_ws_bytes(ctypes.byref(net), int(batch))
+    else:
+        nbytes = abi.load().gnf_made_prefix_ctx_ws_bytes(ctypes.byref(net), c, int(batch))
     if nbytes < 0:
         abi.check(int(nbytes), "gnf_made_prefix_ws_bytes")
     return _ws(nbytes, params[0])
 
 
 @torch.no_grad()
-def made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=None, ws=None):
+def made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=None, ws=None, context=None):
     """Steps t0 <= t < t1 of the column-by-column inversion of a MADE step (gnf_made_prefix): z, x [B, d] fp32 contiguous.
     MADE_NORM_AFFINE writes column var_of_step[t] of x per step ((0, d): the whole inversion, one launch);
     MADE_NORM_NONE (t1 == t0 + 1) writes the conditioner outputs of that variable to h_out [B, out] and leaves the column
     to the caller.  ws (made_prefix_workspace): the same buffer for every call of one inversion; allocated here when a call
-    that needs one comes without."""
+    that needs one comes without.  context: the contiguous fp32 [B, cond_in] device tensor of a conditional plan
+    (gnf_made_prefix_ctx), None for cond_in == 0."""
     params = [p.detach() for p in params]
-    net = _made_net(params, plan)
+    net, c = _made_net(params, plan), _plan_cond_in(plan)
     B, d = x.shape
     if d != plan["d"] or not x.is_contiguous() or (z is not None and (tuple(z.shape) != (B, d) or not z.is_contiguous())):
         raise abi.GnfError("made_prefix_steps: z and x must be contiguous [B, %d]" % plan["d"])
     if h_out is not None and (tuple(h_out.shape) != (B, plan["out"]) or not h_out.is_contiguous()):
         raise abi.GnfError("made_prefix_steps: h_out must be contiguous [B, %d]" % plan["out"])
+    if c == 0:
+        if context is not None:
+            raise abi.GnfError("made_prefix_steps: a context for a plan with cond_in = 0")
+        name, head = "gnf_made_prefix", (ctypes.byref(net),)
+    else:
+        if (context is None or not context.is_cuda or context.device != x.device or context.dtype != torch.float32
+                or tuple(context.shape) != (B, c) or not context.is_contiguous()):
+            raise abi.GnfError("made_prefix_steps: context must be a contiguous fp32 [B, %d] tensor on the device of x" % c)
+        name, head = "gnf_made_prefix_ctx", (ctypes.byref(net), c, ptr(context))
     if ws is None and not (t0 == 0 and t1 == d):
         ws = made_prefix_workspace(params, plan, B)
-    args = lambda w: (ctypes.byref(net), ptr(pack), ptr(z), ptr(x), ptr(h_out), int(t0), int(t1), int(mode), B,
-                      None if w is None else ctypes.c_void_p(w.data_ptr()), 0 if w is None else w.numel() * 4, stream())
+    args = lambda w: head + (ptr(pack), ptr(z), ptr(x), ptr(h_out), int(t0), int(t1), int(mode), B,
+                             None if w is None else ctypes.c_void_p(w.data_ptr()), 0 if w is None else w.numel() * 4,
+                             stream())
     if ws is None:
         # a whole inversion whose tile of activations fits in LDS needs no workspace; the library says when it does not
-        rc = getattr(abi.load(), "gnf_made_prefix")(*args(None))
+        rc = getattr(abi.load(), name)(*args(None))
         if rc == 0:
             return x
         if rc != -3:
-            abi.check(rc, "gnf_made_prefix")
+            abi.check(rc, name)
         ws = made_prefix_workspace(params, plan, B)
-    call("gnf_made_prefix", *args(ws))
+    call(name, *args(ws))
     return x
 
 

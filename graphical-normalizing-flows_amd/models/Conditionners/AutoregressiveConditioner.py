@@ -146,22 +146,30 @@ class MADE(nn.Module):
 
     _prefix_cache = None                 # (key, plan): plain attributes, nothing enters the state_dict
 
-    def prefix_plan(self):
+    def prefix_plan(self, with_context=False):
         """made_prefix_plan(self.m) with its tables on the weights' device, or None when the masks in force are not the
         degree rule of self.m (a loaded checkpoint, a hand-set mask) or the net is conditioned on a context.  Cached;
-        rebuilt when update_masks() installs another ordering or a mask buffer changes."""
-        if getattr(self, "cond_in", 0) != 0:
+        rebuilt when update_masks() installs another ordering or a mask buffer changes.
+        with_context=True: the plan of a net with cond_in > 0 as well -- the same tables plus plan["cond_in"]; the context
+        columns have input degree -1 and sit in front of the variables in the first layer, which is what the prefix
+        kernel's gnf_made_prefix_ctx entry points evaluate (a caller of such a plan hands the context over)."""
+        cond_in = int(getattr(self, "cond_in", 0))
+        if cond_in != 0 and not with_context:
             return None
+        with_context = cond_in != 0                      # (cond_in == 0: one plan, one cache entry, whatever the flag)
         layers = self.masked_layers()
         specs = [l.degree_spec() for l in layers]
         if any(s is None for s in specs):
             return None
-        key = (tuple(l._deg_checked for l in layers), layers[0].weight.device)
+        key = (tuple(l._deg_checked for l in layers), layers[0].weight.device, bool(with_context))
         cache = self._prefix_cache
         if cache is None or cache[0] is not self.m or cache[1] != key:
             L, dev = len(self.hidden_sizes), layers[0].weight.device
             reps = self.nout // self.nin
-            want = [(self.m[l], self.m[l - 1], False) for l in range(L)] + [(np.tile(self.m[-1], reps), self.m[L - 1], True)]
+            din = {l: self.m[l] for l in range(-1, L)}
+            if cond_in:
+                din[-1] = np.concatenate([np.full(cond_in, -1, dtype=self.m[-1].dtype), self.m[-1]])
+            want = [(self.m[l], din[l - 1], False) for l in range(L)] + [(np.tile(self.m[-1], reps), din[L - 1], True)]
             same = all(strict == ws and np.array_equal(do.cpu().numpy(), np.asarray(wo, dtype=np.float32))
                        and np.array_equal(di.cpu().numpy(), np.asarray(wi, dtype=np.float32))
                        for (do, di, strict), (wo, wi, ws) in zip(specs, want))
@@ -172,6 +180,7 @@ class MADE(nn.Module):
                 for k in ("order", "off"):
                     plan[k] = [torch.from_numpy(a).to(dev) for a in plan[k]]
                 plan["var_of_step"] = torch.from_numpy(plan["var_of_step"]).to(dev)
+                plan["cond_in"] = cond_in
             cache = self._prefix_cache = (self.m, key, plan)
         return cache[2]
 
@@ -224,9 +233,11 @@ class AutoregressiveConditioner(Conditioner):
         return self.in_size - 1
 
     # -- column-by-column inversion (NormalizingFlowStep._invert_by_columns) ---------------------------------------------
-    def prefix_plan(self):
+    def prefix_plan(self, with_context=False):
         get = getattr(self.masked_autoregressive_net, "prefix_plan", None)
-        return get() if get is not None else None
+        if get is None:
+            return None
+        return get(with_context=True) if with_context else get()
 
     _held_prefix = None
 
@@ -240,7 +251,7 @@ class AutoregressiveConditioner(Conditioner):
         @contextlib.contextmanager
         def hold():
             prev = self._held_prefix
-            plan = self.prefix_plan()
+            plan = self.prefix_plan(with_context=bool(self.cond_in))
             if prev is None and plan is not None:
                 self._held_prefix = ops.made_prefix_pack(self._prefix_params(), plan)
             try:
@@ -250,10 +261,11 @@ class AutoregressiveConditioner(Conditioner):
         return hold()
 
     def prefix_workspace(self, batch):
-        return ops.made_prefix_workspace(self._prefix_params(), self.prefix_plan(), batch)
+        return ops.made_prefix_workspace(self._prefix_params(), self.prefix_plan(with_context=bool(self.cond_in)), batch)
 
-    def prefix_steps(self, z, x, t0, t1, mode, h_out=None, ws=None):
-        """steps t0 <= t < t1 of the plan on the HIP prefix kernel (gnf_hip.ops.made_prefix_steps)"""
-        plan, params = self.prefix_plan(), self._prefix_params()
+    def prefix_steps(self, z, x, t0, t1, mode, h_out=None, ws=None, context=None):
+        """steps t0 <= t < t1 of the plan on the HIP prefix kernel (gnf_hip.ops.made_prefix_steps); `context`: the checked
+        [B, cond_in] context of a conditional conditioner (the plan is then prefix_plan(with_context=True))"""
+        plan, params = self.prefix_plan(with_context=bool(self.cond_in)), self._prefix_params()
         pack = self._held_prefix if self._held_prefix is not None else ops.made_prefix_pack(params, plan)
-        return ops.made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=h_out, ws=ws)
+        return ops.made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=h_out, ws=ws, context=context)

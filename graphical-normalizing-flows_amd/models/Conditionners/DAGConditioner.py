@@ -586,20 +586,23 @@ class DAGConditioner(Conditioner):
             return self.soft_thresholded_A()
         return self.A
 
-    def forward_rows(self, x, rows, P, host_rows=None, variable_major=False, rows32=None):
+    def forward_rows(self, x, rows, P, host_rows=None, variable_major=False, rows32=None, context=None):
         """h[:, rows, :] only: the conditioner output of row i depends on x through x * P[i] alone, so a
         level-scheduled inversion evaluates each row exactly once.  variable_major: the result as
         [R, B, out] (any strides) instead of [B, R, out] -- the sparse kernels produce that layout, and the level loop
         of the inversion consumes it without a permuting copy.  rows32: `rows` as int32 on the device, for a caller that
-        keeps such a table (the row-subset front of CIFAR10CNN reads it)."""
+        keeps such a table (the row-subset front of CIFAR10CNN reads it).  context (cond_in > 0): the checked [B, cond_in]
+        context; the sparse plan and the fused rows front build the copies inside the first layer and know no context
+        columns, so the R masked copies per sample go to memory and the DAGMLP completes row b*R + i with context[b]."""
         B, R = x.shape[0], rows.numel()
-        plan = self._sparse_plan(x, rows.tolist() if host_rows is None else host_rows, P)
-        if plan is not None:
-            return self.embedding_net.sparse_rows(x, P, plan, variable_major=variable_major)
-        if self._rows_front(x, P):
-            return self._net_rows(x, P, rows.to(torch.int32) if rows32 is None else rows32, variable_major)
+        if context is None:
+            plan = self._sparse_plan(x, rows.tolist() if host_rows is None else host_rows, P)
+            if plan is not None:
+                return self.embedding_net.sparse_rows(x, P, plan, variable_major=variable_major)
+            if self._rows_front(x, P):
+                return self._net_rows(x, P, rows.to(torch.int32) if rows32 is None else rows32, variable_major)
         if variable_major:
-            return self.forward_rows(x, rows, P, host_rows).permute(1, 0, 2)
+            return self.forward_rows(x, rows, P, host_rows, context=context).permute(1, 0, 2)
         if hasattr(self.embedding_net, "exact_pool_ties"):
             self.embedding_net.exact_pool_ties = True                    # deterministic gate by construction
         e = x.unsqueeze(1) * P[rows].unsqueeze(0)                        # [B, R, d]
@@ -607,7 +610,9 @@ class DAGConditioner(Conditioner):
             hot = torch.zeros(R, self.in_size, device=x.device, dtype=x.dtype)
             hot[torch.arange(R, device=x.device), rows] = 1.
             e = torch.cat((e, hot.unsqueeze(0).expand(B, -1, -1)), 2)
-        return self.embedding_net(e.reshape(B * R, -1)).view(B, R, -1)
+        e = e.reshape(B * R, e.shape[2])
+        h = self.embedding_net(e) if context is None else self.embedding_net(e, context, R)
+        return h.view(B, R, h.shape[-1])
 
     def step(self, epoch_number, loss_avg=0.):
         """Once per epoch (:273-293): exponent back-off and dual update schedule."""

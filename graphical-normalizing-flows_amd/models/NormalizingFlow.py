@@ -14,6 +14,7 @@ import torch.nn as nn
 
 from gnf_hip import ops
 from .Conditionners import Conditioner, DAGConditioner
+from .Conditionners.Conditioner import checked_context
 from .Normalizers import Normalizer, AffineNormalizer
 
 
@@ -132,14 +133,15 @@ class NormalizingFlowStep(NormalizingFlow):
         x = torch.zeros_like(z)
         zt = z.t()[self._levels_all]                    # [sum R, B], contiguous
         off = 0
-        into = getattr(self.normalizer, "inverse_transform_into", None) if context is None else None
+        into = getattr(self.normalizer, "inverse_transform_into", None)       # (the normalizers ignore the context)
         rows32 = getattr(self, "_levels_rows32", None)
         if into is not None and (rows32 is None or len(rows32) != len(levels)):
             into = None
         for k, (rows, host_rows) in enumerate(levels):
             R = rows.numel()
             h = cond.forward_rows(x, rows, importance, host_rows, variable_major=True,
-                                  rows32=rows32[k] if rows32 is not None and len(rows32) == len(levels) else None)
+                                  rows32=rows32[k] if rows32 is not None and len(rows32) == len(levels) else None,
+                                  **({} if context is None else {"context": context}))
             # the normalizer writes its [R, B] result into columns `rows` of x itself where it can
             if into is None or not into(zt[off:off + R], h, x, rows32[k]):
                 x[:, rows] = self.normalizer.inverse_transform(zt[off:off + R], h, context).t()
@@ -164,24 +166,36 @@ class NormalizingFlowStep(NormalizingFlow):
         conditioner rows in total instead of (depth + 1) * d.  Same values as the fixed-point passes (non-parents are
         masked by exact zeros either way).  Returns None when not applicable.
 
+        A conditioner built with cond_in > 0 takes its (checked) context along: every level's rows are completed with
+        context[b] by the DAGMLP, on the composed formulation, launch by launch (no graph is captured for such a pass).
+
         On the GPU the pass of a given (gate, batch shape, node count) is captured into a hipGraph the second time it is
         asked for and replayed from then on (`graph_invert`): with a frozen A the schedule, the row tables and the sparse
         plans are static, and a sampling pass over MNIST is ~650 launches of 5-100 us (reference ImageExperiments.py:341-350
         samples after post_process()).  The weight image of the normalizer is packed INSIDE the graph, so a replay reads
         the current parameters."""
         cond = self.conditioner
-        if not (_is_dag(cond) and context is None and self.level_schedule):
+        if not (_is_dag(cond) and self.level_schedule):
             return None
+        cond_in = int(getattr(cond, "cond_in", 0) or 0)
+        if not cond_in and context is not None:
+            return None                                 # the passes raise what a cond_in = 0 conditioner raises
+        if cond_in:
+            context = checked_context(context, cond_in, z)              # ValueError: missing, wrong width / rank / rows
+            if z.dim() != 2 or context.device != z.device or context.dtype != z.dtype:
+                return None
         importance = cond.deterministic_importance()
         if importance is None:
             return None
         levels, lkey = self._levels(importance)
         if levels is None:
             return None
+        if cond_in and z.shape[0] == 0:
+            return torch.zeros_like(z)                  # no rows, no launch (as the column schedule answers an empty batch)
         # a captured pass bakes the ADDRESS of the importance matrix in: only A itself qualifies -- the thresholded forms
         # (s_thresh / h_thresh > 0, the state the reference's threshold sweep sets) are temporaries freed after this call
-        graphable = (self.graph_invert and z.is_cuda and not cond.A.requires_grad and z.dtype == torch.float32
-                     and importance.data_ptr() == cond.A.data_ptr()
+        graphable = (self.graph_invert and context is None and z.is_cuda and not cond.A.requires_grad
+                     and z.dtype == torch.float32 and importance.data_ptr() == cond.A.data_ptr()
                      and len(levels) > 4 and not torch.cuda.is_current_stream_capturing())
         if not graphable:
             return self._invert_levels_body(z, levels, importance, context)
@@ -250,24 +264,37 @@ class NormalizingFlowStep(NormalizingFlow):
         """MADE conditioner: the variables are inverted in degree order, one per step, and a step evaluates only the hidden
         units that became final with the previous column (AutoregressiveConditioner.prefix_plan) -- about half of ONE masked
         forward and ONE normalizer inverse in total, where the passes below spend depth() + 1 = d of each.  The same function
-        in another fp32 summation order.  Returns None when not applicable."""
+        in another fp32 summation order.  Returns None when not applicable.
+
+        A conditional MADE (cond_in > 0) is inverted the same way from its conditional plan (prefix_plan(with_context=True)):
+        the checked context heads the kernel's activation rows, the conditioner module is never called."""
         cond = self.conditioner
         get_plan = getattr(cond, "prefix_plan", None)
-        if not (self.column_schedule and context is None and get_plan is not None and z.is_cuda and z.dim() == 2
+        if not (self.column_schedule and get_plan is not None and z.is_cuda and z.dim() == 2
                 and z.dtype == torch.float32):
             return None
+        cond_in = int(getattr(cond, "cond_in", 0) or 0)
+        if not cond_in and context is not None:
+            return None                                 # the passes raise what a cond_in = 0 conditioner raises
+        if cond_in:
+            context = checked_context(context, cond_in, z)              # ValueError: missing, wrong width / rank / rows
+            if context.device != z.device or context.dtype != torch.float32:
+                return None
         if z.shape[0] == 0:
             # no rows, no launch: the empty result (the passes would stop at the MADE's `.view(0, -1, d)` as the reference's do)
             return torch.zeros_like(z)
-        plan = get_plan()
+        plan = get_plan(with_context=True) if cond_in else get_plan()
         if plan is None or plan["d"] != z.shape[1]:
             return None
+        if cond_in:
+            context = context.contiguous()
         z = z.contiguous()
         x = torch.zeros_like(z)
         B, d, out = z.shape[0], plan["d"], plan["out"]
         with cond.hold_prefix_pack():
             if type(self.normalizer) is AffineNormalizer:
-                cond.prefix_steps(z, x, 0, d, ops.MADE_NORM_AFFINE)          # the whole inversion, one launch
+                # the whole inversion, one launch
+                cond.prefix_steps(z, x, 0, d, ops.MADE_NORM_AFFINE, **({"context": context} if cond_in else {}))
                 return x
             h = torch.empty(B, out, dtype=torch.float32, device=z.device)
             ws = cond.prefix_workspace(B)
@@ -276,7 +303,8 @@ class NormalizingFlowStep(NormalizingFlow):
             into = getattr(self.normalizer, "inverse_transform_into", None)
             for t in range(d):
                 v = plan["var_host"][t]
-                cond.prefix_steps(z, x, t, t + 1, ops.MADE_NORM_NONE, h_out=h, ws=ws)
+                cond.prefix_steps(z, x, t, t + 1, ops.MADE_NORM_NONE, h_out=h, ws=ws,
+                                  **({"context": context} if cond_in else {}))
                 # the normalizer's own inverse of that one column; the fused Monotonic kernel writes x[:, v] itself
                 if into is None or not into(zt[v:v + 1], h.view(1, B, out), x, cols[v:v + 1]):
                     x[:, v:v + 1] = self.normalizer.inverse_transform(z[:, v:v + 1], h.view(B, 1, out), context)

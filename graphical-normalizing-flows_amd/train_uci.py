@@ -9,6 +9,8 @@ Opt-in: `-device_batches` gathers the training batches on the device through a P
 `-threshold_sweep` adds the reference's validation at five hard thresholds every 10th epoch (:183-212).
 `-context_cols K` trains a CONDITIONAL flow p(first d - K columns | last K columns): the model is built with cond_in = K
 and every batch is split into (x, context) -- behind the gather when the batches come from the device.
+`-sample N` (after the last evaluation) draws N samples x ~ p(x | context of the first N test rows) through model.invert into
+`samples.npy` in -folder and prints the mean |z - forward(x, ctx)| (sample_rows).
 
 Checkpoints: `model.pt` is `state_dict()` with the reference's keys, `ADAM.pt` is in torch.optim.Adam's format, so
 either side can resume the other's run."""
@@ -102,6 +104,28 @@ def mean_ll(model, X, b, gen, on_device=False, context_cols=0):
         tot += ll if on_device else ll.item()
         n += 1
     return float(tot) / max(n, 1)
+
+
+@torch.no_grad()
+def sample_rows(model, tst, n, context_cols, seed, folder, say=print):
+    """-sample N: x ~ p(x | c) for the contexts of the first N rows of the test split (their last context_cols columns;
+    an unconditional flow: x ~ p(x)), z ~ N(0, I) from a torch.Generator seeded by `seed`, through model.invert.  Writes
+    samples.npy into `folder`: [N, modelled columns + context columns], in the normalisation of the data.  Returns and
+    reports the mean |z - forward(x, ctx)[0]|, as the reference's image script does for its samples
+    (ImageExperiments.py:341-350)."""
+    import numpy as np
+    rows = tst[:n]
+    _, ctx = split_context(rows, context_cols)
+    d = rows.shape[1] - context_cols
+    z = torch.randn(rows.shape[0], d, generator=torch.Generator().manual_seed(int(seed))).to(rows.device)
+    x = model.invert(z) if ctx is None else model.invert(z, ctx)
+    zz = (model(x) if ctx is None else model(x, ctx))[0]
+    err = float((z - zz).abs().mean()) if z.numel() else 0.
+    out = x if ctx is None else torch.cat((x, ctx), 1)
+    os.makedirs(folder, exist_ok=True)
+    np.save(os.path.join(folder, "samples.npy"), out.cpu().numpy())
+    say("samples: %d rows -> %s - mean |z - forward(x)|: %.3e" % (out.shape[0], os.path.join(folder, "samples.npy"), err))
+    return err
 
 
 THRESHOLDS = (.95, .5, .1, .01, .0001)
@@ -263,6 +287,8 @@ def train(args):
             torch.save(model.state_dict(), os.path.join(args.folder, "model.pt"))
             torch.save(state.optimizer_state_dict(model, args.learning_rate, args.weight_decay),
                        os.path.join(args.folder, "ADAM.pt"))
+    if getattr(args, "sample", 0) > 0 and rank == 0:
+        sample_rows(model, tst, args.sample, ctx_cols, args.seed, args.folder, say)
     if world > 1:
         dist.destroy_process_group()
     return model
@@ -317,6 +343,8 @@ def parse(argv=None):
                     help="DAG conditioners: validation at five hard thresholds every 10th epoch")
     ap.add_argument("-context_cols", default=0, type=int,
                     help="the last K columns of the data are the context of a conditional flow over the others (cond_in = K)")
+    ap.add_argument("-sample", default=0, type=int,
+                    help="after the last evaluation: N samples x ~ p(x | context of the first N test rows) into samples.npy")
     args = ap.parse_args(argv)
     if args.load_config is not None:                         # a named entry of the yml overrides the command line
         with open(args.config_file) as f:
@@ -327,6 +355,8 @@ def parse(argv=None):
         ap.error("-dataset (or a -load_config entry naming one) is required")
     if args.steps_per_replay < 1:
         ap.error("-steps_per_replay must be at least 1")
+    if args.sample < 0:
+        ap.error("-sample must not be negative")
     if args.context_cols < 0:
         ap.error("-context_cols must not be negative")
     if args.steps_per_replay > 1 and not args.device_batches:

@@ -354,7 +354,16 @@ const char* gnf_monotonic_bwd_kernel(void);
  *   z, x: [B, d] contiguous; columns of x of degree < t0 are read, the others written (AFFINE) or left alone (NONE).
  *   ws: >= gnf_made_prefix_ws_bytes(net, B) bytes carrying the activations from one call to the next (the SAME buffer for
  *     every call of one inversion, steps in ascending order from 0); may be NULL for (0, d) calls whose tile fits in LDS,
- *     GNF_EWS tells otherwise.  Values are those of the passes up to fp32 summation order. */
+ *     GNF_EWS tells otherwise.  Values are those of the passes up to fp32 summation order.
+ *   Conditional MADE (ConditionnalMADE, cond_in = c > 0): the gnf_made_prefix_ctx_* entry points take the same descriptor
+ *     with W[0] as [rows, c + d] -- the c context columns in FRONT of the variables, input degree -1, so every unit of the
+ *     first layer reads them from step 0 on -- and context [B, c] contiguous (dword-aligned rows, nothing more is assumed).
+ *     The activation row becomes [context | x in degree order | hidden 0 | ...], the first layer's prefix at step t is
+ *     K = c + t, and pack / ws grow accordingly (first-layer pitch round_up(c + d, 16); ws = 4 B ((c + d + sum width) | 1)
+ *     bytes).  Without hidden layers the outputs of the degree-0 variable read the context (K = c at step 0); with hidden
+ *     layers they stay the output bias.  The context is read by the launch that runs step 0 (and by a whole inversion held
+ *     in LDS); later step launches find it in ws.  cond_in > 2^26: GNF_ESHAPE.  cond_in < 0, or cond_in > 0 with context == NULL and rows to compute:
+ *     GNF_EINVAL.  The four entry points without _ctx ARE the cond_in = 0 calls of these (same bits). */
 #define GNF_MADE_MAX_HIDDEN 8
 #define GNF_MADE_NORM_NONE 0
 #define GNF_MADE_NORM_AFFINE 1
@@ -374,6 +383,12 @@ int gnf_made_prefix_pack(const gnf_made_net* net, float* pack, gnf_stream_t stre
 int64_t gnf_made_prefix_ws_bytes(const gnf_made_net* net, int64_t B);
 int gnf_made_prefix(const gnf_made_net* net, const float* pack, const float* z, float* x, float* h_out, int t0, int t1,
                     int normalizer_mode, int64_t B, void* ws, int64_t ws_bytes, gnf_stream_t stream);
+int64_t gnf_made_prefix_ctx_pack_floats(const gnf_made_net* net, int cond_in);
+int gnf_made_prefix_ctx_pack(const gnf_made_net* net, int cond_in, float* pack, gnf_stream_t stream);
+int64_t gnf_made_prefix_ctx_ws_bytes(const gnf_made_net* net, int cond_in, int64_t B);
+int gnf_made_prefix_ctx(const gnf_made_net* net, int cond_in, const float* context, const float* pack, const float* z,
+                        float* x, float* h_out, int t0, int t1, int normalizer_mode, int64_t B, void* ws, int64_t ws_bytes,
+                        gnf_stream_t stream);
 
 /* ---- MNISTCNN convolutional front: models/MLP.py:36-41 as the DAG embedding net --------
  * (ImageExperiments / NormalizingFlowFactories.py:83-86: size_img = [1,28,28]).
