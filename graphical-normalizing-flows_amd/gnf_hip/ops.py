@@ -272,6 +272,80 @@ def made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=None, ws=Non
     return x
 
 
+# ----------------------------------------------------------------------------- MADE adjoint sweep, rsample
+@torch.no_grad()
+def made_adjoint_pack(params, plan):
+    """the adjoint kernel's weight image: the prefix image followed by every layer transposed (gnf_made_adjoint_pack);
+    parameter-only, one launch (AutoregressiveConditioner.hold_adjoint_pack builds it once for several solves)"""
+    params = [p.detach() for p in params]
+    net, c = _made_net(params, plan), _plan_cond_in(plan)
+    nfl = abi.load().gnf_made_adjoint_pack_floats(ctypes.byref(net), c)
+    if nfl < 0:
+        abi.check(int(nfl), "gnf_made_adjoint_pack_floats")
+    pack = _empty((int(nfl),), params[0])
+    call("gnf_made_adjoint_pack", ctypes.byref(net), c, ptr(pack), stream())
+    return pack
+
+
+@torch.no_grad()
+def made_adjoint(params, plan, pack, x, g, jac, dzdh, context=None, force_ws=False):
+    """lambda [B, d] with J^T lambda = g for the MADE step whose sample is x (gnf_made_adjoint, one launch): x, g, jac
+    [B, d] and dzdh [B, d, out] fp32 contiguous, jac the normalizer's own derivative dz_i/dx_i, dzdh[b, i, :] = dz_bi/dh_bi;
+    context: the contiguous [B, cond_in] tensor of a conditional plan.  force_ws (tests): keep the tile's rows in the
+    workspace even when they fit in LDS -- the same bits."""
+    params = [p.detach() for p in params]
+    net, c = _made_net(params, plan), _plan_cond_in(plan)
+    B, d = x.shape
+    ok = lambda t, shape: (t.is_cuda and t.device == x.device and t.dtype == torch.float32 and tuple(t.shape) == shape
+                           and t.is_contiguous())
+    if d != plan["d"] or not (ok(x, (B, d)) and ok(g, (B, d)) and ok(jac, (B, d)) and ok(dzdh, (B, d, plan["out"]))):
+        raise abi.GnfError("made_adjoint: x, g, jac [B, %d] and dzdh [B, %d, %d] must be contiguous fp32 device tensors"
+                           % (plan["d"], plan["d"], plan["out"]))
+    if (context is not None) != (c > 0) or (c > 0 and not ok(context, (B, c))):
+        raise abi.GnfError("made_adjoint: context must be a contiguous fp32 [B, %d] tensor on the device of x (None for "
+                           "cond_in = 0)" % c)
+    lam = torch.empty_like(x)
+    args = lambda w: (ctypes.byref(net), c, ptr(context), ptr(pack), ptr(x), ptr(g), ptr(jac), ptr(dzdh), ptr(lam), B,
+                      int(bool(force_ws)), None if w is None else ctypes.c_void_p(w.data_ptr()),
+                      0 if w is None else w.numel() * 4, stream())
+    if not force_ws:
+        # a tile whose rows fit in LDS needs no workspace; the library says when it does not
+        rc = abi.load().gnf_made_adjoint(*args(None))
+        if rc == 0:
+            return lam
+        if rc != -3:
+            abi.check(rc, "gnf_made_adjoint")
+    nbytes = abi.load().gnf_made_adjoint_ws_bytes(ctypes.byref(net), c, B)
+    if nbytes < 0:
+        abi.check(int(nbytes), "gnf_made_adjoint_ws_bytes")
+    call("gnf_made_adjoint", *args(_ws(nbytes, x)))
+    return lam
+
+
+class InvertFn(torch.autograd.Function):
+    """x = step^-1(z; theta, context) with the gradient of the implicit function theorem (NormalizingFlowStep.rsample).
+    Forward: step.invert, the same kernels and bits.  Backward, for a cotangent g = dL/dx: lambda solves J^T lambda = g
+    with J = dz/dx of the step at the sample; dL/dz = lambda, and dL/dtheta, dL/dcontext are ONE vjp of the step's forward
+    at x (detached) with cotangent -lambda.  `params` are the step's parameters, passed as inputs so that the gradients
+    reach them (as MonotonicFn takes the integrand's)."""
+
+    @staticmethod
+    def forward(ctx, step, z, context, *params):
+        x = step.invert(z, context)
+        ctx.step = step
+        ctx.has_context = context is not None
+        ctx.save_for_backward(x, *(() if context is None else (context,)), *params)
+        return x
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, *rest = ctx.saved_tensors                    # (raises when a parameter was modified in place since the sample)
+        context = rest.pop(0) if ctx.has_context else None
+        lam, gctx, gparams = ctx.step._rsample_backward(x, context, rest, g.contiguous(), ctx.needs_input_grad[2])
+        return (None, lam, gctx, *gparams)
+
+
 # ----------------------------------------------------------------------------- row reductions
 class LogSumRowsFn(torch.autograd.Function):
     """torch.log(jac).sum(1)   (models/NormalizingFlow.py:70)."""

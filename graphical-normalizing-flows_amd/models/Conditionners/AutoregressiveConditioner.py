@@ -269,3 +269,31 @@ class AutoregressiveConditioner(Conditioner):
         plan, params = self.prefix_plan(with_context=bool(self.cond_in)), self._prefix_params()
         pack = self._held_prefix if self._held_prefix is not None else ops.made_prefix_pack(params, plan)
         return ops.made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=h_out, ws=ws, context=context)
+
+    # -- the adjoint of that sweep (NormalizingFlowStep.rsample's backward) -------------------------------------------------
+    _held_adjoint = None
+
+    def hold_adjoint_pack(self):
+        """context manager: the adjoint kernel's weight image (the prefix image and every layer transposed), built once for
+        the adjoint_solve calls inside"""
+        import contextlib
+
+        @contextlib.contextmanager
+        def hold():
+            prev = self._held_adjoint
+            plan = self.prefix_plan(with_context=bool(self.cond_in))
+            if prev is None and plan is not None:
+                self._held_adjoint = ops.made_adjoint_pack(self._prefix_params(), plan)
+            try:
+                yield
+            finally:
+                self._held_adjoint = prev
+        return hold()
+
+    def adjoint_solve(self, x, g, jac, dzdh, context=None):
+        """lambda [B, d] with J^T lambda = g for the step whose sample is x, on the HIP adjoint kernel (gnf_hip.ops.made_adjoint,
+        one launch): jac [B, d] the normalizer's dz_i/dx_i, dzdh [B, d, out] its dz_i/dh_i; `context`: the checked
+        [B, cond_in] context of a conditional conditioner"""
+        plan, params = self.prefix_plan(with_context=bool(self.cond_in)), self._prefix_params()
+        pack = self._held_adjoint if self._held_adjoint is not None else ops.made_adjoint_pack(params, plan)
+        return ops.made_adjoint(params, plan, pack, x, g, jac, dzdh, context=context)

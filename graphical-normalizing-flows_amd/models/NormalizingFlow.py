@@ -41,6 +41,10 @@ class NormalizingFlow(nn.Module):
     def invert(self, z, context=None):
         raise NotImplementedError
 
+    def rsample(self, z, context=None):
+        """invert(z, context) as a differentiable function of z, the context and the parameters"""
+        raise NotImplementedError
+
     def getConditioners(self):
         raise NotImplementedError
 
@@ -79,6 +83,7 @@ class NormalizingFlowStep(NormalizingFlow):
         self.level_schedule = True       # invert(): topological level schedule for DAG conditioners
         self.graph_invert = True         # ... replayed as a hipGraph from the second pass of a shape on (frozen A, GPU)
         self.column_schedule = True      # invert(): one column per step for MADE conditioners, every hidden unit once
+        self.adjoint_schedule = True     # rsample() backward: the transposed column sweep for MADE conditioners, one launch
 
     def getConditioners(self):
         return [self.conditioner]
@@ -330,6 +335,77 @@ class NormalizingFlowStep(NormalizingFlow):
                     break
         return x
 
+    # -- differentiable sampling --------------------------------------------------------------------------------
+    def rsample(self, z, context=None):
+        """x = invert(z, context) -- the same kernels, the same bits -- with gradients for z, the context and the step's
+        parameters from the implicit function theorem (rsample).  With J = dz/dx of the step at the sample and
+        a cotangent g = dL/dx:  J^T lambda = g,  dL/dz = lambda,  dL/dtheta = -(dS/dtheta)^T lambda, dL/dc likewise: one
+        transposed triangular solve and one vjp of the forward, instead of a backward through depth() + 1 passes.
+
+        A DAG conditioner with a stochastic or noisy gate is refused: the backward re-evaluates the conditioner at the
+        sample, and would draw another gate than the one the sample saw."""
+        cond = self.conditioner
+        if _is_dag(cond) and cond.deterministic_importance() is None:
+            raise ValueError("NormalizingFlowStep.rsample: the DAG conditioner's gate is stochastic (stoch_gate / noise_gate); "
+                             "the backward would recompute the conditioner under another draw of the gate than the sample "
+                             "saw.  Use a deterministic gate (stoch_gate = noise_gate = False)")
+        return ops.InvertFn.apply(self, z, context, *[p for p in self.parameters() if p.requires_grad])
+
+    def _adjoint_plan(self, x, context):
+        """the MADE plan of the adjoint arm when _invert_by_columns would be taken for this sample (and `adjoint_schedule`),
+        else None: the passes arm"""
+        cond = self.conditioner
+        get_plan = getattr(cond, "prefix_plan", None)
+        if not (self.adjoint_schedule and self.column_schedule and get_plan is not None
+                and getattr(cond, "adjoint_solve", None) is not None and x.is_cuda and x.dim() == 2
+                and x.dtype == torch.float32):
+            return None
+        cond_in = int(getattr(cond, "cond_in", 0) or 0)
+        if bool(cond_in) != (context is not None):
+            return None
+        if cond_in and (context.device != x.device or context.dtype != torch.float32):
+            return None
+        plan = get_plan(with_context=True) if cond_in else get_plan()
+        return plan if plan is not None and plan["d"] == x.shape[1] else None
+
+    def _rsample_backward(self, x, context, params, g, want_context):
+        """(lambda, dL/dcontext, [dL/dp for p in params]) of ops.InvertFn for the sample x and the cotangent g = dL/dx"""
+        self._rsample_arm = None                        # which arm the last backward took, and its vjps through the step
+        if x.shape[0] == 0:
+            return torch.zeros_like(x), None, [None] * len(params)
+        want_context = bool(want_context and context is not None)
+        with torch.enable_grad():
+            # two leaves of the same values: grad(z, xa) is N^T lambda alone (the conditioner's path), the diagonal of J is
+            # the normalizer's own jac -- no J^T lambda - D lambda cancellation
+            xa, xb = x.detach().requires_grad_(True), x.detach()
+            ctx = context.detach().requires_grad_(True) if want_context else context
+            h = self.conditioner(xa, ctx)
+            zz, jac = self.normalizer(xb, h, ctx)
+        jac = jac.detach()
+        plan = self._adjoint_plan(x, context)
+        if plan is not None:
+            # the normalizers are element-wise: one backward with a cotangent of ones is dz_bi/dh_bi
+            dzdh, = torch.autograd.grad(zz, h, torch.ones_like(zz), retain_graph=True)
+            lam = self.conditioner.adjoint_solve(x.contiguous(), g, jac.contiguous(), dzdh.contiguous(),
+                                                 **({} if context is None else {"context": context.detach().contiguous()}))
+            self._rsample_arm = ("adjoint", 0)
+        else:
+            # exact by nilpotency: N^(depth + 1) = 0
+            lam, n = g / jac, 0
+            for _ in range(self.conditioner.depth()):
+                nl, = torch.autograd.grad(zz, xa, lam, retain_graph=True, allow_unused=True)
+                n += 1
+                new = g / jac if nl is None else (g - nl) / jac
+                same = torch.equal(new, lam)
+                lam = new
+                if same:
+                    break
+            self._rsample_arm = ("passes", n)
+        wrt = list(params) + ([ctx] if want_context else [])
+        grads = list(torch.autograd.grad(zz, wrt, -lam, allow_unused=True)) if wrt else []
+        gctx = grads.pop() if want_context else None
+        return lam, gctx, grads
+
 
 class FCNormalizingFlow(NormalizingFlow):
     """Steps applied in sequence on flat [B, d] data."""
@@ -385,6 +461,13 @@ class FCNormalizingFlow(NormalizingFlow):
         identical to it."""
         for k in range(len(self.steps) - 1, -1, -1):
             x = self.steps[k].invert(z, context)
+            z = torch.flip(x, dims=[1]) if k else x
+        return z
+
+    def rsample(self, z, context=None):
+        """invert(z, context), differentiable in z, the context and the parameters: the steps' rsample, last to first"""
+        for k in range(len(self.steps) - 1, -1, -1):
+            x = self.steps[k].rsample(z, context)
             z = torch.flip(x, dims=[1]) if k else x
         return z
 
@@ -446,3 +529,7 @@ class CNNormalizingFlow(FCNormalizingFlow):
                 zk = blocks.view(batch, c, h, w, *drop).permute(0, 1, 4, 2, 5, 3, 6).reshape(batch, -1)
             x = flow.invert(zk.reshape(batch, -1), context)
         return x
+
+    def rsample(self, z, context=None):
+        raise NotImplementedError("CNNormalizingFlow.rsample: differentiable sampling of the multi-scale image flow is not "
+                                  "implemented (the flat FCNormalizingFlow.rsample does not apply to it)")

@@ -390,6 +390,35 @@ int gnf_made_prefix_ctx(const gnf_made_net* net, int cond_in, const float* conte
                         float* x, float* h_out, int t0, int t1, int normalizer_mode, int64_t B, void* ws, int64_t ws_bytes,
                         gnf_stream_t stream);
 
+/* ---- MADE adjoint sweep: lambda with J^T lambda = g for one MADE step (NormalizingFlowStep.rsample's backward) ----------
+ * The step is z = S(x; context): h = MADE(context, x), z[b, i] = normalizer(x[b, i], h[b, i, :]).  In degree order
+ * J = dz/dx = diag(jac) + N with N strictly lower triangular, so J^T lambda = g is solved from the last degree down:
+ *   lambda_t = (g[b, v] - u_t) / jac[b, v],  v = var_of_step[t],
+ *   u_t = the cotangent that reaches x[b, v] through the MADE when the outputs of every later variable v' = var_of_step[t'],
+ *         t' > t, carry the cotangent lambda_t' * dzdh[b, v', :].
+ * One launch does the whole solve: it first replays the hidden units from x with the arithmetic (and the tile height) of
+ * gnf_made_prefix, keeping the ReLU decisions act > 0 -- those of the column sweep that produced x -- and then walks
+ * t = d-1 .. 0, finalising per step the cotangents of the hidden units of degree t (suffix contractions of the transposed
+ * weights, the mirror image of the prefix contractions) and u_t.
+ *   net, cond_in: as for gnf_made_prefix_ctx (the masks are NOT read: the caller guarantees the degree rule).
+ *   pack: >= gnf_made_adjoint_pack_floats(net, cond_in) floats, 16-byte aligned, written by gnf_made_adjoint_pack: the
+ *     image of gnf_made_prefix_ctx_pack followed by every layer TRANSPOSED (rows = the units of the layer below in degree
+ *     order, pitch = out_features rounded up to 16, the tail zero).  Parameter-only, valid until a parameter or the ordering
+ *     changes.
+ *   x, g, jac, lambda: [B, d] contiguous; context: [B, cond_in] contiguous (NULL for cond_in = 0); dzdh: [B, d, out]
+ *     contiguous, dzdh[b, i, k] = dz[b, i] / dh[b, i, k] (the normalizers are element-wise, so one normalizer backward with
+ *     a cotangent of ones yields it whatever the normalizer).  All dword-aligned, nothing more is assumed.  jac != 0.
+ *   ws: >= gnf_made_adjoint_ws_bytes(net, cond_in, B) bytes; may be NULL when the tile's rows fit in LDS (160 KB), GNF_EWS
+ *     tells otherwise.  force_ws != 0 keeps the rows in ws even when they would fit: the same code on another pointer, the
+ *     same bits (a test hook).
+ *   fp32 with a fixed summation order for a given (net, cond_in, B); rows never interact.  B = 0 launches nothing. */
+int64_t gnf_made_adjoint_pack_floats(const gnf_made_net* net, int cond_in);
+int gnf_made_adjoint_pack(const gnf_made_net* net, int cond_in, float* pack, gnf_stream_t stream);
+int64_t gnf_made_adjoint_ws_bytes(const gnf_made_net* net, int cond_in, int64_t B);
+int gnf_made_adjoint(const gnf_made_net* net, int cond_in, const float* context, const float* pack, const float* x,
+                     const float* g, const float* jac, const float* dzdh, float* lambda, int64_t B, int force_ws, void* ws,
+                     int64_t ws_bytes, gnf_stream_t stream);
+
 /* ---- MNISTCNN convolutional front: models/MLP.py:36-41 as the DAG embedding net --------
  * (ImageExperiments / NormalizingFlowFactories.py:83-86: size_img = [1,28,28]).
  * e: [n_img, 784] masked images; W1 [16,1,3,3], b1 [16], W2 [16,16,3,3], b2 [16].
