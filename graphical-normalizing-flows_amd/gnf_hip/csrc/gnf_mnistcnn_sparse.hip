@@ -92,6 +92,9 @@ __global__ void sparse_bg_k(const float* __restrict__ b1, const float* __restric
   // every workgroup recomputes the 16 background values (2304 fma) and reduces 4 rows of Wfc1
   const int lane = threadIdx.x & 63, nw = blockDim.x >> 6, wave = blockIdx.x * nw + (threadIdx.x >> 6);
   if (!hbg) return;
+  // the 64 floats of slack that close the tables (gnf_mnistcnn_sparse_prep_bytes): zeros, so that the buffer a caller holds
+  // (ops.mnistcnn_sparse_prepare returns it) is defined to its last word
+  if (blockIdx.x == 0 && threadIdx.x < 64) hbg[F + threadIdx.x] = 0.f;
   for (int n = wave; n < F; n += nw * gridDim.x) {
     float s = 0.f;
     for (int k = lane; k < NCH * 144; k += 64) s = fmaf(Wfc1[(int64_t)n * (NCH * 144) + k], sbg[k / 144], s);

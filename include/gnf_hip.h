@@ -649,7 +649,8 @@ int gnf_mnistcnn_sparse_fwd_train(const float* x, int64_t B, const float* P, con
  * of each crop origin, conv2's response to the all-zero image and fc1 of that background -- are built once by
  * gnf_mnistcnn_sparse_prepare into `prep` (>= gnf_mnistcnn_sparse_prep_bytes(F) bytes) and read by every
  * gnf_mnistcnn_sparse_fwd_prepared call (inference only: nothing is saved for a backward; ws >= R*B*400*4 bytes).
- * Same h1 as gnf_mnistcnn_sparse_fwd, bit for bit. */
+ * Same h1 as gnf_mnistcnn_sparse_fwd, bit for bit.  The last 64 floats of the tables are slack no kernel reads; they are
+ * written as zeros, so the buffer is defined to its end. */
 int64_t gnf_mnistcnn_sparse_prep_bytes(int64_t F);
 int gnf_mnistcnn_sparse_prepare(const float* b1, const float* W2, const float* b2, const float* Wfc1, const float* bfc1,
                                 int64_t F, void* prep, int64_t prep_bytes, gnf_stream_t stream);
