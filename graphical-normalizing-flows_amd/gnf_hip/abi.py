@@ -22,6 +22,8 @@ c_stream = ctypes.c_void_p
 MONO_MAX_LAYERS = 8
 MADE_MAX_HIDDEN = 8       # GNF_MADE_MAX_HIDDEN
 MADE_NORM_NONE, MADE_NORM_AFFINE = 0, 1
+MADE_NORM_SPLINE = 2      # GNF_MADE_NORM_SPLINE: gnf_made_prefix_spline / gnf_made_prefix_ctx_spline only
+SPLINE_MIN_BINS, SPLINE_MAX_BINS = 2, 32
 DAG_PLAN_KC = 32          # GNF_DAG_PLAN_KC
 DAG_ELEM_F32, DAG_ELEM_U8 = 0, 1      # GNF_DAG_ELEM_*
 ABI_VERSION = 11          # GNF_ABI_VERSION of include/gnf_hip.h this binding was written against
@@ -48,6 +50,12 @@ SIGNATURES = {
     "gnf_affine_bwd": (c_int, [c_f, c_f, c_i64, c_i64, c_i64, c_f, c_f, c_f, c_f, c_f, c_f, c_i64, c_i64, c_i64, c_i64,
                                c_i64, c_stream]),
     "gnf_affine_inv": (c_int, [c_f, c_f, c_i64, c_i64, c_i64, c_f, c_i64, c_i64, c_stream]),
+    "gnf_spline_fwd": (c_int, [c_f, c_f, c_i64, c_i64, c_i64, c_i64, c_int, c_double, c_f, c_f, c_f, c_f, c_i64, c_i64,
+                               c_stream]),
+    "gnf_spline_bwd": (c_int, [c_f, c_f, c_i64, c_i64, c_i64, c_i64, c_int, c_double, c_f, c_f, c_f, c_f, c_f, c_f, c_i64,
+                               c_i64, c_i64, c_i64, c_i64, c_stream]),
+    "gnf_spline_inv": (c_int, [c_f, c_f, c_i64, c_i64, c_i64, c_i64, c_int, c_double, c_f, ctypes.c_void_p, c_i64, c_i64,
+                               c_i64, c_stream]),
     "gnf_logsum_rows_fwd": (c_int, [c_f, c_f, c_i64, c_i64, c_stream]),
     "gnf_logsum_rows_bwd": (c_int, [c_f, c_f, c_f, c_i64, c_i64, c_stream]),
     "gnf_normal_logdensity_fwd": (c_int, [c_f, c_f, c_i64, c_i64, c_stream]),
@@ -119,6 +127,10 @@ SIGNATURES = {
     "gnf_made_prefix_ctx_ws_bytes": (c_i64, [ctypes.POINTER(MadeNet), c_int, c_i64]),
     "gnf_made_prefix_ctx": (c_int, [ctypes.POINTER(MadeNet), c_int, c_f, c_f, c_f, c_f, c_f, c_int, c_int, c_int, c_i64,
                                     ctypes.c_void_p, c_i64, c_stream]),
+    "gnf_made_prefix_spline": (c_int, [ctypes.POINTER(MadeNet), c_f, c_f, c_f, c_f, c_int, c_int, c_int, c_int, c_double,
+                                       c_i64, ctypes.c_void_p, c_i64, c_stream]),
+    "gnf_made_prefix_ctx_spline": (c_int, [ctypes.POINTER(MadeNet), c_int, c_f, c_f, c_f, c_f, c_f, c_int, c_int, c_int,
+                                           c_int, c_double, c_i64, ctypes.c_void_p, c_i64, c_stream]),
     "gnf_made_adjoint_pack_floats": (c_i64, [ctypes.POINTER(MadeNet), c_int]),
     "gnf_made_adjoint_pack": (c_int, [ctypes.POINTER(MadeNet), c_int, c_f, c_stream]),
     "gnf_made_adjoint_ws_bytes": (c_i64, [ctypes.POINTER(MadeNet), c_int, c_i64]),

@@ -114,6 +114,8 @@ struct StepArgs {
   MadeLayout lay;
   const int32_t* off[kMaxH];
   const int32_t* var_of_step;
+  int spl_K = 0;                // GNF_MADE_NORM_SPLINE: bins and tail bound of the step's normalizer
+  double spl_T = 0.;
 };
 
 __device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f : v; }

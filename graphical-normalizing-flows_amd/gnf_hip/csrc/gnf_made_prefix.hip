@@ -25,6 +25,7 @@
 // context); with hidden layers those outputs read no hidden unit and stay the output bias.  c = 0 is the unconditional
 // kernel, instruction for instruction on the arithmetic path.
 #include "gnf_made.h"
+#include "gnf_spline.h"
 
 namespace {
 
@@ -33,6 +34,10 @@ __global__ void made_prefix_pack_k(PackArgs a, float* __restrict__ pack) {
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < a.lay.pack_floats; e += (int64_t)gridDim.x * blockDim.x)
     pack[e] = pack_elem(a, e);
 }
+
+// the spline epilogue of a row, kept OUT of line: inlined, its fp64 exponentials take made_prefix_k from 78 - 85 VGPRs to
+// 117 - 129 (a wavefront or two per SIMD less) and to nine dwords of scratch, on the Affine and NONE paths as well
+__device__ __noinline__ float spline_row_inverse(float* r, int K, double T, float z) { return spl_inverse<false>(r, K, T, z); }
 
 // ------------------------------------------------------------------------------------------------ the step kernel
 template <int TB, bool kLds>
@@ -64,7 +69,7 @@ __global__ __launch_bounds__(kThreads) void made_prefix_k(StepArgs s, const floa
   for (int t = t0; t < t1; ++t) {
     const int v = s.var_of_step[t];
     // the step's z is asked for before the layers, which hide its latency
-    const float zv = mode == GNF_MADE_NORM_AFFINE && tid < nrows ? z[(row0 + tid) * d + v] : 0.f;
+    const float zv = mode != GNF_MADE_NORM_NONE && tid < nrows ? z[(row0 + tid) * d + v] : 0.f;
     if (t >= 1)
       for (int l = 0; l < nh; ++l) {
         const int n0 = s.off[l][t - 1], n1 = s.off[l][t];             // the units of degree t - 1
@@ -81,10 +86,16 @@ __global__ __launch_bounds__(kThreads) void made_prefix_k(StepArgs s, const floa
     if (mode == GNF_MADE_NORM_NONE) {
       for (int i = tid; i < nrows * out; i += kThreads) h_out[row0 * out + i] = hbuf[i];
     } else if (tid < nrows) {
-      // AffineNormalizer.py:14-17, the arithmetic of gnf_affine_inv
-      const float mu = fminf(fmaxf(hbuf[tid * out], -5.f), 5.f);
-      const float sg = expf(fminf(fmaxf(hbuf[tid * out + 1], -5.f), 2.f));
-      const float xv = (zv - mu) / sg;
+      float xv;
+      if (mode == GNF_MADE_NORM_SPLINE) {
+        // the arithmetic of gnf_spline_inv on the row's 3K - 1 outputs (hbuf is rewritten by the next step)
+        xv = spline_row_inverse(hbuf + tid * out, s.spl_K, s.spl_T, zv);
+      } else {
+        // AffineNormalizer.py:14-17, the arithmetic of gnf_affine_inv
+        const float mu = fminf(fmaxf(hbuf[tid * out], -5.f), 5.f);
+        const float sg = expf(fminf(fmaxf(hbuf[tid * out + 1], -5.f), 2.f));
+        xv = (zv - mu) / sg;
+      }
       x[(row0 + tid) * d + v] = xv;
       act[(size_t)tid * A + c + t] = xv;
     }
@@ -138,16 +149,25 @@ int64_t gnf_made_prefix_ctx_ws_bytes(const gnf_made_net* net, int cond_in, int64
   return 4 * B * lay.A;
 }
 
-int gnf_made_prefix_ctx(const gnf_made_net* net, int cond_in, const float* context, const float* pack, const float* z,
-                        float* x, float* h_out, int t0, int t1, int normalizer_mode, int64_t B, void* ws, int64_t ws_bytes,
-                        gnf_stream_t stream) {
+int gnf_made_prefix_ctx_spline(const gnf_made_net* net, int cond_in, const float* context, const float* pack, const float* z,
+                               float* x, float* h_out, int t0, int t1, int normalizer_mode, int spline_bins, double spline_tail,
+                               int64_t B, void* ws, int64_t ws_bytes, gnf_stream_t stream) {
   StepArgs s;
   const int rc = make_layout(net, cond_in, &s.lay);
   if (rc) return rc;
   if (B < 0 || t0 < 0 || t1 < t0 || t1 > net->d) return GNF_EINVAL;
-  if (normalizer_mode != GNF_MADE_NORM_NONE && normalizer_mode != GNF_MADE_NORM_AFFINE) return GNF_EINVAL;
+  if (normalizer_mode != GNF_MADE_NORM_NONE && normalizer_mode != GNF_MADE_NORM_AFFINE &&
+      normalizer_mode != GNF_MADE_NORM_SPLINE)
+    return GNF_EINVAL;
   if (normalizer_mode == GNF_MADE_NORM_NONE && t1 > t0 + 1) return GNF_EINVAL;
   if (normalizer_mode == GNF_MADE_NORM_AFFINE && net->out < 2) return GNF_ESHAPE;
+  if (normalizer_mode == GNF_MADE_NORM_SPLINE) {
+    if (spline_bins < kSplMinBins || spline_bins > kSplMaxBins || !(spline_tail > 0.) || !(spline_tail < 3.0e38))
+      return GNF_EINVAL;
+    if (net->out < 3 * spline_bins - 1) return GNF_ESHAPE;
+    s.spl_K = spline_bins;
+    s.spl_T = spline_tail;
+  }
   if (B == 0 || t1 == t0) return 0;
   if (!pack || !x || !net->var_of_step || (cond_in > 0 && !context)) return GNF_EINVAL;
   if ((uintptr_t)pack & 15) return GNF_EINVAL;          // rows of the weight image are read as 16-byte quads (ld4)
@@ -172,6 +192,22 @@ int gnf_made_prefix_ctx(const gnf_made_net* net, int cond_in, const float* conte
     case 8: return launch<8>(s, lds, smem, grid, st, pack, context, z, x, h_out, t0, t1, normalizer_mode, w, B);
     default: return launch<16>(s, lds, smem, grid, st, pack, context, z, x, h_out, t0, t1, normalizer_mode, w, B);
   }
+}
+
+// the entry points from before the spline: the same code, any mode but NONE / AFFINE refused as ever
+int gnf_made_prefix_ctx(const gnf_made_net* net, int cond_in, const float* context, const float* pack, const float* z,
+                        float* x, float* h_out, int t0, int t1, int normalizer_mode, int64_t B, void* ws, int64_t ws_bytes,
+                        gnf_stream_t stream) {
+  if (normalizer_mode == GNF_MADE_NORM_SPLINE) return GNF_EINVAL;
+  return gnf_made_prefix_ctx_spline(net, cond_in, context, pack, z, x, h_out, t0, t1, normalizer_mode, 0, 0., B, ws, ws_bytes,
+                                    stream);
+}
+
+int gnf_made_prefix_spline(const gnf_made_net* net, const float* pack, const float* z, float* x, float* h_out, int t0, int t1,
+                           int normalizer_mode, int spline_bins, double spline_tail, int64_t B, void* ws, int64_t ws_bytes,
+                           gnf_stream_t stream) {
+  return gnf_made_prefix_ctx_spline(net, 0, nullptr, pack, z, x, h_out, t0, t1, normalizer_mode, spline_bins, spline_tail, B,
+                                    ws, ws_bytes, stream);
 }
 
 // the unconditional entry points: cond_in = 0 of the same code

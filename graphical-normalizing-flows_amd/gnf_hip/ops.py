@@ -159,8 +159,85 @@ def affine_inverse(z, h):
     return x
 
 
+# ----------------------------------------------------------------------------- Spline normalizer
+def _spline_args(h, nb_bins, tail_bound):
+    """(K, T) checked against the conditioner output h [.., .., C]: ValueError before anything is launched"""
+    K, T = int(nb_bins), float(tail_bound)
+    if not abi.SPLINE_MIN_BINS <= K <= abi.SPLINE_MAX_BINS:
+        raise ValueError("spline: nb_bins = %d, must be %d .. %d" % (K, abi.SPLINE_MIN_BINS, abi.SPLINE_MAX_BINS))
+    if not (T > 0. and math.isfinite(T)):
+        raise ValueError("spline: tail_bound = %r, must be positive and finite" % (tail_bound,))
+    if h.dim() != 3 or h.shape[2] < 3 * K - 1:
+        raise ValueError("spline: %d bins read 3 K - 1 = %d conditioner outputs per variable, h is %s"
+                         % (K, 3 * K - 1, tuple(h.shape)))
+    return K, T
+
+
+class SplineFn(torch.autograd.Function):
+    """(z, jac, logdet, logn) of the monotone rational-quadratic spline with K bins on [-T, T] (include/gnf_hip.h,
+    gnf_spline_fwd), the two row reductions fused as in AffineFn; the backward recomputes the forward."""
+
+    @staticmethod
+    def forward(ctx, x, h, nb_bins=8, tail_bound=3., want_jac=True, want_logn=False):
+        K, T = _spline_args(h, nb_bins, tail_bound)
+        x = x.contiguous()
+        B, d = x.shape
+        ctx.set_materialize_grads(False)     # a step that only uses logdet / logn must not get zero tensors for z and jac
+        z, logdet = _empty((B, d), x), _empty((B,), x)
+        jac = _empty((B, d), x) if want_jac else None
+        logn = _empty((B,), x) if want_logn else None
+        call("gnf_spline_fwd", ptr(x), ptr(h), h.stride(0), h.stride(1), h.stride(2), h.shape[2], K, T, ptr(z), ptr(jac),
+             ptr(logdet), ptr(logn), B, d, stream())
+        ctx.save_for_backward(x, h)
+        ctx.KT = (K, T)
+        if jac is None:
+            jac = z.new_empty(0)
+            ctx.mark_non_differentiable(jac)
+        if logn is None:
+            logn = z.new_empty(0)
+            ctx.mark_non_differentiable(logn)
+        return z, jac, logdet, logn
+
+    @staticmethod
+    def backward(ctx, gz, gjac, glogdet, glogn=None):
+        x, h = ctx.saved_tensors
+        B, d = x.shape
+        K, T = ctx.KT
+        # same memory format as h so that e.g. MADE's permuted view flows back without a copy
+        gh = torch.empty_like(h) if h.shape[2] == 3 * K - 1 else torch.zeros_like(h)
+        gx = _empty((B, d), x) if ctx.needs_input_grad[0] else None
+        call("gnf_spline_bwd", ptr(x), ptr(h), h.stride(0), h.stride(1), h.stride(2), h.shape[2], K, T,
+             ptr(gz.contiguous()) if gz is not None else None,
+             ptr(gjac.contiguous()) if (gjac is not None and gjac.numel() > 0) else None,
+             ptr(glogdet.contiguous()) if glogdet is not None else None,
+             ptr(glogn.contiguous()) if (glogn is not None and glogn.numel() > 0) else None,
+             ptr(gx), ptr(gh), gh.stride(0), gh.stride(1), gh.stride(2), B, d, stream())
+        return gx, gh, None, None, None, None
+
+
+def spline_inverse(z, h, nb_bins=8, tail_bound=3., out=None, out_cols=None):
+    """the spline's closed-form inverse (gnf_spline_inv).  out / out_cols: write the TRANSPOSED result into columns out_cols
+    of `out`, as monotonic_inverse does for the level and column schedules (z [variables, batch], out [batch, d])."""
+    K, T = _spline_args(h, nb_bins, tail_bound)
+    z = z.contiguous()
+    B, d = z.shape
+    if out is not None:
+        assert out.is_contiguous() and out.dtype == torch.float32 and out.shape[0] == d and out_cols.dtype == torch.int32
+        assert out_cols.numel() == B and out_cols.device == z.device
+        if z.numel() == 0:                   # no variable or no sample (an empty batch is the SECOND dimension here)
+            return out
+        call("gnf_spline_inv", ptr(z), ptr(h), h.stride(0), h.stride(1), h.stride(2), h.shape[2], K, T, ptr(out),
+             abi.rawptr(out_cols), out.shape[1], B, d, stream())
+        return out
+    x = _empty((B, d), z)
+    if z.numel():
+        call("gnf_spline_inv", ptr(z), ptr(h), h.stride(0), h.stride(1), h.stride(2), h.shape[2], K, T, ptr(x), None, 0, B,
+             d, stream())
+    return x
+
+
 # ----------------------------------------------------------------------------- MADE prefix evaluation
-MADE_NORM_NONE, MADE_NORM_AFFINE = abi.MADE_NORM_NONE, abi.MADE_NORM_AFFINE
+MADE_NORM_NONE, MADE_NORM_AFFINE, MADE_NORM_SPLINE = abi.MADE_NORM_NONE, abi.MADE_NORM_AFFINE, abi.MADE_NORM_SPLINE
 
 
 def _made_net(params, plan):
@@ -232,13 +309,14 @@ def made_prefix_workspace(params, plan, batch):
 
 
 @torch.no_grad()
-def made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=None, ws=None, context=None):
+def made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=None, ws=None, context=None, spline=None):
     """Steps t0 <= t < t1 of the column-by-column inversion of a MADE step (gnf_made_prefix): z, x [B, d] fp32 contiguous.
     MADE_NORM_AFFINE writes column var_of_step[t] of x per step ((0, d): the whole inversion, one launch);
     MADE_NORM_NONE (t1 == t0 + 1) writes the conditioner outputs of that variable to h_out [B, out] and leaves the column
     to the caller.  ws (made_prefix_workspace): the same buffer for every call of one inversion; allocated here when a call
     that needs one comes without.  context: the contiguous fp32 [B, cond_in] device tensor of a conditional plan
-    (gnf_made_prefix_ctx), None for cond_in == 0."""
+    (gnf_made_prefix_ctx), None for cond_in == 0.  MADE_NORM_SPLINE takes spline = (nb_bins, tail_bound) and runs on the
+    gnf_made_prefix*_spline entry points (the others refuse that mode)."""
     params = [p.detach() for p in params]
     net, c = _made_net(params, plan), _plan_cond_in(plan)
     B, d = x.shape
@@ -257,9 +335,13 @@ def made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=None, ws=Non
         name, head = "gnf_made_prefix_ctx", (ctypes.byref(net), c, ptr(context))
     if ws is None and not (t0 == 0 and t1 == d):
         ws = made_prefix_workspace(params, plan, B)
-    args = lambda w: head + (ptr(pack), ptr(z), ptr(x), ptr(h_out), int(t0), int(t1), int(mode), B,
-                             None if w is None else ctypes.c_void_p(w.data_ptr()), 0 if w is None else w.numel() * 4,
-                             stream())
+    extra = ()
+    if int(mode) == MADE_NORM_SPLINE:
+        if spline is None:
+            raise abi.GnfError("made_prefix_steps: MADE_NORM_SPLINE needs spline = (nb_bins, tail_bound)")
+        name, extra = name + "_spline", (int(spline[0]), float(spline[1]))
+    args = lambda w: head + (ptr(pack), ptr(z), ptr(x), ptr(h_out), int(t0), int(t1), int(mode)) + extra + (
+        B, None if w is None else ctypes.c_void_p(w.data_ptr()), 0 if w is None else w.numel() * 4, stream())
     if ws is None:
         # a whole inversion whose tile of activations fits in LDS needs no workspace; the library says when it does not
         rc = getattr(abi.load(), name)(*args(None))

@@ -263,12 +263,14 @@ class AutoregressiveConditioner(Conditioner):
     def prefix_workspace(self, batch):
         return ops.made_prefix_workspace(self._prefix_params(), self.prefix_plan(with_context=bool(self.cond_in)), batch)
 
-    def prefix_steps(self, z, x, t0, t1, mode, h_out=None, ws=None, context=None):
+    def prefix_steps(self, z, x, t0, t1, mode, h_out=None, ws=None, context=None, spline=None):
         """steps t0 <= t < t1 of the plan on the HIP prefix kernel (gnf_hip.ops.made_prefix_steps); `context`: the checked
-        [B, cond_in] context of a conditional conditioner (the plan is then prefix_plan(with_context=True))"""
+        [B, cond_in] context of a conditional conditioner (the plan is then prefix_plan(with_context=True)); `spline`:
+        (nb_bins, tail_bound) for ops.MADE_NORM_SPLINE"""
         plan, params = self.prefix_plan(with_context=bool(self.cond_in)), self._prefix_params()
         pack = self._held_prefix if self._held_prefix is not None else ops.made_prefix_pack(params, plan)
-        return ops.made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=h_out, ws=ws, context=context)
+        return ops.made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=h_out, ws=ws, context=context,
+                                     **({} if spline is None else {"spline": spline}))
 
     # -- the adjoint of that sweep (NormalizingFlowStep.rsample's backward) -------------------------------------------------
     _held_adjoint = None

@@ -6,5 +6,6 @@ The names exported here are the ones the reference's package exports."""
 from .Normalizer import Normalizer
 from .AffineNormalizer import AffineNormalizer
 from .MonotonicNormalizer import MonotonicNormalizer
+from .SplineNormalizer import SplineNormalizer      # not in the reference: rational-quadratic spline, closed-form inverse
 
-__all__ = ["Normalizer", "AffineNormalizer", "MonotonicNormalizer"]
+__all__ = ["Normalizer", "AffineNormalizer", "MonotonicNormalizer", "SplineNormalizer"]

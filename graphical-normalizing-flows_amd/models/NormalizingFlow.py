@@ -15,7 +15,7 @@ import torch.nn as nn
 from gnf_hip import ops
 from .Conditionners import Conditioner, DAGConditioner
 from .Conditionners.Conditioner import checked_context
-from .Normalizers import Normalizer, AffineNormalizer
+from .Normalizers import Normalizer, AffineNormalizer, SplineNormalizer
 
 
 # captured inversion graphs per NormalizingFlowStep, kept OUTSIDE the modules: a hipGraph is neither copyable nor
@@ -300,6 +300,11 @@ class NormalizingFlowStep(NormalizingFlow):
             if type(self.normalizer) is AffineNormalizer:
                 # the whole inversion, one launch
                 cond.prefix_steps(z, x, 0, d, ops.MADE_NORM_AFFINE, **({"context": context} if cond_in else {}))
+                return x
+            if type(self.normalizer) is SplineNormalizer:
+                # likewise: the spline's closed-form inverse is the kernel's per-row epilogue
+                cond.prefix_steps(z, x, 0, d, ops.MADE_NORM_SPLINE, spline=(self.normalizer.nb_bins, self.normalizer.tail_bound),
+                                  **({"context": context} if cond_in else {}))
                 return x
             h = torch.empty(B, out, dtype=torch.float32, device=z.device)
             ws = cond.prefix_workspace(B)

@@ -57,6 +57,13 @@ def MNIST_A_prior(in_size, kernel):
     return A
 
 
+def _emb_size(normalizer_type, normalizer_args, default):
+    """conditioner outputs per pixel: a normalizer type that offers `h_size` (SplineNormalizer: 3 nb_bins - 1) says how many
+    it reads; the reference's two keep their 2 / 30"""
+    h_size = getattr(normalizer_type, "h_size", None)
+    return default if h_size is None else int(h_size(**normalizer_args))
+
+
 # the scales of the MNIST factories: (image size, block dropped after the scale, MNISTCNN fc sizes)
 _MNIST_SCALES = (([1, 28, 28], [1, 2, 2], [2304, 128]),
                  ([1, 14, 14], [1, 2, 2], [400, 64]),
@@ -68,7 +75,7 @@ def _mnist_dag_steps(n_steps, img_size, fc, normalizer_type, normalizer_args, l1
     """`n_steps` DAG-conditioner steps on one image scale, each with its own MNISTCNN embedding net."""
     pixels = img_size[0] * img_size[1] * img_size[2]
     monotonic = normalizer_type is MonotonicNormalizer
-    emb_size = 30 if monotonic else 2
+    emb_size = _emb_size(normalizer_type, normalizer_args, 30 if monotonic else 2)
     out = []
     for _ in range(n_steps):
         prior = MNIST_A_prior(img_size[1], prior_kernel) if prior_kernel is not None else None
@@ -114,7 +121,7 @@ def _cifar_dag_steps(n_steps, img_size, fc, k_size, normalizer_type, normalizer_
     """`n_steps` DAG-conditioner steps on one image scale, each with its own CIFAR10CNN embedding net; the normalizer is
     built from `normalizer_args` alone (a Monotonic caller passes `cond_size` itself, as with the reference)"""
     pixels = img_size[0] * img_size[1] * img_size[2]
-    emb_size = 2 if normalizer_type is AffineNormalizer else 30
+    emb_size = _emb_size(normalizer_type, normalizer_args, 2 if normalizer_type is AffineNormalizer else 30)
     out = []
     for _ in range(n_steps):
         net = CIFAR10CNN(out_d=emb_size, fc_l=fc, size_img=img_size, k_size=k_size)

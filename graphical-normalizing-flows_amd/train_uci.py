@@ -28,11 +28,11 @@ import yaml
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from models import (buildFCNormalizingFlow, DAGConditioner, CouplingConditioner, AutoregressiveConditioner,  # noqa: E402
-                    AffineNormalizer, MonotonicNormalizer)
+                    AffineNormalizer, MonotonicNormalizer, SplineNormalizer)
 from gnf_hip import dp  # noqa: E402
 
 COND = {"DAG": DAGConditioner, "Coupling": CouplingConditioner, "Autoregressive": AutoregressiveConditioner}
-NORM = {"affine": AffineNormalizer, "monotonic": MonotonicNormalizer}
+NORM = {"affine": AffineNormalizer, "monotonic": MonotonicNormalizer, "spline": SplineNormalizer}
 DIMS = {"power": 6, "gas": 8, "hepmass": 21, "miniboone": 43, "bsds300": 63, "digits": 64, "proteins": 11}
 
 
@@ -77,6 +77,12 @@ def build(args, dim):
     if norm_t is MonotonicNormalizer:
         nargs = {"integrand_net": args.int_net, "cond_size": args.emb_net[-1], "nb_steps": args.nb_steps,
                  "solver": args.solver}
+    if norm_t is SplineNormalizer:
+        nargs = {"nb_bins": getattr(args, "spline_bins", 8), "tail_bound": getattr(args, "spline_tail", 3.)}
+        need = SplineNormalizer.h_size(**nargs)
+        if args.emb_net[-1] < need:              # before any training: the kernel would refuse the first batch
+            raise ValueError("-normalizer spline with -spline_bins %d reads 3 K - 1 = %d conditioner outputs per variable: "
+                             "the last entry of -emb_net is %d" % (nargs["nb_bins"], need, args.emb_net[-1]))
     model = buildFCNormalizingFlow(args.nb_flow, cond_t, cargs, norm_t, nargs)
     if getattr(args, "gated_front", False):      # DAG gate and one-hot built inside the first DAGMLP layer (csrc/gnf_dagmlp.hip)
         for c in model.getConditioners():
@@ -329,6 +335,8 @@ def parse(argv=None):
     ap.add_argument("-l1", default=.2, type=float)
     ap.add_argument("-gumble_T", default=1., type=float)
     ap.add_argument("-normalizer", default="affine", choices=sorted(NORM))
+    ap.add_argument("-spline_bins", default=8, type=int, help="-normalizer spline: bins K (2 .. 32); -emb_net must end in >= 3 K - 1")
+    ap.add_argument("-spline_tail", default=3., type=float, help="-normalizer spline: the spline acts on [-T, T], identity outside")
     ap.add_argument("-int_net", default=[100, 100, 100, 100], nargs="+", type=int)
     ap.add_argument("-nb_steps", default=20, type=int)
     ap.add_argument("-solver", default="CC", type=str, choices=["CC", "CCParallel"])

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-/* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_*, gnf_image_prep, gnf_dagmlp_*, gnf_dag_levels*, gnf_toy_sample, gnf_shuffle_keys, gnf_tab_batch and gnf_group_bias_* were ADDED under this number (no existing symbol
+/* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_*, gnf_image_prep, gnf_dagmlp_*, gnf_dag_levels*, gnf_toy_sample, gnf_shuffle_keys, gnf_tab_batch, gnf_group_bias_*, gnf_spline_* and gnf_made_prefix*_spline were ADDED under this number (no existing symbol
  * changed; a binding written against the earlier 11 keeps working, and tests/test_cifar_factory.py pins the value) */
 #define GNF_ABI_VERSION 11
 #define GNF_EINVAL (-1)   /* bad argument (null pointer, negative size, ...)          */
@@ -70,6 +70,29 @@ int gnf_affine_bwd(const float* x, const float* h, int64_t h_sb, int64_t h_sd, i
 /* x = (z - mu)/sigma  (AffineNormalizer.py:14-17). */
 int gnf_affine_inv(const float* z, const float* h, int64_t h_sb, int64_t h_sd, int64_t h_sc,
                    float* x, int64_t B, int64_t d, gnf_stream_t stream);
+
+/* ---- Spline normalizer: monotone rational-quadratic spline (Durkan et al. 2019), K bins on [-T, T], identity outside ---
+ * 2 <= K <= 32, T > 0 (else GNF_EINVAL).  Of the h_c components of h[b,i,:] (addressed as in gnf_affine_*; h_c < 3K-1:
+ * GNF_ESHAPE) the first 3K-1 are read: K width logits, K height logits, K-1 derivative logits.
+ *   w = 1e-3 + (1 - 1e-3 K) softmax(h[0:K]),  X_0 = -T, X_k = -T + 2T sum_{j<k} w_j, X_K = T; Y alike from h[K:2K];
+ *   D_0 = D_K = 1, D_k = 1e-3 + softplus(h[2K+k-1]);  k = #{j in 1..K-1: x >= X_j}, W = X_{k+1}-X_k, H = Y_{k+1}-Y_k,
+ *   xi = (x-X_k)/W, s = H/W, e = D_{k+1}+D_k-2s, den = s + e xi(1-xi):
+ *   z = Y_k + H (s xi^2 + D_k xi(1-xi))/den,  jac = s^2 (D_{k+1} xi^2 + 2 s xi(1-xi) + D_k (1-xi)^2)/den^2   for -T <= x <= T,
+ *   z = x, jac = 1 otherwise (NaN and +-inf included).
+ * fwd: z [B,d]; jac [B,d], logdet [B] (= sum_i log jac) and logn [B] (= -0.5 sum_i (log 2pi + z^2)) may be NULL; the
+ *   reductions happen in the pass that produces z, in a fixed order.
+ * bwd: recomputes the forward; cotangents gz, gjac [B,d], glogdet, glogn [B], each may be NULL; gx [B,d] or NULL;
+ *   gh[b,i,c] at b*g_sb + i*g_sd + c*g_sc receives components 0 .. 3K-2 (the caller zero-fills any beyond).
+ * inv: x = the inverse of z.  out_cols == NULL: x [B,d].  out_cols (int32 [B]) given: the variable-major scatter form
+ *   of gnf_monotonic_inv_scatter -- z [B,d] holds B variables of d samples and element (b,j) goes to
+ *   x[j*out_width + out_cols[b]]; nothing else of x is written. */
+int gnf_spline_fwd(const float* x, const float* h, int64_t h_sb, int64_t h_sd, int64_t h_sc, int64_t h_c, int K, double T,
+                   float* z, float* jac, float* logdet, float* logn, int64_t B, int64_t d, gnf_stream_t stream);
+int gnf_spline_bwd(const float* x, const float* h, int64_t h_sb, int64_t h_sd, int64_t h_sc, int64_t h_c, int K, double T,
+                   const float* gz, const float* gjac, const float* glogdet, const float* glogn, float* gx, float* gh,
+                   int64_t g_sb, int64_t g_sd, int64_t g_sc, int64_t B, int64_t d, gnf_stream_t stream);
+int gnf_spline_inv(const float* z, const float* h, int64_t h_sb, int64_t h_sd, int64_t h_sc, int64_t h_c, int K, double T,
+                   float* x, const int32_t* out_cols, int64_t out_width, int64_t B, int64_t d, gnf_stream_t stream);
 
 /* ---- row reductions: models/NormalizingFlow.py:70, NormalizingFlowFactories.py:15-16 --
  * logsum:  out[b] = sum_i log(jac[b,i]);        bwd: gjac[b,i] = g[b]/jac[b,i]
@@ -389,6 +412,17 @@ int64_t gnf_made_prefix_ctx_ws_bytes(const gnf_made_net* net, int cond_in, int64
 int gnf_made_prefix_ctx(const gnf_made_net* net, int cond_in, const float* context, const float* pack, const float* z,
                         float* x, float* h_out, int t0, int t1, int normalizer_mode, int64_t B, void* ws, int64_t ws_bytes,
                         gnf_stream_t stream);
+/* The same two entry points with a third mode: GNF_MADE_NORM_SPLINE (out >= 3 spline_bins - 1, else GNF_ESHAPE; bins and
+ * tail as for gnf_spline_inv, else GNF_EINVAL) inverts column var_of_step[t] per step with the arithmetic of gnf_spline_inv
+ * on the step's outputs; (0, d) is the whole inversion of a Spline + MADE step in one launch.  NONE / AFFINE: the calls
+ * above (spline_bins / spline_tail ignored).  gnf_made_prefix and gnf_made_prefix_ctx themselves refuse the new mode. */
+#define GNF_MADE_NORM_SPLINE 2
+int gnf_made_prefix_spline(const gnf_made_net* net, const float* pack, const float* z, float* x, float* h_out, int t0, int t1,
+                           int normalizer_mode, int spline_bins, double spline_tail, int64_t B, void* ws, int64_t ws_bytes,
+                           gnf_stream_t stream);
+int gnf_made_prefix_ctx_spline(const gnf_made_net* net, int cond_in, const float* context, const float* pack, const float* z,
+                               float* x, float* h_out, int t0, int t1, int normalizer_mode, int spline_bins, double spline_tail,
+                               int64_t B, void* ws, int64_t ws_bytes, gnf_stream_t stream);
 
 /* ---- MADE adjoint sweep: lambda with J^T lambda = g for one MADE step (NormalizingFlowStep.rsample's backward) ----------
  * The step is z = S(x; context): h = MADE(context, x), z[b, i] = normalizer(x[b, i], h[b, i, :]).  In degree order
