@@ -131,6 +131,8 @@ SIGNATURES = {
                                        c_i64, ctypes.c_void_p, c_i64, c_stream]),
     "gnf_made_prefix_ctx_spline": (c_int, [ctypes.POINTER(MadeNet), c_int, c_f, c_f, c_f, c_f, c_f, c_int, c_int, c_int,
                                            c_int, c_double, c_i64, ctypes.c_void_p, c_i64, c_stream]),
+    "gnf_made_prefix_do": (c_int, [ctypes.POINTER(MadeNet), c_int, c_f, c_f, c_f, c_f, c_f, c_int, c_int, c_int, c_int,
+                                   c_double, ctypes.c_void_p, c_i64, ctypes.c_void_p, c_i64, c_stream]),
     "gnf_made_adjoint_pack_floats": (c_i64, [ctypes.POINTER(MadeNet), c_int]),
     "gnf_made_adjoint_pack": (c_int, [ctypes.POINTER(MadeNet), c_int, c_f, c_stream]),
     "gnf_made_adjoint_ws_bytes": (c_i64, [ctypes.POINTER(MadeNet), c_int, c_i64]),

@@ -24,6 +24,14 @@
 // layers the output layer is that first layer (K = c at step 0: the outputs of the degree-0 variable move with the
 // context); with hidden layers those outputs read no hidden unit and stay the output bias.  c = 0 is the unconditional
 // kernel, instruction for instruction on the arithmetic path.
+//
+// An intervention do(x_P = v) (gnf_made_prefix_do, NormalizingFlowStep.intervene) hands a pin table over, one byte per
+// VARIABLE.  A pinned step keeps the hidden units of degree t - 1 -- later columns read them -- and replaces the rest by a
+// load: the caller's x[b, v] becomes the activation row's input c + t; no output-layer product, no epilogue, no store to x.
+// The table is the same for every lane, so the branch is uniform and both sides meet the same two barriers.  The kernel
+// is instantiated with and without pins: pin == NULL launches the kernel of the entry points above, untouched.
+#include <vector>
+
 #include "gnf_made.h"
 #include "gnf_spline.h"
 
@@ -40,11 +48,11 @@ __global__ void made_prefix_pack_k(PackArgs a, float* __restrict__ pack) {
 __device__ __noinline__ float spline_row_inverse(float* r, int K, double T, float z) { return spl_inverse<false>(r, K, T, z); }
 
 // ------------------------------------------------------------------------------------------------ the step kernel
-template <int TB, bool kLds>
+template <int TB, bool kLds, bool kPin>
 __global__ __launch_bounds__(kThreads) void made_prefix_k(StepArgs s, const float* __restrict__ pack,
                                                           const float* __restrict__ context, const float* __restrict__ z,
                                                           float* x, float* __restrict__ h_out, int t0, int t1, int mode,
-                                                          float* ws, int64_t B) {
+                                                          float* ws, int64_t B, const uint8_t* __restrict__ pin) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const MadeLayout& L = s.lay;
   float* red = smem;
@@ -62,14 +70,16 @@ __global__ __launch_bounds__(kThreads) void made_prefix_k(StepArgs s, const floa
     __syncthreads();
   }
   if (!kLds && t0 >= 1) {
-    // the column the caller inverted since the previous launch: the newest input of this one
+    // the column the caller inverted (or pinned: x holds it either way) since the previous launch: the newest input of
+    // this one
     if (tid < nrows) act[(size_t)tid * A + c + t0 - 1] = x[(row0 + tid) * d + s.var_of_step[t0 - 1]];
     __syncthreads();
   }
   for (int t = t0; t < t1; ++t) {
     const int v = s.var_of_step[t];
     // the step's z is asked for before the layers, which hide its latency
-    const float zv = mode != GNF_MADE_NORM_NONE && tid < nrows ? z[(row0 + tid) * d + v] : 0.f;
+    const bool pinned = kPin && pin[v] != 0;                           // one byte per variable: uniform over the workgroup
+    const float zv = mode != GNF_MADE_NORM_NONE && !pinned && tid < nrows ? z[(row0 + tid) * d + v] : 0.f;
     if (t >= 1)
       for (int l = 0; l < nh; ++l) {
         const int n0 = s.off[l][t - 1], n1 = s.off[l][t];             // the units of degree t - 1
@@ -77,13 +87,20 @@ __global__ __launch_bounds__(kThreads) void made_prefix_k(StepArgs s, const floa
         layer_step<TB>(pack + L.w_off[l] + (size_t)n0 * L.ldw[l], L.ldw[l], L.rows[l] - n0, pack + L.b_off[l] + n0,
                        n1 - n0, K, act + (l == 0 ? 0 : L.act_off[l - 1]), A, act + L.act_off[l] + n0, A, true, nrows, red);
       }
-    {
+    if (pinned) {
+      // do(x_v): the caller's value is what the later steps read; the step's outputs and its z have no reader.  The barrier
+      // stands where the output layer's would (the last step's readers of hbuf are past the one that ended it)
+      if (tid < nrows) act[(size_t)tid * A + c + t] = x[(row0 + tid) * d + v];
+      __syncthreads();
+    } else {
       const int K = nh == 0 ? c + t : s.off[nh - 1][t];                // strict rule: degree < t (the context's is -1)
       const int n0 = t * out;
       layer_step<TB>(pack + L.w_off[nh] + (size_t)n0 * L.ldw[nh], L.ldw[nh], L.rows[nh] - n0, pack + L.b_off[nh] + n0,
                      out, K, act + (nh == 0 ? 0 : L.act_off[nh - 1]), A, hbuf, out, false, nrows, red);
     }
-    if (mode == GNF_MADE_NORM_NONE) {
+    if (pinned) {
+      // nothing: h_out and x[b, v] stay the caller's
+    } else if (mode == GNF_MADE_NORM_NONE) {
       for (int i = tid; i < nrows * out; i += kThreads) h_out[row0 * out + i] = hbuf[i];
     } else if (tid < nrows) {
       float xv;
@@ -109,12 +126,86 @@ int64_t lds_bytes(const MadeLayout& lay, int TB, bool with_act) {
 
 template <int TB>
 int launch(const StepArgs& s, bool lds, size_t smem, int64_t grid, hipStream_t st, const float* pack, const float* context,
-           const float* z, float* x, float* h_out, int t0, int t1, int mode, float* ws, int64_t B) {
-  hipError_t e = lds ? gnf_launch_lds(made_prefix_k<TB, true>, dim3((unsigned)grid), dim3(kThreads), smem, st, s, pack,
-                                      context, z, x, h_out, t0, t1, mode, ws, B)
-                     : gnf_launch_lds(made_prefix_k<TB, false>, dim3((unsigned)grid), dim3(kThreads), smem, st, s, pack,
-                                      context, z, x, h_out, t0, t1, mode, ws, B);
+           const float* z, float* x, float* h_out, int t0, int t1, int mode, float* ws, int64_t B, const uint8_t* pin) {
+  const dim3 g((unsigned)grid), b(kThreads);
+  hipError_t e;
+  if (pin)
+    e = lds ? gnf_launch_lds(made_prefix_k<TB, true, true>, g, b, smem, st, s, pack, context, z, x, h_out, t0, t1, mode, ws, B,
+                             pin)
+            : gnf_launch_lds(made_prefix_k<TB, false, true>, g, b, smem, st, s, pack, context, z, x, h_out, t0, t1, mode, ws,
+                             B, pin);
+  else
+    e = lds ? gnf_launch_lds(made_prefix_k<TB, true, false>, g, b, smem, st, s, pack, context, z, x, h_out, t0, t1, mode, ws,
+                             B, pin)
+            : gnf_launch_lds(made_prefix_k<TB, false, false>, g, b, smem, st, s, pack, context, z, x, h_out, t0, t1, mode, ws,
+                             B, pin);
   return e == hipSuccess ? 0 : (int)e;
+}
+
+// GNF_MADE_NORM_NONE over more than one step: every step but the last must be pinned (its outputs would have no caller to
+// invert them).  The table lives on the device, so this one form of the call reads it back -- d bytes and the steps'
+// variables -- and waits for the stream; every other form is checked from the host arguments alone.
+int check_pinned_run(const gnf_made_net* net, const uint8_t* pin, int t0, int t1, hipStream_t st) {
+  std::vector<uint8_t> tab((size_t)net->d);
+  std::vector<int32_t> var((size_t)(t1 - 1 - t0));
+  hipError_t e = hipMemcpyAsync(tab.data(), pin, tab.size(), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(var.data(), net->var_of_step + t0, 4 * var.size(), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return (int)e;
+  for (int32_t v : var)
+    if (v < 0 || v >= net->d || !tab[(size_t)v]) return GNF_EINVAL;
+  return 0;
+}
+
+int prefix_run(const gnf_made_net* net, int cond_in, const float* context, const float* pack, const float* z, float* x,
+               float* h_out, int t0, int t1, int normalizer_mode, int spline_bins, double spline_tail, const uint8_t* pin,
+               int64_t B, void* ws, int64_t ws_bytes, gnf_stream_t stream) {
+  StepArgs s;
+  const int rc = make_layout(net, cond_in, &s.lay);
+  if (rc) return rc;
+  if (B < 0 || t0 < 0 || t1 < t0 || t1 > net->d) return GNF_EINVAL;
+  if (normalizer_mode != GNF_MADE_NORM_NONE && normalizer_mode != GNF_MADE_NORM_AFFINE &&
+      normalizer_mode != GNF_MADE_NORM_SPLINE)
+    return GNF_EINVAL;
+  // NONE hands ONE variable's outputs back; more steps only behind a run of pinned ones (checked below, on the table)
+  const bool run = normalizer_mode == GNF_MADE_NORM_NONE && t1 > t0 + 1;
+  if (run && !pin) return GNF_EINVAL;
+  if (normalizer_mode == GNF_MADE_NORM_AFFINE && net->out < 2) return GNF_ESHAPE;
+  if (normalizer_mode == GNF_MADE_NORM_SPLINE) {
+    if (spline_bins < kSplMinBins || spline_bins > kSplMaxBins || !(spline_tail > 0.) || !(spline_tail < 3.0e38))
+      return GNF_EINVAL;
+    if (net->out < 3 * spline_bins - 1) return GNF_ESHAPE;
+    s.spl_K = spline_bins;
+    s.spl_T = spline_tail;
+  }
+  if (B == 0 || t1 == t0) return 0;
+  if (!pack || !x || !net->var_of_step || (cond_in > 0 && !context)) return GNF_EINVAL;
+  if ((uintptr_t)pack & 15) return GNF_EINVAL;          // rows of the weight image are read as 16-byte quads (ld4)
+  if (normalizer_mode == GNF_MADE_NORM_NONE ? !h_out : !z) return GNF_EINVAL;
+  for (int l = 0; l < net->nh; ++l) {
+    if (!net->off[l]) return GNF_EINVAL;
+    s.off[l] = net->off[l];
+  }
+  s.var_of_step = net->var_of_step;
+  const int TB = tile_rows(net, B);
+  const int64_t grid = (B + TB - 1) / TB;
+  if (grid > 0x7fffffff) return GNF_ESHAPE;
+  hipStream_t st = (hipStream_t)stream;
+  if (run) {
+    const int bad = check_pinned_run(net, pin, t0, t1, st);
+    if (bad) return bad;
+  }
+  // the whole inversion in one launch keeps the tile's activations in LDS; step launches hand them on through ws
+  const bool lds = t0 == 0 && t1 == net->d && lds_bytes(s.lay, TB, true) <= kLdsBytes;
+  if (lds_bytes(s.lay, TB, false) > kLdsBytes) return GNF_ESHAPE;
+  if (!lds && (!ws || ws_bytes < 4 * B * s.lay.A)) return GNF_EWS;
+  const size_t smem = (size_t)lds_bytes(s.lay, TB, lds);
+  float* w = (float*)ws;
+  switch (TB) {
+    case 4: return launch<4>(s, lds, smem, grid, st, pack, context, z, x, h_out, t0, t1, normalizer_mode, w, B, pin);
+    case 8: return launch<8>(s, lds, smem, grid, st, pack, context, z, x, h_out, t0, t1, normalizer_mode, w, B, pin);
+    default: return launch<16>(s, lds, smem, grid, st, pack, context, z, x, h_out, t0, t1, normalizer_mode, w, B, pin);
+  }
 }
 
 }  // namespace
@@ -152,46 +243,16 @@ int64_t gnf_made_prefix_ctx_ws_bytes(const gnf_made_net* net, int cond_in, int64
 int gnf_made_prefix_ctx_spline(const gnf_made_net* net, int cond_in, const float* context, const float* pack, const float* z,
                                float* x, float* h_out, int t0, int t1, int normalizer_mode, int spline_bins, double spline_tail,
                                int64_t B, void* ws, int64_t ws_bytes, gnf_stream_t stream) {
-  StepArgs s;
-  const int rc = make_layout(net, cond_in, &s.lay);
-  if (rc) return rc;
-  if (B < 0 || t0 < 0 || t1 < t0 || t1 > net->d) return GNF_EINVAL;
-  if (normalizer_mode != GNF_MADE_NORM_NONE && normalizer_mode != GNF_MADE_NORM_AFFINE &&
-      normalizer_mode != GNF_MADE_NORM_SPLINE)
-    return GNF_EINVAL;
-  if (normalizer_mode == GNF_MADE_NORM_NONE && t1 > t0 + 1) return GNF_EINVAL;
-  if (normalizer_mode == GNF_MADE_NORM_AFFINE && net->out < 2) return GNF_ESHAPE;
-  if (normalizer_mode == GNF_MADE_NORM_SPLINE) {
-    if (spline_bins < kSplMinBins || spline_bins > kSplMaxBins || !(spline_tail > 0.) || !(spline_tail < 3.0e38))
-      return GNF_EINVAL;
-    if (net->out < 3 * spline_bins - 1) return GNF_ESHAPE;
-    s.spl_K = spline_bins;
-    s.spl_T = spline_tail;
-  }
-  if (B == 0 || t1 == t0) return 0;
-  if (!pack || !x || !net->var_of_step || (cond_in > 0 && !context)) return GNF_EINVAL;
-  if ((uintptr_t)pack & 15) return GNF_EINVAL;          // rows of the weight image are read as 16-byte quads (ld4)
-  if (normalizer_mode == GNF_MADE_NORM_NONE ? !h_out : !z) return GNF_EINVAL;
-  for (int l = 0; l < net->nh; ++l) {
-    if (!net->off[l]) return GNF_EINVAL;
-    s.off[l] = net->off[l];
-  }
-  s.var_of_step = net->var_of_step;
-  const int TB = tile_rows(net, B);
-  const int64_t grid = (B + TB - 1) / TB;
-  if (grid > 0x7fffffff) return GNF_ESHAPE;
-  // the whole inversion in one launch keeps the tile's activations in LDS; step launches hand them on through ws
-  const bool lds = t0 == 0 && t1 == net->d && lds_bytes(s.lay, TB, true) <= kLdsBytes;
-  if (lds_bytes(s.lay, TB, false) > kLdsBytes) return GNF_ESHAPE;
-  if (!lds && (!ws || ws_bytes < 4 * B * s.lay.A)) return GNF_EWS;
-  const size_t smem = (size_t)lds_bytes(s.lay, TB, lds);
-  hipStream_t st = (hipStream_t)stream;
-  float* w = (float*)ws;
-  switch (TB) {
-    case 4: return launch<4>(s, lds, smem, grid, st, pack, context, z, x, h_out, t0, t1, normalizer_mode, w, B);
-    case 8: return launch<8>(s, lds, smem, grid, st, pack, context, z, x, h_out, t0, t1, normalizer_mode, w, B);
-    default: return launch<16>(s, lds, smem, grid, st, pack, context, z, x, h_out, t0, t1, normalizer_mode, w, B);
-  }
+  return prefix_run(net, cond_in, context, pack, z, x, h_out, t0, t1, normalizer_mode, spline_bins, spline_tail, nullptr, B,
+                    ws, ws_bytes, stream);
+}
+
+// ... and with a pin table (do(x_P = v)): pin == NULL is the call above
+int gnf_made_prefix_do(const gnf_made_net* net, int cond_in, const float* context, const float* pack, const float* z, float* x,
+                       float* h_out, int t0, int t1, int normalizer_mode, int spline_bins, double spline_tail,
+                       const uint8_t* pin, int64_t B, void* ws, int64_t ws_bytes, gnf_stream_t stream) {
+  return prefix_run(net, cond_in, context, pack, z, x, h_out, t0, t1, normalizer_mode, spline_bins, spline_tail, pin, B, ws,
+                    ws_bytes, stream);
 }
 
 // the entry points from before the spline: the same code, any mode but NONE / AFFINE refused as ever

@@ -309,17 +309,23 @@ def made_prefix_workspace(params, plan, batch):
 
 
 @torch.no_grad()
-def made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=None, ws=None, context=None, spline=None):
+def made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=None, ws=None, context=None, spline=None, pin=None):
     """Steps t0 <= t < t1 of the column-by-column inversion of a MADE step (gnf_made_prefix): z, x [B, d] fp32 contiguous.
     MADE_NORM_AFFINE writes column var_of_step[t] of x per step ((0, d): the whole inversion, one launch);
     MADE_NORM_NONE (t1 == t0 + 1) writes the conditioner outputs of that variable to h_out [B, out] and leaves the column
     to the caller.  ws (made_prefix_workspace): the same buffer for every call of one inversion; allocated here when a call
     that needs one comes without.  context: the contiguous fp32 [B, cond_in] device tensor of a conditional plan
     (gnf_made_prefix_ctx), None for cond_in == 0.  MADE_NORM_SPLINE takes spline = (nb_bins, tail_bound) and runs on the
-    gnf_made_prefix*_spline entry points (the others refuse that mode)."""
+    gnf_made_prefix*_spline entry points (the others refuse that mode).  pin: the contiguous uint8 [d] device table of an
+    intervention, one byte per VARIABLE, non-zero = pinned (gnf_made_prefix_do): a pinned step reads its column of x, which
+    the caller filled, and writes nothing; MADE_NORM_NONE may then span t1 > t0 + 1 steps whose all but the last are pinned
+    (the library checks that against the table, at the price of a stream synchronisation).  None: the calls above."""
     params = [p.detach() for p in params]
     net, c = _made_net(params, plan), _plan_cond_in(plan)
     B, d = x.shape
+    if pin is not None and (pin.dtype != torch.uint8 or pin.device != x.device or tuple(pin.shape) != (plan["d"],)
+                            or not pin.is_contiguous()):
+        raise abi.GnfError("made_prefix_steps: pin must be a contiguous uint8 [%d] tensor on the device of x" % plan["d"])
     if d != plan["d"] or not x.is_contiguous() or (z is not None and (tuple(z.shape) != (B, d) or not z.is_contiguous())):
         raise abi.GnfError("made_prefix_steps: z and x must be contiguous [B, %d]" % plan["d"])
     if h_out is not None and (tuple(h_out.shape) != (B, plan["out"]) or not h_out.is_contiguous()):
@@ -340,6 +346,10 @@ def made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=None, ws=Non
         if spline is None:
             raise abi.GnfError("made_prefix_steps: MADE_NORM_SPLINE needs spline = (nb_bins, tail_bound)")
         name, extra = name + "_spline", (int(spline[0]), float(spline[1]))
+    if pin is not None:
+        # the one entry point that supersets the others: (net, cond_in, context, ..., bins, tail, pin, ...)
+        name, head = "gnf_made_prefix_do", (ctypes.byref(net), c, None if c == 0 else ptr(context))
+        extra = (extra or (0, 0.)) + (ctypes.c_void_p(pin.data_ptr()),)
     args = lambda w: head + (ptr(pack), ptr(z), ptr(x), ptr(h_out), int(t0), int(t1), int(mode)) + extra + (
         B, None if w is None else ctypes.c_void_p(w.data_ptr()), 0 if w is None else w.numel() * 4, stream())
     if ws is None:

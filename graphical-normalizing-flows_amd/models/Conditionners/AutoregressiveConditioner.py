@@ -88,6 +88,21 @@ def made_prefix_plan(m, nin, nout):
             "var_of_step": np.argsort(deg_in, kind="stable").astype(np.int32), "max_new": max_new}
 
 
+def made_do_launches(var_of_step, pinned):
+    """The NONE-mode launches (t0, t1) of a column sweep under do(x_pinned): one per FREE variable, in degree order, each
+    starting behind the previous one's column -- so the run of pinned degrees in front of a free column is walked inside
+    the launch that computes that column's outputs (step t1 - 1 free, every step of [t0, t1 - 1) pinned: what
+    gnf_made_prefix_do demands of such a call) -- and nothing for a trailing run of pinned degrees, which no column
+    reads.  Pure host logic: var_of_step[t] = the variable of degree t, pinned = the pinned variables."""
+    pinned = set(int(v) for v in pinned)
+    out, t0 = [], 0
+    for t, v in enumerate(var_of_step):
+        if int(v) not in pinned:
+            out.append((t0, t + 1))
+            t0 = t + 1
+    return out
+
+
 class MADE(nn.Module):
     """Masked autoencoder, reference AutoregressiveConditioner.py:28-109: natural ordering (`random=False`, what the
     conditioner builds) or sampled orderings (`random=True`), cycling through `num_masks` seeds on update_masks().  Every
@@ -263,14 +278,16 @@ class AutoregressiveConditioner(Conditioner):
     def prefix_workspace(self, batch):
         return ops.made_prefix_workspace(self._prefix_params(), self.prefix_plan(with_context=bool(self.cond_in)), batch)
 
-    def prefix_steps(self, z, x, t0, t1, mode, h_out=None, ws=None, context=None, spline=None):
+    def prefix_steps(self, z, x, t0, t1, mode, h_out=None, ws=None, context=None, spline=None, pin=None):
         """steps t0 <= t < t1 of the plan on the HIP prefix kernel (gnf_hip.ops.made_prefix_steps); `context`: the checked
         [B, cond_in] context of a conditional conditioner (the plan is then prefix_plan(with_context=True)); `spline`:
-        (nb_bins, tail_bound) for ops.MADE_NORM_SPLINE"""
+        (nb_bins, tail_bound) for ops.MADE_NORM_SPLINE; `pin`: the uint8 [d] pin table, by variable, of an intervention
+        (gnf_made_prefix_do: a pinned step reads its column of x)"""
         plan, params = self.prefix_plan(with_context=bool(self.cond_in)), self._prefix_params()
         pack = self._held_prefix if self._held_prefix is not None else ops.made_prefix_pack(params, plan)
         return ops.made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=h_out, ws=ws, context=context,
-                                     **({} if spline is None else {"spline": spline}))
+                                     **({} if spline is None else {"spline": spline}),
+                                     **({} if pin is None else {"pin": pin}))
 
     # -- the adjoint of that sweep (NormalizingFlowStep.rsample's backward) -------------------------------------------------
     _held_adjoint = None

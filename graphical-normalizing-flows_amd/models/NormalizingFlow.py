@@ -23,9 +23,52 @@ from .Normalizers import Normalizer, AffineNormalizer, SplineNormalizer
 _INV_GRAPHS = weakref.WeakKeyDictionary()
 
 
+def _crop_order(host_rows):
+    """the variables of one level of a 28 x 28 image in the order the sparse embedding kernels work in: crop origin, pixel"""
+    return tuple(sorted(host_rows, key=lambda r: (8 * ops.crop_origin(r // 28) + ops.crop_origin(r % 28), r)))
+
+
 def _is_dag(conditioner):
     # exact type test, as everywhere in the reference (subclasses are deliberately not recognised)
     return type(conditioner) is DAGConditioner
+
+
+_SINGLE_STEP = ("%s: an intervention is defined on the data-side equations x_i = T^-1(z_i; h_i(x_pa(i), context)) of a "
+                "ONE-step flow; the intermediate variables of a stacked or multi-scale flow are not the x_i (this flow has "
+                "%d steps)")
+
+
+def do_arguments(do_index, do_value, z):
+    """(pinned variables as a tuple of ints, their values as a [B, S] tensor like z) of an intervention on z [B, d]:
+    do_index a sequence of ints or an integer tensor [S], unique and in range; do_value a float, [S] or [B, S].
+    ValueError otherwise."""
+    if z.dim() != 2:
+        raise ValueError("intervene: z must be [B, d], got %s" % (tuple(z.shape),))
+    B, d = z.shape
+    if torch.is_tensor(do_index):
+        if (do_index.dim() != 1 or do_index.dtype.is_floating_point or do_index.dtype.is_complex
+                or do_index.dtype == torch.bool):
+            raise ValueError("intervene: do_index must be a sequence of ints or an integer tensor [S]")
+        idx = tuple(int(i) for i in do_index.tolist())
+    else:
+        idx = tuple(do_index)
+        if any(isinstance(i, bool) or not isinstance(i, int) for i in idx):
+            raise ValueError("intervene: do_index must be a sequence of ints or an integer tensor [S]")
+    if any(i < 0 or i >= d for i in idx):
+        raise ValueError("intervene: do_index %s out of range for d = %d" % (list(idx), d))
+    if len(set(idx)) != len(idx):
+        raise ValueError("intervene: do_index %s names a variable twice" % (list(idx),))
+    S = len(idx)
+    if torch.is_tensor(do_value) and do_value.dim() > 0:
+        if tuple(do_value.shape) not in ((S,), (B, S)):
+            raise ValueError("intervene: do_value must be a float, [S] or [B, S] = [%d, %d], got %s"
+                             % (B, S, tuple(do_value.shape)))
+        vals = do_value.detach().to(device=z.device, dtype=z.dtype).expand(B, S).contiguous()
+    elif torch.is_tensor(do_value) or isinstance(do_value, (int, float)):
+        vals = torch.full((B, S), float(do_value), dtype=z.dtype, device=z.device)
+    else:
+        raise ValueError("intervene: do_value must be a float, [S] or [B, S], got %r" % (type(do_value),))
+    return idx, vals
 
 
 class NormalizingFlow(nn.Module):
@@ -43,6 +86,14 @@ class NormalizingFlow(nn.Module):
 
     def rsample(self, z, context=None):
         """invert(z, context) as a differentiable function of z, the context and the parameters"""
+        raise NotImplementedError
+
+    def intervene(self, z, do_index, do_value, context=None):
+        """x under do(x[:, do_index] = do_value): the pinned equations replaced by constants, every other one kept"""
+        raise NotImplementedError
+
+    def counterfactual(self, x, do_index, do_value, context=None):
+        """what the observation x would have been under do(x[:, do_index] = do_value): abduct z = forward(x), intervene"""
         raise NotImplementedError
 
     def getConditioners(self):
@@ -118,9 +169,7 @@ class NormalizingFlowStep(NormalizingFlow):
             if lv is not None and cond.A.shape[0] == 784:
                 # the order of the variables INSIDE a level is free: take the one the sparse embedding kernels work in (crop
                 # origin, then pixel), so that their output needs no un-sorting gather
-                lv = [(torch.as_tensor(sorted(hr, key=lambda r: (8 * ops.crop_origin(r // 28) + ops.crop_origin(r % 28), r)),
-                                       dtype=torch.long, device=rows.device),
-                       tuple(sorted(hr, key=lambda r: (8 * ops.crop_origin(r // 28) + ops.crop_origin(r % 28), r))))
+                lv = [(torch.as_tensor(_crop_order(hr), dtype=torch.long, device=rows.device), _crop_order(hr))
                       for rows, hr in lv]
             self._levels_val = lv
             self._levels_all = torch.cat([rows for rows, _ in lv]) if lv else None   # one gather of z per pass
@@ -129,17 +178,18 @@ class NormalizingFlowStep(NormalizingFlow):
             _INV_GRAPHS.pop(self, None)                 # graphs captured for another gate replay another schedule
         return self._levels_val, key
 
-    def _invert_levels_body(self, z, levels, importance, context):
+    def _invert_levels_body(self, z, levels, importance, context, x=None, tables=None):
         """variable-major inside: z is gathered ONCE into [sum of level sizes, B] (a level is a contiguous slice), the
         conditioner rows come as [R, B, out] -- the layout the sparse kernels write -- and the normalizer's inverse is
         element-wise in whatever two leading dimensions z and h share.  Per level that leaves the embedding front, the
         inverse and one scatter into x (no gather of z, no un-sorting or permuting copy of h)."""
         cond = self.conditioner
-        x = torch.zeros_like(z)
-        zt = z.t()[self._levels_all]                    # [sum R, B], contiguous
+        # (intervene() brings its own x, pinned columns filled, and the (all rows, int32 rows) tables of its own schedule)
+        x = torch.zeros_like(z) if x is None else x
+        zt = z.t()[self._levels_all if tables is None else tables[0]]         # [sum R, B], contiguous
         off = 0
         into = getattr(self.normalizer, "inverse_transform_into", None)       # (the normalizers ignore the context)
-        rows32 = getattr(self, "_levels_rows32", None)
+        rows32 = getattr(self, "_levels_rows32", None) if tables is None else tables[1]
         if into is not None and (rows32 is None or len(rows32) != len(levels)):
             into = None
         for k, (rows, host_rows) in enumerate(levels):
@@ -340,6 +390,191 @@ class NormalizingFlowStep(NormalizingFlow):
                     break
         return x
 
+    # -- interventions ------------------------------------------------------------------------------------------
+    DO_LEVELS_MAX = 8                    # mutilated level schedules kept per step (pinned tuples of one gate)
+
+    def _do_levels(self, importance, idx):
+        """(levels, (all rows, int32 rows per level)) of the MUTILATED graph of do(x_idx): the pinned variables lose their
+        parents (their rows of the importance matrix zeroed) and leave the level lists; levels that held only pinned
+        variables vanish.  None for a cyclic graph.  Cached beside -- never in -- invert's `_levels_*` attributes, on the
+        key of `_levels` plus the pinned tuple; a trainable A caches nothing, as there."""
+        cond = self.conditioner
+        key = (None if cond.A.requires_grad else
+               (cond.A.data_ptr(), cond.A._version, float(cond.h_thresh), bool(cond.s_thresh), cond.A.device,
+                getattr(cond, "_cache_epoch", 0), tuple(sorted(idx))))
+        cache = self.__dict__.setdefault("_do_levels_cache", {})
+        if key is not None and key in cache:
+            return cache[key]
+        cut = importance.detach().clone()
+        cut[list(idx)] = 0
+        lv = cond.levels(cut, with_host=True)
+        entry = None
+        if lv is not None:
+            pinned, out = set(idx), []
+            for rows, host in lv:
+                keep = tuple(r for r in host if r not in pinned)
+                if cond.A.shape[0] == 784:              # the order inside a level that the sparse embedding kernels work in
+                    keep = _crop_order(keep)
+                if keep:
+                    out.append((rows if len(keep) == len(host) and cond.A.shape[0] != 784 else
+                                torch.as_tensor(keep, dtype=torch.long, device=rows.device), keep))
+            tables = ((torch.cat([rows for rows, _ in out]), [rows.to(torch.int32) for rows, _ in out]) if out else
+                      (None, None))
+            entry = (out, tables)
+        if key is not None:
+            if len(cache) >= self.DO_LEVELS_MAX:
+                cache.clear()
+            cache[key] = entry
+        return entry
+
+    def _intervene_by_levels(self, z, idx, vals, context):
+        """DAG conditioner, deterministic gate: the level schedule of the mutilated graph.  x[:, idx] = vals is written
+        before the first level, then `_invert_levels_body` runs on the remaining rows -- fewer conditioner rows and no
+        more levels than invert needs.  Launch by launch: no graph is captured, and invert's cache and its captured
+        graphs are not touched.  Returns None when not applicable (the conditions of `_invert_by_levels`)."""
+        cond = self.conditioner
+        if not (_is_dag(cond) and self.level_schedule):
+            return None
+        cond_in = int(getattr(cond, "cond_in", 0) or 0)
+        if not cond_in and context is not None:
+            return None
+        if cond_in:
+            context = checked_context(context, cond_in, z)
+            if z.dim() != 2 or context.device != z.device or context.dtype != z.dtype:
+                return None
+        importance = cond.deterministic_importance()
+        if importance is None:
+            return None
+        if idx:
+            entry = self._do_levels(importance, idx)
+            if entry is None:
+                return None
+            levels, tables = entry
+        else:                                           # P empty: invert's own schedule, read as invert reads it
+            levels, _ = self._levels(importance)
+            if levels is None:
+                return None
+            tables = None
+        x = torch.zeros_like(z)
+        if idx:
+            x[:, list(idx)] = vals
+        if z.shape[0] == 0 or not levels:
+            return x
+        return self._invert_levels_body(z, levels, importance, context, x=x, tables=tables)
+
+    def _intervene_by_columns(self, z, idx, vals, context):
+        """MADE conditioner: the column sweep with a pin table (gnf_made_prefix_do).  x[:, idx] = vals is written first; a
+        pinned step reads its column instead of computing it.  Affine / Spline + MADE stay ONE launch; any other normalizer
+        is stepped through AutoregressiveConditioner.made_do_launches: one launch per FREE column, which advances through
+        the run of pinned degrees in front of it, and none for a trailing run.  Returns None when not applicable (the
+        conditions of `_invert_by_columns`)."""
+        from .Conditionners.AutoregressiveConditioner import made_do_launches
+        cond = self.conditioner
+        get_plan = getattr(cond, "prefix_plan", None)
+        if not (self.column_schedule and get_plan is not None and z.is_cuda and z.dim() == 2
+                and z.dtype == torch.float32):
+            return None
+        cond_in = int(getattr(cond, "cond_in", 0) or 0)
+        if not cond_in and context is not None:
+            return None
+        if cond_in:
+            context = checked_context(context, cond_in, z)
+            if context.device != z.device or context.dtype != torch.float32:
+                return None
+        if z.shape[0] == 0:
+            return torch.zeros_like(z)
+        plan = get_plan(with_context=True) if cond_in else get_plan()
+        if plan is None or plan["d"] != z.shape[1]:
+            return None
+        kw = {"context": context.contiguous()} if cond_in else {}
+        z = z.contiguous()
+        x = torch.zeros_like(z)
+        B, d, out = z.shape[0], plan["d"], plan["out"]
+        if idx:
+            x[:, list(idx)] = vals
+            if len(idx) == d:
+                return x                                # every degree is a trailing pinned one: no launch
+            pin = torch.zeros(d, dtype=torch.uint8, device=z.device)
+            pin[list(idx)] = 1
+            kw["pin"] = pin
+        with cond.hold_prefix_pack():
+            if type(self.normalizer) is AffineNormalizer:
+                cond.prefix_steps(z, x, 0, d, ops.MADE_NORM_AFFINE, **kw)
+                return x
+            if type(self.normalizer) is SplineNormalizer:
+                cond.prefix_steps(z, x, 0, d, ops.MADE_NORM_SPLINE, spline=(self.normalizer.nb_bins, self.normalizer.tail_bound),
+                                  **kw)
+                return x
+            h = torch.empty(B, out, dtype=torch.float32, device=z.device)
+            ws = cond.prefix_workspace(B)
+            zt = z.t().contiguous()
+            cols = torch.arange(d, dtype=torch.int32, device=z.device)
+            into = getattr(self.normalizer, "inverse_transform_into", None)
+            for t0, t1 in made_do_launches(plan["var_host"], idx):
+                v = plan["var_host"][t1 - 1]            # the launch's one free column, behind t1 - 1 - t0 pinned ones
+                cond.prefix_steps(z, x, t0, t1, ops.MADE_NORM_NONE, h_out=h, ws=ws, **kw)
+                if into is None or not into(zt[v:v + 1], h.view(1, B, out), x, cols[v:v + 1]):
+                    x[:, v:v + 1] = self.normalizer.inverse_transform(z[:, v:v + 1], h.view(B, 1, out), context)
+        return x
+
+    def _refuse_stochastic_gate(self):
+        cond = self.conditioner
+        if _is_dag(cond) and cond.deterministic_importance() is None:
+            raise ValueError("NormalizingFlowStep.intervene: the DAG conditioner's gate is stochastic (stoch_gate / noise_gate); "
+                             "every evaluation of the conditioner would draw another graph than the one the intervention "
+                             "cuts.  Use a deterministic gate (stoch_gate = noise_gate = False)")
+
+    def intervene(self, z, do_index, do_value, context=None):
+        """x under do(x[:, do_index] = do_value) (interventions):  x[b, i] = do_value[b, i] exactly for a pinned
+        i, x[b, i] = normalizer^-1(z[b, i], conditioner(x, context)[b, i]) for every other; z[:, do_index] is ignored.  An
+        empty do_index is invert(z, context), bit for bit.  Three arms on invert's conditions (`level_schedule`,
+        `column_schedule`), recorded in `_intervene_arm`: "levels" (DAG), "columns" (MADE), "passes" (anything, anywhere:
+        x <- where(pinned, v, normalizer^-1(z, conditioner(x))) from where(pinned, v, 0), depth() + 1 passes of the
+        un-mutilated graph -- the mutilated one is never deeper -- with invert's early exit).
+
+        A DAG conditioner with a stochastic or noisy gate is refused as rsample refuses it: every pass and every level
+        would draw another graph to mutilate."""
+        import contextlib
+        cond = self.conditioner
+        self._refuse_stochastic_gate()
+        idx, vals = do_arguments(do_index, do_value, z)
+        self._intervene_arm = None
+        with torch.no_grad(), contextlib.ExitStack() as stack:
+            for _, _, make in self._holders():
+                stack.enter_context(make())
+            x = self._intervene_by_levels(z, idx, vals, context)
+            if x is not None:
+                self._intervene_arm = "levels"
+                return x
+            x = self._intervene_by_columns(z, idx, vals, context)
+            if x is not None:
+                self._intervene_arm = "columns"
+                return x
+            self._intervene_arm = "passes"
+            cols = list(idx)
+            x = torch.zeros_like(z)
+            if cols:
+                x[:, cols] = vals
+            if len(cols) == z.shape[1]:
+                return x                                # no free equation: the conditioner is never asked
+            for _ in range(cond.depth() + 1):
+                previous = x
+                x = self.normalizer.inverse_transform(z, cond(x, context), context)
+                if cols:
+                    x[:, cols] = vals
+                if torch.equal(x, previous):
+                    break
+        return x
+
+    def counterfactual(self, x, do_index, do_value, context=None):
+        """abduction, then action: z = forward(x, context), then intervene(z, ...).  No column is copied from x: what a
+        non-descendant of the pinned variables comes back as is the inversion's own residual."""
+        self._refuse_stochastic_gate()
+        do_arguments(do_index, do_value, x)             # (the argument errors before the abduction's launches)
+        with torch.no_grad():
+            z, _ = self.forward(x, context)
+        return self.intervene(z, do_index, do_value, context)
+
     # -- differentiable sampling --------------------------------------------------------------------------------
     def rsample(self, z, context=None):
         """x = invert(z, context) -- the same kernels, the same bits -- with gradients for z, the context and the step's
@@ -476,6 +711,19 @@ class FCNormalizingFlow(NormalizingFlow):
             z = torch.flip(x, dims=[1]) if k else x
         return z
 
+    def _single_step(self, what):
+        if len(self.steps) != 1:
+            raise ValueError(_SINGLE_STEP % (type(self).__name__ + "." + what, len(self.steps)))
+        return self.steps[0]
+
+    def intervene(self, z, do_index, do_value, context=None):
+        """the single step's intervene; ValueError for a flow of several steps"""
+        return self._single_step("intervene").intervene(z, do_index, do_value, context)
+
+    def counterfactual(self, x, do_index, do_value, context=None):
+        """the single step's counterfactual; ValueError for a flow of several steps"""
+        return self._single_step("counterfactual").counterfactual(x, do_index, do_value, context)
+
 
 class CNNormalizingFlow(FCNormalizingFlow):
     """Multi-scale image flow (reference :172-226): after every scale the image is cut into d_c x d_h x d_w blocks;
@@ -538,3 +786,11 @@ class CNNormalizingFlow(FCNormalizingFlow):
     def rsample(self, z, context=None):
         raise NotImplementedError("CNNormalizingFlow.rsample: differentiable sampling of the multi-scale image flow is not "
                                   "implemented (the flat FCNormalizingFlow.rsample does not apply to it)")
+
+    def intervene(self, z, do_index, do_value, context=None):
+        raise ValueError(_SINGLE_STEP % ("CNNormalizingFlow.intervene", len(self.steps)) + "; a multi-scale flow has none "
+                         "of one step's equations even with a single scale: its latent is cut and re-interleaved")
+
+    def counterfactual(self, x, do_index, do_value, context=None):
+        raise ValueError(_SINGLE_STEP % ("CNNormalizingFlow.counterfactual", len(self.steps)) + "; a multi-scale flow has "
+                         "none of one step's equations even with a single scale: its latent is cut and re-interleaved")

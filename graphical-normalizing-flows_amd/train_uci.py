@@ -11,6 +11,10 @@ Opt-in: `-device_batches` gathers the training batches on the device through a P
 and every batch is split into (x, context) -- behind the gather when the batches come from the device.
 `-sample N` (after the last evaluation) draws N samples x ~ p(x | context of the first N test rows) through model.invert into
 `samples.npy` in -folder and prints the mean |z - forward(x, ctx)| (sample_rows).
+`-do COL=VALUE [COL=VALUE ...]` (with -sample N) draws N INTERVENTIONAL samples as well, from the same z and contexts, through
+model.intervene into `samples_do.npy`, and prints the mean |z - forward(x, ctx)| over the un-pinned columns and the
+per-column mean shift against the un-intervened samples (sample_do_rows).  One-step flows only: -nb_flow > 1 ends with the
+model's ValueError, reported.
 
 Checkpoints: `model.pt` is `state_dict()` with the reference's keys, `ADAM.pt` is in torch.optim.Adam's format, so
 either side can resume the other's run."""
@@ -132,6 +136,51 @@ def sample_rows(model, tst, n, context_cols, seed, folder, say=print):
     np.save(os.path.join(folder, "samples.npy"), out.cpu().numpy())
     say("samples: %d rows -> %s - mean |z - forward(x)|: %.3e" % (out.shape[0], os.path.join(folder, "samples.npy"), err))
     return err
+
+
+def parse_do(pairs, d):
+    """-do COL=VALUE ... -> ([columns], [values]); ValueError for anything else (a column twice or outside 0 .. d - 1 is
+    left to model.intervene, which says it better)"""
+    cols, vals = [], []
+    for item in pairs:
+        col, sep, val = str(item).partition("=")
+        try:
+            if not sep:
+                raise ValueError
+            cols.append(int(col))
+            vals.append(float(val))
+        except ValueError:
+            raise ValueError("-do %r: expected COL=VALUE with an integer column of the %d modelled ones and a number"
+                             % (item, d)) from None
+    return cols, vals
+
+
+@torch.no_grad()
+def sample_do_rows(model, tst, n, context_cols, seed, folder, do, say=print):
+    """-sample N -do COL=VALUE ...: x ~ p(x | do(x_COL = VALUE), c) for the z and the contexts sample_rows uses, through
+    model.intervene.  Writes samples_do.npy ([N, modelled columns + context columns]); reports the mean |z - forward(x, ctx)|
+    over the UN-pinned columns (a pinned column's z is not the one drawn) and the per-column mean of x_do - x against the
+    un-intervened samples of the same z.  Returns (that mean, the shifts as a list)."""
+    import numpy as np
+    rows = tst[:n]
+    _, ctx = split_context(rows, context_cols)
+    d = rows.shape[1] - context_cols
+    cols, vals = parse_do(do, d)
+    z = torch.randn(rows.shape[0], d, generator=torch.Generator().manual_seed(int(seed))).to(rows.device)
+    value = torch.tensor(vals, dtype=z.dtype, device=z.device)
+    x = model.intervene(z, cols, value) if ctx is None else model.intervene(z, cols, value, ctx)
+    base = model.invert(z) if ctx is None else model.invert(z, ctx)
+    zz = (model(x) if ctx is None else model(x, ctx))[0]
+    free = [i for i in range(d) if i not in cols]
+    err = float((z - zz)[:, free].abs().mean()) if z.shape[0] and free else 0.
+    shift = (x - base).mean(0).tolist() if z.shape[0] else [0.] * d
+    out = x if ctx is None else torch.cat((x, ctx), 1)
+    os.makedirs(folder, exist_ok=True)
+    np.save(os.path.join(folder, "samples_do.npy"), out.cpu().numpy())
+    say("samples under do(%s): %d rows -> %s - mean |z - forward(x)| over the un-pinned columns: %.3e"
+        % (", ".join("x%d = %g" % cv for cv in zip(cols, vals)), out.shape[0], os.path.join(folder, "samples_do.npy"), err))
+    say("mean shift per column against the un-intervened samples: " + " ".join("%+.4f" % s for s in shift))
+    return err, shift
 
 
 THRESHOLDS = (.95, .5, .1, .01, .0001)
@@ -293,10 +342,19 @@ def train(args):
             torch.save(model.state_dict(), os.path.join(args.folder, "model.pt"))
             torch.save(state.optimizer_state_dict(model, args.learning_rate, args.weight_decay),
                        os.path.join(args.folder, "ADAM.pt"))
+    refused = False
     if getattr(args, "sample", 0) > 0 and rank == 0:
         sample_rows(model, tst, args.sample, ctx_cols, args.seed, args.folder, say)
+        if getattr(args, "do", None):
+            try:
+                sample_do_rows(model, tst, args.sample, ctx_cols, args.seed, args.folder, args.do, say)
+            except ValueError as exc:                        # a multi-step flow, a column twice or out of range
+                say("-do: %s" % exc)
+                refused = True
     if world > 1:
-        dist.destroy_process_group()
+        dist.destroy_process_group()                         # (before the exit below: the other ranks wait in it)
+    if refused:
+        raise SystemExit(2)
     return model
 
 
@@ -353,6 +411,8 @@ def parse(argv=None):
                     help="the last K columns of the data are the context of a conditional flow over the others (cond_in = K)")
     ap.add_argument("-sample", default=0, type=int,
                     help="after the last evaluation: N samples x ~ p(x | context of the first N test rows) into samples.npy")
+    ap.add_argument("-do", default=None, nargs="+", metavar="COL=VALUE",
+                    help="with -sample N: N samples under the intervention do(x_COL = VALUE, ...) into samples_do.npy")
     args = ap.parse_args(argv)
     if args.load_config is not None:                         # a named entry of the yml overrides the command line
         with open(args.config_file) as f:
@@ -367,6 +427,8 @@ def parse(argv=None):
         ap.error("-sample must not be negative")
     if args.context_cols < 0:
         ap.error("-context_cols must not be negative")
+    if args.do and args.sample <= 0:
+        ap.error("-do needs -sample N (the interventional samples are drawn from the z of the plain ones)")
     if args.steps_per_replay > 1 and not args.device_batches:
         ap.error("-steps_per_replay needs -device_batches (a replayed group reads its batches from device memory)")
     if not args.folder:

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-/* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_*, gnf_image_prep, gnf_dagmlp_*, gnf_dag_levels*, gnf_toy_sample, gnf_shuffle_keys, gnf_tab_batch, gnf_group_bias_*, gnf_spline_* and gnf_made_prefix*_spline were ADDED under this number (no existing symbol
+/* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_*, gnf_image_prep, gnf_dagmlp_*, gnf_dag_levels*, gnf_toy_sample, gnf_shuffle_keys, gnf_tab_batch, gnf_group_bias_*, gnf_spline_*, gnf_made_prefix*_spline and gnf_made_prefix_do were ADDED under this number (no existing symbol
  * changed; a binding written against the earlier 11 keeps working, and tests/test_cifar_factory.py pins the value) */
 #define GNF_ABI_VERSION 11
 #define GNF_EINVAL (-1)   /* bad argument (null pointer, negative size, ...)          */
@@ -423,6 +423,26 @@ int gnf_made_prefix_spline(const gnf_made_net* net, const float* pack, const flo
 int gnf_made_prefix_ctx_spline(const gnf_made_net* net, int cond_in, const float* context, const float* pack, const float* z,
                                float* x, float* h_out, int t0, int t1, int normalizer_mode, int spline_bins, double spline_tail,
                                int64_t B, void* ws, int64_t ws_bytes, gnf_stream_t stream);
+/* gnf_made_prefix_ctx_spline with a pin table: the column sweep of an intervention do(x_P = v)
+ * (NormalizingFlowStep.intervene).  pin: [d] bytes on the device, one per VARIABLE (not per step), non-zero = pinned; any
+ * address (bytes are read one by one).  pin == NULL IS gnf_made_prefix_ctx_spline: the same kernel, the same bits.
+ *   A pinned step t (v = var_of_step[t], pin[v] != 0) READS x[b, v], which the caller filled before the call, as the
+ *   input of the later steps; it writes neither x nor h_out and computes neither the outputs of v nor its inverse (z[b, v]
+ *   is not read).  The hidden units of degree t - 1 are computed as ever: later columns need them.  An un-pinned step is
+ *   the step of the entry points above.  (0, d) calls, with the tile in LDS or through ws, take pins like any other.
+ *   GNF_MADE_NORM_NONE: t1 > t0 + 1 is allowed when every step of [t0, t1 - 1) is pinned: the launch advances through the
+ *   run and writes h_out for step t1 - 1 alone -- nothing when that step is pinned as well.  An un-pinned step inside the
+ *   run is GNF_EINVAL.  That check lives HERE, not with the caller: this one form of the call copies the table and the
+ *   run's var_of_step entries to the host and waits for the stream (so it cannot be captured into a graph); every other
+ *   form is asynchronous as before.  Step launches still load x[:, var_of_step[t0 - 1]] into ws, pinned or inverted.
+ *   h_out (NONE) and z (AFFINE / SPLINE) must be non-NULL as above even when every step of the call is pinned; B == 0 or
+ *   t1 == t0 returns 0 before any pointer is dereferenced -- except that NONE with t1 > t0 + 1 and pin == NULL is
+ *   GNF_EINVAL whatever B (the refusal of the entry points above, which comes first); pin != NULL with B > 0 and
+ *   x == NULL is GNF_EINVAL. */
+int gnf_made_prefix_do(const gnf_made_net* net, int cond_in, const float* context, const float* pack, const float* z, float* x,
+                       float* h_out, int t0, int t1, int normalizer_mode, int spline_bins, double spline_tail,
+                       const uint8_t* pin /* [d], by VARIABLE, device */, int64_t B, void* ws, int64_t ws_bytes,
+                       gnf_stream_t stream);
 
 /* ---- MADE adjoint sweep: lambda with J^T lambda = g for one MADE step (NormalizingFlowStep.rsample's backward) ----------
  * The step is z = S(x; context): h = MADE(context, x), z[b, i] = normalizer(x[b, i], h[b, i, :]).  In degree order
