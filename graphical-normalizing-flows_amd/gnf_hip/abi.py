@@ -62,6 +62,14 @@ SIGNATURES = {
     "gnf_normal_logdensity_bwd": (c_int, [c_f, c_f, c_f, c_i64, c_i64, c_stream]),
     "gnf_nll_reduce_fwd": (c_int, [c_f, c_f, c_f, c_f, c_i64, c_i64, c_stream]),
     "gnf_nll_reduce_bwd": (c_int, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i64, c_i64, c_stream]),
+    # (pin: uint8 [R, d], regime: int32 [B] or NULL -- device pointers of any dtype, ops passes them through rawptr)
+    "gnf_nll_do_fwd": (c_int, [c_f, c_f, ctypes.c_void_p, ctypes.c_void_p, c_i64, c_f, c_f, c_i64, c_i64, c_stream]),
+    "gnf_nll_do_bwd": (c_int, [c_f, c_f, ctypes.c_void_p, ctypes.c_void_p, c_i64, c_f, c_f, c_f, c_f, c_f, c_i64, c_i64,
+                               c_stream]),
+    "gnf_affine_do_fwd": (c_int, [c_f, c_f, c_i64, c_i64, c_i64, ctypes.c_void_p, ctypes.c_void_p, c_i64, c_f, c_f, c_f, c_f,
+                                  c_i64, c_i64, c_stream]),
+    "gnf_affine_do_bwd": (c_int, [c_f, c_f, c_i64, c_i64, c_i64, ctypes.c_void_p, ctypes.c_void_p, c_i64, c_f, c_f, c_f, c_f,
+                                  c_f, c_f, c_i64, c_i64, c_i64, c_i64, c_i64, c_stream]),
     "gnf_nll_mean_fwd": (c_int, [c_f, c_f, c_f, c_f, c_i64, c_stream]),
     "gnf_nll_mean_bwd": (c_int, [c_f, c_f, c_f, c_i64, c_stream]),
     "gnf_nll_loss_max_elems": (c_i64, []),

@@ -223,7 +223,8 @@ GRAPH_MAX_ELEMS = 1 << 18               # auto-replay only steps small enough to
                                         # elements; cfg5's 3.1 M-element step is GPU-bound and stages GiBs per capture)
 
 
-def train_step(flow, state, x_shard, lr=1e-3, weight_decay=1e-5, optimizer=hip_adam, graph="auto", context=None):
+def train_step(flow, state, x_shard, lr=1e-3, weight_decay=1e-5, optimizer=hip_adam, graph="auto", context=None, targets=None,
+               regime=None, check_regime=True):
     """fwd + log|det J| + NLL (+ constraints) + bwd on the local shard, one all-reduce, Adam.
     loss_rank = constraints - mean_local(log p); averaging over ranks gives the global mean.
 
@@ -232,9 +233,17 @@ def train_step(flow, state, x_shard, lr=1e-3, weight_decay=1e-5, optimizer=hip_a
     launch-by-launch path.  The returned loss tensor of a replayed step is reused by the next replay.
 
     context: the [rows of x_shard, cond_in] context of a conditional flow.  Such a step always runs launch by launch: a
-    captured step has one input buffer, and no GraphedStep is built for it."""
+    captured step has one input buffer, and no GraphedStep is built for it.
+
+    targets (and regime): the step minimises flow.loss_do(x_shard, targets, regime, context), the interventional likelihood
+    of a mix of observational and interventional rows (models.NormalizingFlow.do_targets).  `regime` holds the rows of THIS
+    rank's shard.  Launch by launch as with a context: no GraphedStep.  check_regime=False skips the range check of the regime
+    ids (one host synchronisation per step) for a caller that validated its data set once; a uint8 table and an int32 regime
+    vector already on the device then reach the kernels without a launch in between."""
     world = dist.get_world_size() if dist.is_initialized() else 1
-    if (graph and context is None and world == 1 and not collective_on() and optimizer is hip_adam and x_shard.is_cuda
+    if targets is None and regime is not None:
+        raise ValueError("train_step: a regime vector needs the [R, d] table of targets")
+    if (graph and context is None and targets is None and world == 1 and not collective_on() and optimizer is hip_adam and x_shard.is_cuda
             and x_shard.numel() <= GRAPH_MAX_ELEMS and torch.is_grad_enabled() and GraphedStep.graphable(flow)):
         gs = getattr(state, "_graphed", None)
         if gs is None or gs.flow is not flow or (gs.lr, gs.weight_decay) != (lr, weight_decay):
@@ -242,7 +251,7 @@ def train_step(flow, state, x_shard, lr=1e-3, weight_decay=1e-5, optimizer=hip_a
                                               owned_by_state=True)
             return gs.loss
         return gs(x_shard)
-    loss = accumulate(flow, x_shard, context=context)
+    loss = accumulate(flow, x_shard, context=context, targets=targets, regime=regime, check_regime=check_regime)
     apply_step(state, lr, weight_decay, optimizer)
     return loss
 
@@ -258,13 +267,19 @@ def _one(like):
     return _ONES[key]
 
 
-def accumulate(flow, x_shard, scale=1., context=None):
+def accumulate(flow, x_shard, scale=1., context=None, targets=None, regime=None, check_regime=True):
     """fwd + log|det J| + NLL (+ constraints) + bwd of ONE micro-batch; gradients add up in `.grad` until apply_step().
     The image driver's gradient accumulation (ImageExperiments.py:205-213: loss / batch_per_optim_step, backward on
     every batch, optimiser every k-th) is k calls with scale = 1/k followed by one apply_step.  context: the micro-batch's
-    rows of the context of a conditional flow (cond_in > 0)."""
-    z, logdet = flow(x_shard) if context is None else flow(x_shard, context)
-    loss = flow.loss(z, logdet)
+    rows of the context of a conditional flow (cond_in > 0).  targets / regime: the loss is flow.loss_do(x_shard, targets,
+    regime, context) -- the micro-batch's own regime rows."""
+    if targets is None and regime is not None:
+        raise ValueError("accumulate: a regime vector needs the [R, d] table of targets")
+    if targets is not None:
+        loss = flow.loss_do(x_shard, targets, regime, context, check_regime)
+    else:
+        z, logdet = flow(x_shard) if context is None else flow(x_shard, context)
+        loss = flow.loss(z, logdet)
     if scale != 1.:
         loss = loss * scale
     loss.backward(_one(loss) if loss.dim() == 0 else None)

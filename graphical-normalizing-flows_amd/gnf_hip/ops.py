@@ -506,6 +506,98 @@ class NllReduceFn(torch.autograd.Function):
         return gz, gjac
 
 
+# ----------------------------------------------------------------------------- interventional likelihood
+def _do_table(pin, regime, like):
+    """(pin pointer, regime pointer or None, R) of a checked mask table for the masked reductions: pin uint8 [R, d] and
+    regime int32 [B] or None, contiguous, on the device of `like` (models.NormalizingFlow.do_targets makes them)"""
+    B, d = like.shape
+    if pin.dtype != torch.uint8 or pin.dim() != 2 or pin.shape[1] != d or not pin.is_contiguous() or pin.device != like.device:
+        raise ValueError("pin must be a contiguous uint8 [R, %d] table on %s, got %s %s on %s"
+                         % (d, like.device, pin.dtype, tuple(pin.shape), pin.device))
+    R = pin.shape[0]
+    if regime is None:
+        if R != 1 and R != B:
+            raise ValueError("pin has %d rows: without a regime vector it must have 1 or B = %d" % (R, B))
+        return abi.rawptr(pin), None, R
+    if (regime.dtype != torch.int32 or tuple(regime.shape) != (B,) or not regime.is_contiguous()
+            or regime.device != like.device):
+        raise ValueError("regime must be a contiguous int32 [%d] vector on %s, got %s %s on %s"
+                         % (B, like.device, regime.dtype, tuple(regime.shape), regime.device))
+    return abi.rawptr(pin), abi.rawptr(regime), R
+
+
+class NllDoFn(torch.autograd.Function):
+    """NllReduceFn over the FREE variables only: (sum_free log jac, -.5 sum_free (log 2 pi + z^2)), the truncated
+    factorisation log p(x | do(x_S)) behind any normalizer's (z, jac).  pin [R, d] uint8 (non-zero: pinned), regime int32 [B]
+    or None (R = 1: one target set for the batch, R = B: a row per sample).  A pinned element's z and jac never enter a sum or
+    a cotangent; a regime id outside [0, R) gives NaN rows.  pin and regime carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, z, jac, pin, regime=None):
+        z, jac = z.contiguous(), jac.contiguous()
+        B, d = z.shape
+        ctx.set_materialize_grads(False)
+        p, r, R = _do_table(pin, regime, z)
+        logdet, logn = _empty((B,), z), _empty((B,), z)
+        call("gnf_nll_do_fwd", ptr(z), ptr(jac), p, r, R, ptr(logdet), ptr(logn), B, d, stream())
+        ctx.save_for_backward(z, jac, pin, *([] if regime is None else [regime]))
+        return logdet, logn
+
+    @staticmethod
+    def backward(ctx, glogdet, glogn):
+        z, jac, pin, *rest = ctx.saved_tensors
+        regime = rest[0] if rest else None
+        B, d = z.shape
+        p, r, R = _do_table(pin, regime, z)
+        gz, gjac = _empty((B, d), z), _empty((B, d), z)
+        call("gnf_nll_do_bwd", ptr(z), ptr(jac), p, r, R, ptr(glogdet.contiguous()) if glogdet is not None else None,
+             ptr(glogn.contiguous()) if glogn is not None else None, None, ptr(gz), ptr(gjac), B, d, stream())
+        return gz, gjac, None, None
+
+
+class AffineDoFn(torch.autograd.Function):
+    """AffineFn (without the in-place clamp) with log|det J| and the Normal log-density reduced over the FREE columns in the
+    pass that writes z: (z, jac, logdet, logn) under do(x_S).  z is written for every column -- a pinned column's z is
+    defined and unused --, the row cotangents of logdet / logn reach x and h through free elements only, those of z and jac
+    act on every element.  Both layouts of h (contiguous [B, d, 2], MADE's permuted view); gh comes back in h's format."""
+
+    @staticmethod
+    def forward(ctx, x, h, pin, regime=None, want_jac=False):
+        x = x.contiguous()
+        B, d = x.shape
+        ctx.set_materialize_grads(False)
+        if h.dim() != 3 or h.shape[0] != B or h.shape[1] != d or h.shape[2] < 2:
+            raise ValueError("AffineDoFn: h must be [%d, %d, >= 2], got %s" % (B, d, tuple(h.shape)))
+        p, r, R = _do_table(pin, regime, x)
+        z, logdet, logn = _empty((B, d), x), _empty((B,), x), _empty((B,), x)
+        jac = _empty((B, d), x) if want_jac else None
+        call("gnf_affine_do_fwd", ptr(x), ptr(h), h.stride(0), h.stride(1), h.stride(2), p, r, R, ptr(z), ptr(jac),
+             ptr(logdet), ptr(logn), B, d, stream())
+        ctx.save_for_backward(x, h, pin, *([] if regime is None else [regime]))
+        ctx.hshape = tuple(h.shape)
+        if jac is None:
+            jac = z.new_empty(0)
+            ctx.mark_non_differentiable(jac)
+        return z, jac, logdet, logn
+
+    @staticmethod
+    def backward(ctx, gz, gjac, glogdet, glogn):
+        x, h, pin, *rest = ctx.saved_tensors
+        regime = rest[0] if rest else None
+        B, d = x.shape
+        p, r, R = _do_table(pin, regime, x)
+        # same memory format as h so that e.g. MADE's permuted view flows back without a copy
+        gh = torch.empty_like(h) if ctx.hshape[2] == 2 else torch.zeros_like(h)
+        gx = _empty((B, d), x) if ctx.needs_input_grad[0] else None
+        call("gnf_affine_do_bwd", ptr(x), ptr(h), h.stride(0), h.stride(1), h.stride(2), p, r, R,
+             ptr(gz.contiguous()) if gz is not None else None,
+             ptr(gjac.contiguous()) if (gjac is not None and gjac.numel() > 0) else None,
+             ptr(glogdet.contiguous()) if glogdet is not None else None,
+             ptr(glogn.contiguous()) if glogn is not None else None,
+             ptr(gx), ptr(gh), gh.stride(0), gh.stride(1), gh.stride(2), B, d, stream())
+        return gx, gh, None, None, None
+
+
 class NllMeanFn(torch.autograd.Function):
     """addend - (logdet + logn).mean(): FCNormalizingFlow.loss (models/NormalizingFlow.py:144-146; addend = the constraints
     term as a 0-dim tensor, or None) and its cotangents, one launch each way."""

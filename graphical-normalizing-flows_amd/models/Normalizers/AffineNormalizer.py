@@ -23,5 +23,13 @@ class AffineNormalizer(Normalizer):
         z, _, logdet, _ = ops.AffineFn.apply(x, h, self.inplace_clamp, False, False)
         return z, logdet
 
+    def forward_logdet_do(self, x, h, pin, regime=None, context=None):
+        """(z, logdet, logn) under do(x_S) from the kernel that computes z: the two row sums run over the free columns only.
+        With `inplace_clamp` (h rewritten) the composed form of the base class is taken: the masked kernel never stores to h."""
+        if self.inplace_clamp:
+            return super().forward_logdet_do(x, h, pin, regime, context)
+        z, _, logdet, logn = ops.AffineDoFn.apply(x, h, pin, regime, False)
+        return z, logdet, logn
+
     def inverse_transform(self, z, h, context=None):
         return ops.affine_inverse(z, h)

@@ -14,3 +14,12 @@ class Normalizer(nn.Module):
 
     def inverse_transform(self, z, h, context=None):
         pass
+
+    def forward_logdet_do(self, x, h, pin, regime=None, context=None):
+        """(z, logdet, logn) under do(x_S): forward's (z, jac) with log jac and log N(z) summed over the FREE variables
+        only (pin uint8 [R, d], regime int32 [B] or None: models.NormalizingFlow.do_targets) in one masked reduction pass.
+        A normalizer whose kernel can reduce over a row itself overrides this (AffineNormalizer)."""
+        from gnf_hip import ops
+        z, jac = self(x, h, context)
+        logdet, logn = ops.NllDoFn.apply(z, jac, pin, regime)
+        return z, logdet, logn

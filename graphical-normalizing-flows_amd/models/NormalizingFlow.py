@@ -71,6 +71,88 @@ def do_arguments(do_index, do_value, z):
     return idx, vals
 
 
+def _targets_known_empty(targets):
+    """True when the HOST can see that nothing is pinned (an empty index list / tensor): no device value is read"""
+    if torch.is_tensor(targets):
+        return targets.dim() == 1 and targets.numel() == 0 and targets.dtype not in (torch.bool, torch.uint8)
+    try:
+        return len(targets) == 0
+    except TypeError:
+        return False
+
+
+def do_targets(targets, regime, x, check_regime=True):
+    """(pin uint8 [R, d] contiguous on x's device, regime int32 [B] on x's device or None): the mask table of the
+    interventional likelihood (gnf_hip.ops.NllDoFn / AffineDoFn) for data x [B, d].  `targets`:
+      a sequence of ints or an integer tensor [S] -- one target set for the whole batch, unique and in range, as the do_index
+        of intervene (a uint8 tensor is always read as a MASK, never as indices);
+      a bool / uint8 tensor [d]                   -- the same as a mask;
+      a bool / uint8 tensor [R, d] with regime [B] (integer ids in [0, R)) -- a target set per regime;
+      a bool / uint8 tensor [B, d] without a regime -- a target set per sample.
+    ValueError for any other rank, width or dtype, for a regime without an [R, d] table, and for a regime id outside [0, R).
+    That last check reads regime.min() / .max() -- one synchronisation on a device tensor; check_regime=False skips it for a
+    caller that validated its data set once (the kernels answer a bad id with NaN rows and never index the table with it).
+    A contiguous uint8 table and an int32 regime vector already on x's device are handed on as they are -- the kernels read
+    any non-zero byte as pinned -- so an unchecked call costs no launch."""
+    if x.dim() != 2:
+        raise ValueError("do_targets: x must be [B, d], got %s" % (tuple(x.shape),))
+    B, d = x.shape
+    table = None
+    if torch.is_tensor(targets) and targets.dtype in (torch.bool, torch.uint8):
+        if targets.dim() not in (1, 2) or targets.shape[-1] != d:
+            raise ValueError("do_targets: a mask of targets must be [d], [R, d] or [B, d] with d = %d, got %s"
+                             % (d, tuple(targets.shape)))
+        if targets.dim() == 1:
+            table = targets.view(1, d)
+        else:
+            table = targets
+            if regime is None and table.shape[0] not in (1, B):
+                raise ValueError("do_targets: a [%d, d] mask without a regime vector must have B = %d rows (or one)"
+                                 % (table.shape[0], B))
+        if regime is not None and targets.dim() != 2:
+            raise ValueError("do_targets: a regime vector needs an [R, d] table of targets, got a [d] mask")
+        if table.dtype == torch.uint8 and table.device == x.device and table.is_contiguous():
+            pin = table                                 # the kernels read any non-zero byte as pinned: no launch, no copy
+        else:
+            pin = (table != 0).to(device=x.device, dtype=torch.uint8).contiguous()
+    else:
+        if regime is not None:
+            raise ValueError("do_targets: a regime vector needs a bool / uint8 [R, d] table of targets")
+        if torch.is_tensor(targets):
+            if (targets.dim() != 1 or targets.dtype.is_floating_point or targets.dtype.is_complex):
+                raise ValueError("do_targets: targets must be a sequence of ints, an integer tensor [S] or a bool / uint8 "
+                                 "mask, got %s %s" % (targets.dtype, tuple(targets.shape)))
+            idx = tuple(int(i) for i in targets.tolist())
+        else:
+            try:
+                idx = tuple(targets)
+            except TypeError:
+                raise ValueError("do_targets: targets must be a sequence of ints, an integer tensor [S] or a bool / uint8 "
+                                 "mask, got %r" % (type(targets),)) from None
+            if any(isinstance(i, bool) or not isinstance(i, int) for i in idx):
+                raise ValueError("do_targets: targets must be a sequence of ints, an integer tensor [S] or a bool / uint8 mask")
+        if any(i < 0 or i >= d for i in idx):
+            raise ValueError("do_targets: targets %s out of range for d = %d" % (list(idx), d))
+        if len(set(idx)) != len(idx):
+            raise ValueError("do_targets: targets %s name a variable twice" % (list(idx),))
+        host = torch.zeros(1, d, dtype=torch.uint8)
+        if idx:
+            host[0, list(idx)] = 1
+        pin = host.to(x.device)
+    if regime is None:
+        return pin, None
+    if (not torch.is_tensor(regime) or regime.dim() != 1 or regime.shape[0] != B or regime.dtype.is_floating_point
+            or regime.dtype.is_complex or regime.dtype == torch.bool):
+        raise ValueError("do_targets: regime must be an integer tensor [B] = [%d], got %s"
+                         % (B, (regime.dtype, tuple(regime.shape)) if torch.is_tensor(regime) else type(regime)))
+    R = pin.shape[0]
+    if check_regime and B > 0:
+        lo, hi = int(regime.min()), int(regime.max())
+        if lo < 0 or hi >= R:
+            raise ValueError("do_targets: regime ids span [%d, %d], the table has R = %d rows" % (lo, hi, R))
+    return pin, regime.to(device=x.device, dtype=torch.int32).contiguous()
+
+
 class NormalizingFlow(nn.Module):
     """Protocol shared by all flows.  forward(x, context=None) -> (z, log|det J|).  The aggregate queries have
     default implementations in terms of getConditioners(), which every concrete flow provides."""
@@ -149,6 +231,28 @@ class NormalizingFlowStep(NormalizingFlow):
             return fused(x, h, context)
         z, jac = self.normalizer(x, h, context)
         return z, ops.LogSumRowsFn.apply(jac)
+
+    def forward_do(self, x, targets, regime=None, context=None, check_regime=True):
+        """(z, logdet, logn) of x under do(x_S): z = forward's z for every column, logdet[b] = sum over the FREE variables of
+        log|dz_i/dx_i| and logn[b] = sum over the free variables of log N(z_i) -- the truncated factorisation
+        log p(x | do(x_S)) = logdet + logn (interventional likelihood).  The pinned values still feed their
+        children's conditioners; their own terms never enter a sum or a gradient.  targets / regime: do_targets.  All three
+        results are differentiable; this is the training path, so a stochastic DAG gate is allowed.
+
+        The Affine normalizer reduces in the kernel that writes z (ops.AffineDoFn); every other normalizer runs as in
+        forward and ops.NllDoFn reduces its (z, jac).  Targets the HOST knows to be empty ([] or an empty index tensor)
+        take forward itself and the unmasked Normal log-density, bit for bit."""
+        if regime is None and _targets_known_empty(targets):
+            if x.dim() != 2:
+                raise ValueError("do_targets: x must be [B, d], got %s" % (tuple(x.shape),))
+            z, logdet = self.forward(x, context)
+            return z, logdet, ops.NormalLogDensityFn.apply(z)
+        pin, reg = do_targets(targets, regime, x, check_regime)
+        h = self.conditioner(x, context)
+        fused = getattr(self.normalizer, "forward_logdet_do", None)
+        if fused is None:                               # a plug-in that does not derive from Normalizer: the base method on it
+            return Normalizer.forward_logdet_do(self.normalizer, x, h, pin, reg, context)
+        return fused(x, h, pin, reg, context)
 
     # -- inversion ----------------------------------------------------------------------------------------------
     def _levels(self, importance):
@@ -720,6 +824,41 @@ class FCNormalizingFlow(NormalizingFlow):
         """the single step's intervene; ValueError for a flow of several steps"""
         return self._single_step("intervene").intervene(z, do_index, do_value, context)
 
+    # -- likelihoods --------------------------------------------------------------------------------------------
+    def log_prob(self, x, context=None):
+        """log p(x) [B]: log|det J| + z_log_density(z) of forward, the observational convenience"""
+        z, logdet = self.forward(x, context)
+        return logdet + self.z_log_density(z)
+
+    def _do_step(self, what):
+        """the single step of a flow whose likelihood can be truncated; ValueError otherwise"""
+        step = self._single_step(what)
+        dens = self.z_log_density
+        # the test `loss` uses for its fold: the factories' standard normal itself, nothing that merely inherits from it
+        if not (getattr(dens, "standard_normal", False)
+                and getattr(type(dens), "_std_forward", None) is type(dens).forward):
+            raise ValueError("%s.%s: the truncated factorisation drops the pinned variables' terms log N(z_i) of a FACTORISED "
+                             "base density; z_log_density here is %s, not the factories' standard normal, and a joint density "
+                             "has no per-variable terms to truncate" % (type(self).__name__, what, type(dens).__name__))
+        return step
+
+    def log_prob_do(self, x, targets, regime=None, context=None, check_regime=True):
+        """log p(x | do(x_S)) [B]: the joint's terms with those of the intervention targets left out (targets / regime:
+        do_targets).  ValueError for a flow of several steps and for a base density other than the standard normal."""
+        _, logdet, logn = self._do_step("log_prob_do").forward_do(x, targets, regime, context, check_regime)
+        return logdet + logn
+
+    def loss_do(self, x, targets, regime=None, context=None, check_regime=True):
+        """constraintsLoss() - mean_b log p(x_b | do(x_S(b))): the training loss on a mix of observational and interventional
+        rows, through the batch-mean launch of `loss` (ops.NllMeanFn)"""
+        _, logdet, logn = self._do_step("loss_do").forward_do(x, targets, regime, context, check_regime)
+        c = self.constraintsLoss()
+        if isinstance(c, float) and c == 0.:
+            return ops.NllMeanFn.apply(logdet, logn)
+        if torch.is_tensor(c) and c.is_cuda and c.dim() == 0 and c.dtype == torch.float32:
+            return ops.NllMeanFn.apply(logdet, logn, c)
+        return c + ops.NllMeanFn.apply(logdet, logn)
+
     def counterfactual(self, x, do_index, do_value, context=None):
         """the single step's counterfactual; ValueError for a flow of several steps"""
         return self._single_step("counterfactual").counterfactual(x, do_index, do_value, context)
@@ -794,3 +933,7 @@ class CNNormalizingFlow(FCNormalizingFlow):
     def counterfactual(self, x, do_index, do_value, context=None):
         raise ValueError(_SINGLE_STEP % ("CNNormalizingFlow.counterfactual", len(self.steps)) + "; a multi-scale flow has "
                          "none of one step's equations even with a single scale: its latent is cut and re-interleaved")
+
+    def _do_step(self, what):
+        raise ValueError(_SINGLE_STEP % ("CNNormalizingFlow." + what, len(self.steps)) + "; a multi-scale flow has none "
+                         "of one step's equations even with a single scale: its latent is cut and re-interleaved")

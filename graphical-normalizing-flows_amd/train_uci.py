@@ -16,6 +16,12 @@ model.intervene into `samples_do.npy`, and prints the mean |z - forward(x, ctx)|
 per-column mean shift against the un-intervened samples (sample_do_rows).  One-step flows only: -nb_flow > 1 ends with the
 model's ValueError, reported.
 
+`-regimes` trains on a MIX of observational and interventional rows with the interventional likelihood
+(model.loss_do / log_prob_do): the -data npz then also holds `targets` [R, modelled columns] (non-zero: the variable is an
+intervention target in that regime) and `trn_regime` / `val_regime` / `tst_regime` [n]; `-data synthetic -regimes` makes
+regime r = row % (d + 1), regime 0 observational, regime r > 0 pinning column r - 1 at 2 + 0.1 randn.  One-step flows, host
+batches only: refused with -device_batches, -steps_per_replay > 1 and -nb_flow > 1.
+
 Checkpoints: `model.pt` is `state_dict()` with the reference's keys, `ADAM.pt` is in torch.optim.Adam's format, so
 either side can resume the other's run."""
 import argparse
@@ -47,6 +53,52 @@ def load_split(spec, dataset, seed=0):
         return [torch.randn(n, d, generator=g) for n in (20000, 2000, 2000)]
     z = np.load(spec)
     return [torch.from_numpy(np.asarray(z[k], dtype=np.float32)) for k in ("trn", "val", "tst")]
+
+
+def load_regimes(spec, dataset, splits, context_cols=0, seed=0):
+    """-regimes: (splits, targets uint8 [R, d], [trn_regime, val_regime, tst_regime] as int64 [n]) for the d modelled columns.
+    synthetic: regime r = row % (d + 1); regime 0 is observational, regime r > 0 targets column r - 1, whose values are
+    overwritten by 2 + 0.1 randn (the splits are changed in place).  A file: its arrays `targets` and `*_regime`.
+    validate_regimes checks what comes back."""
+    if spec == "synthetic":
+        d = DIMS[dataset] - context_cols
+        g = torch.Generator().manual_seed(seed + 1)
+        targets = torch.cat((torch.zeros(1, d, dtype=torch.uint8), torch.eye(d, dtype=torch.uint8)))
+        regimes = []
+        for X in splits:
+            r = torch.arange(X.shape[0]) % (d + 1)
+            for col in range(d):
+                rows = r == col + 1
+                X[rows.to(X.device), col] = (2. + .1 * torch.randn(int(rows.sum()), generator=g)).to(X.device)
+            regimes.append(r)
+        return splits, targets, regimes
+    z = np.load(spec)
+    missing = [k for k in ("targets", "trn_regime", "val_regime", "tst_regime") if k not in z.files]
+    if missing:
+        raise ValueError("-regimes: %s holds no %s (needed: targets [R, d], trn_regime / val_regime / tst_regime [n])"
+                         % (spec, ", ".join(missing)))
+    targets = torch.from_numpy(np.asarray(z["targets"]))
+    return splits, targets, [torch.from_numpy(np.asarray(z[k + "_regime"])) for k in ("trn", "val", "tst")]
+
+
+def validate_regimes(targets, regimes, splits, d):
+    """once, after loading: targets [R, d] (bool / integer, read as non-zero = pinned) and one integer regime id in [0, R) per
+    row of every split -> (targets as uint8, regimes as int64).  ValueError otherwise.  The per-batch calls then skip the
+    check (check_regime=False)."""
+    if targets.dim() != 2 or targets.shape[1] != d or targets.dtype.is_floating_point or targets.dtype.is_complex:
+        raise ValueError("-regimes: targets must be an integer or bool [R, %d] table, got %s %s"
+                         % (d, targets.dtype, tuple(targets.shape)))
+    R = targets.shape[0]
+    out = []
+    for name, r, X in zip(("trn", "val", "tst"), regimes, splits):
+        if r.dim() != 1 or r.shape[0] != X.shape[0] or r.dtype.is_floating_point or r.dtype.is_complex or r.dtype == torch.bool:
+            raise ValueError("-regimes: %s_regime must be an integer vector [%d], got %s %s"
+                             % (name, X.shape[0], r.dtype, tuple(r.shape)))
+        if r.numel() and (int(r.min()) < 0 or int(r.max()) >= R):
+            raise ValueError("-regimes: %s_regime spans [%d, %d], targets has R = %d rows"
+                             % (name, int(r.min()), int(r.max()), R))
+        out.append(r.to(torch.int64))
+    return (targets != 0).to(torch.uint8).contiguous(), out
 
 
 def batches(X, b, shuffle, gen):
@@ -114,6 +166,18 @@ def mean_ll(model, X, b, gen, on_device=False, context_cols=0):
         tot += ll if on_device else ll.item()
         n += 1
     return float(tot) / max(n, 1)
+
+
+@torch.no_grad()
+def mean_ll_do(model, X, regime, targets, b, context_cols=0):
+    """-regimes: mean over the batches of the batch means of log p(x | do(x_S(regime))) (model.log_prob_do; the regime ids
+    were validated once, after loading)"""
+    tot, n = 0., 0
+    for i in range(0, X.shape[0], b):
+        cur, ctx = split_context(X[i:i + b], context_cols)
+        tot += model.log_prob_do(cur, targets, regime[i:i + b], ctx, check_regime=False).mean().item()
+        n += 1
+    return tot / max(n, 1)
 
 
 @torch.no_grad()
@@ -186,10 +250,11 @@ def sample_do_rows(model, tst, n, context_cols, seed, folder, do, say=print):
 THRESHOLDS = (.95, .5, .1, .01, .0001)
 
 
-def threshold_sweep(model, val, b, gen, epoch, say, on_device=False, context_cols=0):
+def threshold_sweep(model, val, b, gen, epoch, say, on_device=False, context_cols=0, do_tab=None):
     """every 10th epoch (UCIExperiments.py:183-212): validation with the deterministic hard-thresholded adjacency at five
     thresholds, the gate settings restored afterwards.  The mean is over the batch count (the reference divides by the
-    last batch INDEX, :202), and h_thresh returns to the value it had (the reference leaves the last threshold set)"""
+    last batch INDEX, :202), and h_thresh returns to the value it had (the reference leaves the last threshold set).
+    do_tab (-regimes): (targets, regime ids of `val`) -- the rows are scored by log_prob_do, as the epoch's validation is"""
     conds = model.getConditioners()
     saved = [(c.stoch_gate, c.noise_gate, c.s_thresh, c.h_thresh) for c in conds]
     for c in conds:
@@ -199,7 +264,10 @@ def threshold_sweep(model, val, b, gen, epoch, say, on_device=False, context_col
             for c in conds:
                 c.h_thresh = th
             # (-context_cols 0 makes today's call: a mean_ll installed by a caller keeps its five arguments)
-            ll = mean_ll(model, val, b, gen, on_device, context_cols) if context_cols else mean_ll(model, val, b, gen, on_device)
+            if do_tab is not None:
+                ll = mean_ll_do(model, val, do_tab[1], do_tab[0], b, context_cols)
+            else:
+                ll = mean_ll(model, val, b, gen, on_device, context_cols) if context_cols else mean_ll(model, val, b, gen, on_device)
             with torch.no_grad():
                 dagness = float(max(model.DAGness()))
             say("epoch: %d - Threshold: %4f - Valid log-likelihood: %4f - <<DAGness>>: %4f" % (epoch, th, ll, dagness))
@@ -208,10 +276,11 @@ def threshold_sweep(model, val, b, gen, epoch, say, on_device=False, context_col
             c.stoch_gate, c.noise_gate, c.s_thresh, c.h_thresh = sg, ng, st, ht
 
 
-def train_epoch(args, model, state, norm_t, trn, src, epoch_no, rank, world, gen):
+def train_epoch(args, model, state, norm_t, trn, src, epoch_no, rank, world, gen, do_tab=None):
     """the optimisation steps of one epoch -> (device sum of the step losses, number of steps).  src = None: the batches
     are slices of a host permutation drawn from `gen`, copied over; a dp.DeviceBatches: gathered on the device from the
-    permutation of epoch `epoch_no`"""
+    permutation of epoch `epoch_no`.  do_tab (-regimes; src is None then): (targets, regime ids of the training rows) -- every
+    step minimises model.loss_do on its batch with that batch's own ids (each rank its shard's), validated once in train()"""
     dev = trn.device
     ll_tot, n = torch.zeros((), device=dev), 0
     ctx_cols = int(getattr(args, "context_cols", 0))
@@ -223,19 +292,21 @@ def train_epoch(args, model, state, norm_t, trn, src, epoch_no, rank, world, gen
         while group > 1 and src.full_left() >= group and dp.steps_replayable(model, src):
             ll_tot += dp.train_steps(model, state, src, group, lr=args.learning_rate, weight_decay=args.weight_decay)
             n += group
-        feed = (src.next() for _ in range(src.left()))
+        feed = ((src.next(), None) for _ in range(src.left()))
     else:
-        feed = (trn[rows.to(dev)] for rows in shard_batches(trn.shape[0], max(args.b_size, world), rank, world, gen))
-    for x in feed:
+        shards = (rows.to(dev) for rows in shard_batches(trn.shape[0], max(args.b_size, world), rank, world, gen))
+        feed = ((trn[rows], None if do_tab is None else do_tab[1][rows]) for rows in shards)
+    for x, reg in feed:
         if norm_t is MonotonicNormalizer:                    # node-count jitter of the reference (:131-133)
             k = args.nb_steps + int(torch.randint(0, 10, [1], generator=gen))
             for nrm in model.getNormalizers():
                 nrm.nb_steps = k
+        kw = {}                                              # (neither option makes exactly today's call)
         if ctx_cols:                                         # (a gathered batch is split behind the gather)
-            x, ctx = split_context(x, ctx_cols)
-            loss = dp.train_step(model, state, x, lr=args.learning_rate, weight_decay=args.weight_decay, context=ctx)
-        else:
-            loss = dp.train_step(model, state, x, lr=args.learning_rate, weight_decay=args.weight_decay)
+            x, kw["context"] = split_context(x, ctx_cols)
+        if reg is not None:
+            kw.update(targets=do_tab[0], regime=reg, check_regime=False)
+        loss = dp.train_step(model, state, x, lr=args.learning_rate, weight_decay=args.weight_decay, **kw)
         ll_tot += loss.detach()
         n += 1
     return ll_tot, n
@@ -265,6 +336,16 @@ def train(args):
     ctx_cols = int(getattr(args, "context_cols", 0))
     if not 0 <= ctx_cols < trn.shape[1]:
         raise SystemExit("-context_cols %d: the data has %d columns, at least one must be modelled" % (ctx_cols, trn.shape[1]))
+    do_tab = None
+    if getattr(args, "regimes", False):
+        # validated ONCE, here; every batch then goes to the kernels unchecked (their NaN rule is the backstop)
+        splits, targets, regimes = load_regimes(args.data, args.dataset, [trn, val, tst], ctx_cols)
+        try:
+            targets, regimes = validate_regimes(targets, regimes, splits, trn.shape[1] - ctx_cols)
+        except ValueError as exc:
+            raise SystemExit(str(exc))
+        trn, val, tst = splits
+        do_tab = (targets.to(dev), [r.to(dev).to(torch.int32) for r in regimes])   # the kernels' types: no cast per batch
     model, cond_t, norm_t = build(args, trn.shape[1] - ctx_cols)
     os.makedirs(args.folder, exist_ok=True)
     tag = "_" + args.f_number if args.f_number is not None else ""
@@ -308,7 +389,8 @@ def train(args):
                     c.constrainA(zero_threshold=0.)
         ll_tot = torch.zeros((), device=dev)
         if not args.test:
-            ll_tot, n = train_epoch(args, model, state, norm_t, trn, src, epoch0 + epoch, rank, world, gen)
+            ll_tot, n = train_epoch(args, model, state, norm_t, trn, src, epoch0 + epoch, rank, world, gen,
+                                    *(() if do_tab is None else ((do_tab[0], do_tab[1][0]),)))
             ll_tot /= max(n, 1)
             if world > 1:
                 # model.step() decides the dual update / post-processing from this value (DAGConditioner.step): every
@@ -325,7 +407,10 @@ def train(args):
         if norm_t is MonotonicNormalizer:
             for nrm in model.getNormalizers():
                 nrm.nb_steps = args.nb_steps + 20
-        ll_val = mean_ll(model, val, args.b_size, gen, on_dev, *ctx_arg)
+        if do_tab is not None:
+            ll_val = mean_ll_do(model, val, do_tab[1][1], do_tab[0], args.b_size, ctx_cols)
+        else:
+            ll_val = mean_ll(model, val, args.b_size, gen, on_dev, *ctx_arg)
         with torch.no_grad():
             dagness = float(max(model.DAGness()))
         say("epoch: %d - Train loss: %4f - Valid log-likelihood: %4f - <<DAGness>>: %4f - Elapsed time per epoch %4f "
@@ -334,10 +419,15 @@ def train(args):
             if dagness < 1e-20 and -ll_val < best:
                 best = -ll_val
                 torch.save(model.state_dict(), os.path.join(args.folder, "best_model.pt"))
-                say("epoch: %d - Test log-likelihood: %4f - <<DAGness>>: %4f"
-                    % (epoch, mean_ll(model, tst, args.b_size, gen, on_dev, *ctx_arg), dagness))
+                ll_tst = (mean_ll_do(model, tst, do_tab[1][2], do_tab[0], args.b_size, ctx_cols) if do_tab is not None else
+                          mean_ll(model, tst, args.b_size, gen, on_dev, *ctx_arg))
+                say("epoch: %d - Test log-likelihood: %4f - <<DAGness>>: %4f" % (epoch, ll_tst, dagness))
         if getattr(args, "threshold_sweep", False) and epoch % 10 == 0 and cond_t is DAGConditioner:
-            threshold_sweep(model, val, args.b_size, gen, epoch, say, on_dev, *ctx_arg)   # every rank: same work, rank 0 logs
+            # every rank: same work, rank 0 logs
+            if do_tab is not None:
+                threshold_sweep(model, val, args.b_size, gen, epoch, say, on_dev, ctx_cols, (do_tab[0], do_tab[1][1]))
+            else:
+                threshold_sweep(model, val, args.b_size, gen, epoch, say, on_dev, *ctx_arg)
         if rank == 0:
             torch.save(model.state_dict(), os.path.join(args.folder, "model.pt"))
             torch.save(state.optimizer_state_dict(model, args.learning_rate, args.weight_decay),
@@ -413,6 +503,9 @@ def parse(argv=None):
                     help="after the last evaluation: N samples x ~ p(x | context of the first N test rows) into samples.npy")
     ap.add_argument("-do", default=None, nargs="+", metavar="COL=VALUE",
                     help="with -sample N: N samples under the intervention do(x_COL = VALUE, ...) into samples_do.npy")
+    ap.add_argument("-regimes", default=False, action="store_true",
+                    help="train on observational and interventional rows with the interventional likelihood: -data holds "
+                         "targets [R, d] and trn_regime / val_regime / tst_regime [n] (synthetic: regime = row %% (d + 1))")
     args = ap.parse_args(argv)
     if args.load_config is not None:                         # a named entry of the yml overrides the command line
         with open(args.config_file) as f:
@@ -431,6 +524,16 @@ def parse(argv=None):
         ap.error("-do needs -sample N (the interventional samples are drawn from the z of the plain ones)")
     if args.steps_per_replay > 1 and not args.device_batches:
         ap.error("-steps_per_replay needs -device_batches (a replayed group reads its batches from device memory)")
+    if args.regimes:
+        if args.device_batches:
+            ap.error("-regimes with -device_batches: the device-side epochs gather the data rows only, a batch's regime ids "
+                     "are not carried through the gather")
+        if args.steps_per_replay > 1:
+            ap.error("-regimes with -steps_per_replay > 1: a replayed group has one input buffer per step and none for the "
+                     "regime ids; a step with regimes runs launch by launch")
+        if args.nb_flow > 1:
+            ap.error("-regimes with -nb_flow > 1: the truncated factorisation is defined on the data-side equations of a "
+                     "ONE-step flow")
     if not args.folder:
         args.folder = os.path.join("runs", args.load_config or args.dataset)
     return args

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-/* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_*, gnf_image_prep, gnf_dagmlp_*, gnf_dag_levels*, gnf_toy_sample, gnf_shuffle_keys, gnf_tab_batch, gnf_group_bias_*, gnf_spline_*, gnf_made_prefix*_spline and gnf_made_prefix_do were ADDED under this number (no existing symbol
+/* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_*, gnf_image_prep, gnf_dagmlp_*, gnf_dag_levels*, gnf_toy_sample, gnf_shuffle_keys, gnf_tab_batch, gnf_group_bias_*, gnf_spline_*, gnf_made_prefix*_spline, gnf_made_prefix_do, gnf_nll_do_* and gnf_affine_do_* were ADDED under this number (no existing symbol
  * changed; a binding written against the earlier 11 keeps working, and tests/test_cifar_factory.py pins the value) */
 #define GNF_ABI_VERSION 11
 #define GNF_EINVAL (-1)   /* bad argument (null pointer, negative size, ...)          */
@@ -110,6 +110,36 @@ int gnf_nll_reduce_fwd(const float* z, const float* jac, float* logdet, float* l
                        gnf_stream_t stream);
 int gnf_nll_reduce_bwd(const float* z, const float* jac, const float* glogdet, const float* glogn, const float* gz_in,
                        float* gz, float* gjac, int64_t B, int64_t d, gnf_stream_t stream);
+/* Interventional likelihood (csrc/gnf_do_terms.hip): the same two reductions over the FREE variables only, the truncated
+ * factorisation  log p(x | do(x_S)) = sum_{i not in S} [log jac_i + log N(z_i)].
+ *   pin    uint8 [R, d], device, contiguous, ANY address (read byte by byte); non-zero = variable i is an intervention
+ *          target in regime r.  NULL is GNF_EINVAL: the unmasked entry points above exist.
+ *   regime int32 [B] or NULL.  NULL: R == 1 applies row 0 of pin to every sample, R == B applies row b to sample b, any
+ *          other R is GNF_EINVAL.  A regime id outside [0, R) never indexes the table: that sample's logdet and logn are NaN,
+ *          and in the backward its row of every output cotangent is NaN.
+ *   fwd:  logdet[b] = sum_{i free} log jac[b,i]     logn[b] = -0.5 sum_{i free} (log 2pi + z[b,i]^2)
+ *   bwd:  free:    gz[b,i] = (gz_in ? gz_in[b,i] : 0) - z[b,i] glogn[b]    gjac[b,i] = glogdet[b] / jac[b,i]
+ *         pinned:  gz[b,i] = (gz_in ? gz_in[b,i] : 0)                      gjac[b,i] = +0
+ *         (glogdet / glogn / gz_in may be NULL = zero)
+ * A pinned element's z and jac never enter a sum or a cotangent (select, not multiply: they may be inf, NaN or 0).  B == 0
+ * returns 0 before any pointer is looked at.  Fixed summation order for a given (B, d, R, alignment), no atomics, no
+ * workspace. */
+int gnf_nll_do_fwd(const float* z, const float* jac, const uint8_t* pin, const int32_t* regime, int64_t R, float* logdet,
+                   float* logn, int64_t B, int64_t d, gnf_stream_t stream);
+int gnf_nll_do_bwd(const float* z, const float* jac, const uint8_t* pin, const int32_t* regime, int64_t R,
+                   const float* glogdet, const float* glogn, const float* gz_in, float* gz, float* gjac, int64_t B, int64_t d,
+                   gnf_stream_t stream);
+/* The fused form for the Affine normalizer: gnf_affine_fwd / _bwd (without clamp_inplace; any strides of h / gh) with
+ * logdet / logn reduced over the free columns in the pass that writes z.  z (and jac, optional) are written for EVERY column;
+ * a pinned column's z is defined and unused.  bwd: gz / gjac (optional) act on every element as in gnf_affine_bwd; the row
+ * cotangents glogdet / glogn reach gh and gx through free elements only.  logn / glogn may be NULL as in the unmasked pair. */
+int gnf_affine_do_fwd(const float* x, const float* h, int64_t h_sb, int64_t h_sd, int64_t h_sc, const uint8_t* pin,
+                      const int32_t* regime, int64_t R, float* z, float* jac, float* logdet, float* logn, int64_t B,
+                      int64_t d, gnf_stream_t stream);
+int gnf_affine_do_bwd(const float* x, const float* h, int64_t h_sb, int64_t h_sd, int64_t h_sc, const uint8_t* pin,
+                      const int32_t* regime, int64_t R, const float* gz, const float* gjac, const float* glogdet,
+                      const float* glogn, float* gx, float* gh, int64_t g_sb, int64_t g_sd, int64_t g_sc, int64_t B, int64_t d,
+                      gnf_stream_t stream);
 /* FCNormalizingFlow.loss (models/NormalizingFlow.py:144-146): out[0] = addend[0] - mean_b(logdet[b] + logn[b]) (addend: the
  * constraints term as a device scalar, or NULL = 0), one workgroup, fixed summation order;
  * bwd: glogdet[b] = glogn[b] = -g[0]/B (g: device scalar; the addend's cotangent is g itself). */
