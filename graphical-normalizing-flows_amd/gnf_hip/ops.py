@@ -280,17 +280,11 @@ def made_prefix_pack(params, plan):
     steps through an inversion builds it once (AutoregressiveConditioner.hold_prefix_pack)"""
     params = [p.detach() for p in params]
     net, c = _made_net(params, plan), _plan_cond_in(plan)
-    if c == 0:
-        nfl = abi.load().gnf_made_prefix_pack_floats(ctypes.byref(net))
-    else:
-        nfl = abi.load().gnf_made_prefix_ctx_pack_floats(ctypes.byref(net), c)
+    nfl = abi.load().gnf_made_prefix_ctx_pack_floats(ctypes.byref(net), c)       # (c = 0: the unconditional image)
     if nfl < 0:
-        abi.check(int(nfl), "gnf_made_prefix_pack_floats")
+        abi.check(int(nfl), "gnf_made_prefix_ctx_pack_floats")
     pack = _empty((int(nfl),), params[0])
-    if c == 0:
-        call("gnf_made_prefix_pack", ctypes.byref(net), ptr(pack), stream())
-    else:
-        call("gnf_made_prefix_ctx_pack", ctypes.byref(net), c, ptr(pack), stream())
+    call("gnf_made_prefix_ctx_pack", ctypes.byref(net), c, ptr(pack), stream())
     return pack
 
 
@@ -299,27 +293,24 @@ def made_prefix_workspace(params, plan, batch):
     """the activation workspace that carries an inversion of `batch` rows from one made_prefix_steps call to the next"""
     params = [p.detach() for p in params]
     net, c = _made_net(params, plan), _plan_cond_in(plan)
-    if c == 0:
-        nbytes = abi.load().gnf_made_prefix_ws_bytes(ctypes.byref(net), int(batch))
-    else:
-        nbytes = abi.load().gnf_made_prefix_ctx_ws_bytes(ctypes.byref(net), c, int(batch))
+    nbytes = abi.load().gnf_made_prefix_ctx_ws_bytes(ctypes.byref(net), c, int(batch))
     if nbytes < 0:
-        abi.check(int(nbytes), "gnf_made_prefix_ws_bytes")
+        abi.check(int(nbytes), "gnf_made_prefix_ctx_ws_bytes")
     return _ws(nbytes, params[0])
 
 
 @torch.no_grad()
 def made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=None, ws=None, context=None, spline=None, pin=None):
-    """Steps t0 <= t < t1 of the column-by-column inversion of a MADE step (gnf_made_prefix): z, x [B, d] fp32 contiguous.
+    """Steps t0 <= t < t1 of the column-by-column inversion of a MADE step: z, x [B, d] fp32 contiguous.  Every call runs on
+    gnf_made_prefix_do, the entry point whose arguments superset the other four's (NULL context, no bins, NULL table).
     MADE_NORM_AFFINE writes column var_of_step[t] of x per step ((0, d): the whole inversion, one launch);
     MADE_NORM_NONE (t1 == t0 + 1) writes the conditioner outputs of that variable to h_out [B, out] and leaves the column
     to the caller.  ws (made_prefix_workspace): the same buffer for every call of one inversion; allocated here when a call
-    that needs one comes without.  context: the contiguous fp32 [B, cond_in] device tensor of a conditional plan
-    (gnf_made_prefix_ctx), None for cond_in == 0.  MADE_NORM_SPLINE takes spline = (nb_bins, tail_bound) and runs on the
-    gnf_made_prefix*_spline entry points (the others refuse that mode).  pin: the contiguous uint8 [d] device table of an
-    intervention, one byte per VARIABLE, non-zero = pinned (gnf_made_prefix_do): a pinned step reads its column of x, which
-    the caller filled, and writes nothing; MADE_NORM_NONE may then span t1 > t0 + 1 steps whose all but the last are pinned
-    (the library checks that against the table, at the price of a stream synchronisation).  None: the calls above."""
+    that needs one comes without.  context: the contiguous fp32 [B, cond_in] device tensor of a conditional plan, None for
+    cond_in == 0.  MADE_NORM_SPLINE takes spline = (nb_bins, tail_bound).  pin: the contiguous uint8 [d] device table of an
+    intervention, one byte per VARIABLE, non-zero = pinned: a pinned step reads its column of x, which the caller filled,
+    and writes nothing; MADE_NORM_NONE may then span t1 > t0 + 1 steps whose all but the last are pinned (the library
+    checks that against the table, at the price of a stream synchronisation)."""
     params = [p.detach() for p in params]
     net, c = _made_net(params, plan), _plan_cond_in(plan)
     B, d = x.shape
@@ -330,37 +321,30 @@ def made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=None, ws=Non
         raise abi.GnfError("made_prefix_steps: z and x must be contiguous [B, %d]" % plan["d"])
     if h_out is not None and (tuple(h_out.shape) != (B, plan["out"]) or not h_out.is_contiguous()):
         raise abi.GnfError("made_prefix_steps: h_out must be contiguous [B, %d]" % plan["out"])
-    if c == 0:
-        if context is not None:
-            raise abi.GnfError("made_prefix_steps: a context for a plan with cond_in = 0")
-        name, head = "gnf_made_prefix", (ctypes.byref(net),)
-    else:
-        if (context is None or not context.is_cuda or context.device != x.device or context.dtype != torch.float32
-                or tuple(context.shape) != (B, c) or not context.is_contiguous()):
-            raise abi.GnfError("made_prefix_steps: context must be a contiguous fp32 [B, %d] tensor on the device of x" % c)
-        name, head = "gnf_made_prefix_ctx", (ctypes.byref(net), c, ptr(context))
+    if c == 0 and context is not None:
+        raise abi.GnfError("made_prefix_steps: a context for a plan with cond_in = 0")
+    if c and (context is None or not context.is_cuda or context.device != x.device or context.dtype != torch.float32
+              or tuple(context.shape) != (B, c) or not context.is_contiguous()):
+        raise abi.GnfError("made_prefix_steps: context must be a contiguous fp32 [B, %d] tensor on the device of x" % c)
     if ws is None and not (t0 == 0 and t1 == d):
         ws = made_prefix_workspace(params, plan, B)
-    extra = ()
+    bins, tail = 0, 0.
     if int(mode) == MADE_NORM_SPLINE:
         if spline is None:
             raise abi.GnfError("made_prefix_steps: MADE_NORM_SPLINE needs spline = (nb_bins, tail_bound)")
-        name, extra = name + "_spline", (int(spline[0]), float(spline[1]))
-    if pin is not None:
-        # the one entry point that supersets the others: (net, cond_in, context, ..., bins, tail, pin, ...)
-        name, head = "gnf_made_prefix_do", (ctypes.byref(net), c, None if c == 0 else ptr(context))
-        extra = (extra or (0, 0.)) + (ctypes.c_void_p(pin.data_ptr()),)
-    args = lambda w: head + (ptr(pack), ptr(z), ptr(x), ptr(h_out), int(t0), int(t1), int(mode)) + extra + (
-        B, None if w is None else ctypes.c_void_p(w.data_ptr()), 0 if w is None else w.numel() * 4, stream())
+        bins, tail = int(spline[0]), float(spline[1])
+    args = lambda w: (ctypes.byref(net), c, ptr(context), ptr(pack), ptr(z), ptr(x), ptr(h_out), int(t0), int(t1), int(mode),
+                      bins, tail, None if pin is None else ctypes.c_void_p(pin.data_ptr()), B,
+                      None if w is None else ctypes.c_void_p(w.data_ptr()), 0 if w is None else w.numel() * 4, stream())
     if ws is None:
         # a whole inversion whose tile of activations fits in LDS needs no workspace; the library says when it does not
-        rc = getattr(abi.load(), name)(*args(None))
+        rc = abi.load().gnf_made_prefix_do(*args(None))
         if rc == 0:
             return x
         if rc != -3:
-            abi.check(rc, name)
+            abi.check(rc, "gnf_made_prefix_do")
         ws = made_prefix_workspace(params, plan, B)
-    call(name, *args(ws))
+    call("gnf_made_prefix_do", *args(ws))
     return x
 
 

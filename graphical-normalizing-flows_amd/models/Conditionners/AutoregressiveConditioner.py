@@ -282,12 +282,11 @@ class AutoregressiveConditioner(Conditioner):
         """steps t0 <= t < t1 of the plan on the HIP prefix kernel (gnf_hip.ops.made_prefix_steps); `context`: the checked
         [B, cond_in] context of a conditional conditioner (the plan is then prefix_plan(with_context=True)); `spline`:
         (nb_bins, tail_bound) for ops.MADE_NORM_SPLINE; `pin`: the uint8 [d] pin table, by variable, of an intervention
-        (gnf_made_prefix_do: a pinned step reads its column of x)"""
+        (a pinned step reads its column of x)"""
         plan, params = self.prefix_plan(with_context=bool(self.cond_in)), self._prefix_params()
         pack = self._held_prefix if self._held_prefix is not None else ops.made_prefix_pack(params, plan)
         return ops.made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=h_out, ws=ws, context=context,
-                                     **({} if spline is None else {"spline": spline}),
-                                     **({} if pin is None else {"pin": pin}))
+                                     spline=spline, pin=pin)
 
     # -- the adjoint of that sweep (NormalizingFlowStep.rsample's backward) -------------------------------------------------
     _held_adjoint = None

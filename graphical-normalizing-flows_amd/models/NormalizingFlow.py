@@ -7,6 +7,7 @@ by name); the bodies are written against gnf_hip.ops.
     stack:  steps in sequence, feature order reversed between steps, log-dets added             (reference :110-126)
     loss:   sum of conditioner constraint terms - mean(log|det J| + log N(z))                  (reference :128-146)
 """
+import contextlib
 import weakref
 
 import torch
@@ -14,6 +15,7 @@ import torch.nn as nn
 
 from gnf_hip import ops
 from .Conditionners import Conditioner, DAGConditioner
+from .Conditionners.AutoregressiveConditioner import made_do_launches
 from .Conditionners.Conditioner import checked_context
 from .Normalizers import Normalizer, AffineNormalizer, SplineNormalizer
 
@@ -33,9 +35,59 @@ def _is_dag(conditioner):
     return type(conditioner) is DAGConditioner
 
 
+def _is_std_normal(dens):
+    """the factories' standard-normal base density itself, nothing that merely inherits from it: a subclass that overrides
+    forward (tempered / scaled / conditional density) is called as the reference calls it"""
+    return bool(getattr(dens, "standard_normal", False) and getattr(type(dens), "_std_forward", None) is type(dens).forward)
+
+
+def _is_zero(c):
+    return isinstance(c, float) and c == 0.
+
+
+def _is_device_scalar(c):
+    return torch.is_tensor(c) and c.is_cuda and c.dim() == 0 and c.dtype == torch.float32
+
+
+def _nll_mean(c, logdet, logn):
+    """c - mean(logdet + logn) for the constraints term c: one launch where c is plain zero or a device scalar"""
+    if _is_zero(c):
+        return ops.NllMeanFn.apply(logdet, logn)                                 # -(logdet + logn).mean(), one launch
+    if _is_device_scalar(c):
+        return ops.NllMeanFn.apply(logdet, logn, c)                              # constraints - mean(...), the same launch
+    return c + ops.NllMeanFn.apply(logdet, logn)
+
+
 _SINGLE_STEP = ("%s: an intervention is defined on the data-side equations x_i = T^-1(z_i; h_i(x_pa(i), context)) of a "
                 "ONE-step flow; the intermediate variables of a stacked or multi-scale flow are not the x_i (this flow has "
                 "%d steps)")
+
+
+def _index_tuple(index, d, who, must_be, twice, got):
+    """a sequence of ints or an integer tensor [S] (never bool) as a tuple of unique ints in [0, d); ValueError otherwise,
+    worded for the caller: `who` names the function and its argument, `must_be` what the argument may be, `twice` is the
+    verb of the repeated-variable message, `got` says whether a refusal also names what came (then a non-iterable is a
+    ValueError too, not the TypeError of tuple())"""
+    def bad(seen=""):
+        return ValueError("%s must be %s%s" % (who, must_be, ", got " + seen if got and seen else ""))
+    if torch.is_tensor(index):
+        if index.dim() != 1 or index.dtype.is_floating_point or index.dtype.is_complex or index.dtype == torch.bool:
+            raise bad("%s %s" % (index.dtype, tuple(index.shape)))
+        idx = tuple(int(i) for i in index.tolist())
+    else:
+        try:
+            idx = tuple(index)
+        except TypeError:
+            if not got:
+                raise
+            raise bad("%r" % (type(index),)) from None
+        if any(isinstance(i, bool) or not isinstance(i, int) for i in idx):
+            raise bad()
+    if any(i < 0 or i >= d for i in idx):
+        raise ValueError("%s %s out of range for d = %d" % (who, list(idx), d))
+    if len(set(idx)) != len(idx):
+        raise ValueError("%s %s %s a variable twice" % (who, list(idx), twice))
+    return idx
 
 
 def do_arguments(do_index, do_value, z):
@@ -45,19 +97,7 @@ def do_arguments(do_index, do_value, z):
     if z.dim() != 2:
         raise ValueError("intervene: z must be [B, d], got %s" % (tuple(z.shape),))
     B, d = z.shape
-    if torch.is_tensor(do_index):
-        if (do_index.dim() != 1 or do_index.dtype.is_floating_point or do_index.dtype.is_complex
-                or do_index.dtype == torch.bool):
-            raise ValueError("intervene: do_index must be a sequence of ints or an integer tensor [S]")
-        idx = tuple(int(i) for i in do_index.tolist())
-    else:
-        idx = tuple(do_index)
-        if any(isinstance(i, bool) or not isinstance(i, int) for i in idx):
-            raise ValueError("intervene: do_index must be a sequence of ints or an integer tensor [S]")
-    if any(i < 0 or i >= d for i in idx):
-        raise ValueError("intervene: do_index %s out of range for d = %d" % (list(idx), d))
-    if len(set(idx)) != len(idx):
-        raise ValueError("intervene: do_index %s names a variable twice" % (list(idx),))
+    idx = _index_tuple(do_index, d, "intervene: do_index", "a sequence of ints or an integer tensor [S]", "names", False)
     S = len(idx)
     if torch.is_tensor(do_value) and do_value.dim() > 0:
         if tuple(do_value.shape) not in ((S,), (B, S)):
@@ -118,23 +158,8 @@ def do_targets(targets, regime, x, check_regime=True):
     else:
         if regime is not None:
             raise ValueError("do_targets: a regime vector needs a bool / uint8 [R, d] table of targets")
-        if torch.is_tensor(targets):
-            if (targets.dim() != 1 or targets.dtype.is_floating_point or targets.dtype.is_complex):
-                raise ValueError("do_targets: targets must be a sequence of ints, an integer tensor [S] or a bool / uint8 "
-                                 "mask, got %s %s" % (targets.dtype, tuple(targets.shape)))
-            idx = tuple(int(i) for i in targets.tolist())
-        else:
-            try:
-                idx = tuple(targets)
-            except TypeError:
-                raise ValueError("do_targets: targets must be a sequence of ints, an integer tensor [S] or a bool / uint8 "
-                                 "mask, got %r" % (type(targets),)) from None
-            if any(isinstance(i, bool) or not isinstance(i, int) for i in idx):
-                raise ValueError("do_targets: targets must be a sequence of ints, an integer tensor [S] or a bool / uint8 mask")
-        if any(i < 0 or i >= d for i in idx):
-            raise ValueError("do_targets: targets %s out of range for d = %d" % (list(idx), d))
-        if len(set(idx)) != len(idx):
-            raise ValueError("do_targets: targets %s name a variable twice" % (list(idx),))
+        idx = _index_tuple(targets, d, "do_targets: targets",       # (a bool / uint8 tensor is a mask: it never gets here)
+                           "a sequence of ints, an integer tensor [S] or a bool / uint8 mask", "name", True)
         host = torch.zeros(1, d, dtype=torch.uint8)
         if idx:
             host[0, list(idx)] = 1
@@ -255,51 +280,74 @@ class NormalizingFlowStep(NormalizingFlow):
         return fused(x, h, pin, reg, context)
 
     # -- inversion ----------------------------------------------------------------------------------------------
-    def _levels(self, importance):
-        """the level schedule of the current gate, recomputed only when A (storage or version counter) or the gate's
-        thresholds changed: DAGConditioner.levels() is a host synchronisation in front of every sampling pass otherwise.
-        With `device_graph` it is two launches (gnf_hip.ops.dag_levels), a sort and one copy of 2 d + 3 integers; without
-        it the d x d adjacency goes to the host and is walked in Python (5 ms against 0.9 at 784 x 784, 39 .. 427 ms
-        against 1.6 .. 15 at d = 3072: profiles/dag_graph_ab.txt)"""
+    DO_LEVELS_MAX = 8                    # mutilated level schedules kept per step (pinned tuples of one gate)
+
+    def _levels(self, importance, idx=()):
+        """(levels, (all rows, int32 rows per level)) of the current gate under do(x_idx), or None for a cyclic graph: the
+        pinned variables lose their parents (their rows of the importance matrix zeroed) and leave the level lists; levels
+        that held only pinned variables vanish.  idx = (): the schedule of invert.
+
+        Recomputed only when A (storage or version counter) or the gate's thresholds changed: DAGConditioner.levels() is a
+        host synchronisation in front of every sampling pass otherwise.  With `device_graph` it is two launches
+        (gnf_hip.ops.dag_levels), a sort and one copy of 2 d + 3 integers; without it the d x d adjacency goes to the host
+        and is walked in Python (5 ms against 0.9 at 784 x 784, 39 .. 427 ms against 1.6 .. 15 at d = 3072:
+        profiles/dag_graph_ab.txt).  The un-pinned schedule is held alone in `_levels_own` -- the captured graphs of invert
+        replay it, so no intervention may evict it -- and the mutilated ones in `_levels_do`, at most DO_LEVELS_MAX."""
         cond = self.conditioner
         # A trainable A is rewritten by the optimiser through a raw pointer (gnf_hip.dp: fused Adam on the flat buffer, a
         # replayed hipGraph), which moves neither its version counter nor its address: nothing is cached for it.  A frozen
         # one is keyed on (storage, version, thresholds, the conditioner's cache epoch -- see invalidate_caches()).
         key = (None if cond.A.requires_grad else
                (cond.A.data_ptr(), cond.A._version, float(cond.h_thresh), bool(cond.s_thresh), cond.A.device,
-                getattr(cond, "_cache_epoch", 0)))
-        if key is None or getattr(self, "_levels_key", None) != key:
-            lv = cond.levels(importance, with_host=True)
-            if lv is not None and cond.A.shape[0] == 784:
-                # the order of the variables INSIDE a level is free: take the one the sparse embedding kernels work in (crop
-                # origin, then pixel), so that their output needs no un-sorting gather
-                lv = [(torch.as_tensor(_crop_order(hr), dtype=torch.long, device=rows.device), _crop_order(hr))
-                      for rows, hr in lv]
-            self._levels_val = lv
-            self._levels_all = torch.cat([rows for rows, _ in lv]) if lv else None   # one gather of z per pass
-            self._levels_rows32 = [rows.to(torch.int32) for rows, _ in lv] if lv else None   # scatter tables of the inverse
-            self._levels_key = key
+                getattr(cond, "_cache_epoch", 0), tuple(sorted(idx))))
+        cache, own = self.__dict__.setdefault("_levels_do", {}), self.__dict__.get("_levels_own")
+        if key is not None and idx and key in cache:
+            return cache[key]
+        if key is not None and not idx and own is not None and own[0] == key:
+            return own[1]
+        cut = importance
+        if idx:
+            cut = importance.detach().clone()
+            cut[list(idx)] = 0
+        lv = cond.levels(cut, with_host=True)
+        entry = None
+        if lv is not None:
+            # the order of the variables INSIDE a level is free: for a 28 x 28 image take the one the sparse embedding kernels
+            # work in (crop origin, then pixel), so that their output needs no un-sorting gather
+            pinned, crop, out = set(idx), cond.A.shape[0] == 784, []
+            for rows, host in lv:
+                keep = tuple(r for r in host if r not in pinned)
+                if crop:
+                    keep = _crop_order(keep)
+                if keep:
+                    out.append((rows if keep == host else torch.as_tensor(keep, dtype=torch.long, device=rows.device), keep))
+            # one gather of z per pass, and the scatter tables of the inverse
+            entry = (out, (torch.cat([rows for rows, _ in out]), [rows.to(torch.int32) for rows, _ in out]) if out else
+                     (None, None))
+        if not idx:
+            self._levels_own = None if key is None else (key, entry)
             _INV_GRAPHS.pop(self, None)                 # graphs captured for another gate replay another schedule
-        return self._levels_val, key
+        elif key is not None:
+            if len(cache) >= self.DO_LEVELS_MAX:
+                cache.clear()
+            cache[key] = entry
+        return entry
 
-    def _invert_levels_body(self, z, levels, importance, context, x=None, tables=None):
+    def _invert_levels_body(self, z, levels, importance, context, tables, x=None):
         """variable-major inside: z is gathered ONCE into [sum of level sizes, B] (a level is a contiguous slice), the
         conditioner rows come as [R, B, out] -- the layout the sparse kernels write -- and the normalizer's inverse is
         element-wise in whatever two leading dimensions z and h share.  Per level that leaves the embedding front, the
-        inverse and one scatter into x (no gather of z, no un-sorting or permuting copy of h)."""
+        inverse and one scatter into x (no gather of z, no un-sorting or permuting copy of h).  tables: the second half of
+        `_levels`' answer for these levels; x: the start of an intervention, pinned columns filled."""
         cond = self.conditioner
-        # (intervene() brings its own x, pinned columns filled, and the (all rows, int32 rows) tables of its own schedule)
         x = torch.zeros_like(z) if x is None else x
-        zt = z.t()[self._levels_all if tables is None else tables[0]]         # [sum R, B], contiguous
+        all_rows, rows32 = tables
+        zt = z.t()[all_rows]                                                  # [sum R, B], contiguous
         off = 0
         into = getattr(self.normalizer, "inverse_transform_into", None)       # (the normalizers ignore the context)
-        rows32 = getattr(self, "_levels_rows32", None) if tables is None else tables[1]
-        if into is not None and (rows32 is None or len(rows32) != len(levels)):
-            into = None
         for k, (rows, host_rows) in enumerate(levels):
             R = rows.numel()
-            h = cond.forward_rows(x, rows, importance, host_rows, variable_major=True,
-                                  rows32=rows32[k] if rows32 is not None and len(rows32) == len(levels) else None,
+            h = cond.forward_rows(x, rows, importance, host_rows, variable_major=True, rows32=rows32[k],
                                   **({} if context is None else {"context": context}))
             # the normalizer writes its [R, B] result into columns `rows` of x itself where it can
             if into is None or not into(zt[off:off + R], h, x, rows32[k]):
@@ -320,36 +368,65 @@ class NormalizingFlowStep(NormalizingFlow):
             out.append((net, "_held_prep", net.hold_prepared))
         return out
 
-    def _invert_by_levels(self, z, context):
+    def _fast_arm(self, z, context):
+        """which schedule inverts (z, context), and with what: ("levels", importance, checked context) for a DAG conditioner
+        with a deterministic gate (`level_schedule`), ("columns", plan, checked contiguous context) for a MADE whose masks
+        are its degree rule (`column_schedule`; the plan is None for an empty batch, which needs none), None for the
+        fixed-point passes.  A conditioner built with cond_in > 0 has its context checked first -- ValueError: missing, wrong
+        width / rank / rows; one with cond_in = 0 that is given a context goes to the passes, which raise what it raises."""
+        cond = self.conditioner
+        cond_in = int(getattr(cond, "cond_in", 0) or 0)
+        if not cond_in and context is not None:
+            return None
+        if _is_dag(cond) and self.level_schedule:
+            ctx = checked_context(context, cond_in, z) if cond_in else context
+            if not cond_in or (z.dim() == 2 and ctx.device == z.device and ctx.dtype == z.dtype):
+                importance = cond.deterministic_importance()
+                if importance is not None:
+                    return "levels", importance, ctx
+        get_plan = getattr(cond, "prefix_plan", None)
+        if not (self.column_schedule and get_plan is not None and z.is_cuda and z.dim() == 2
+                and z.dtype == torch.float32):
+            return None
+        if cond_in:
+            context = checked_context(context, cond_in, z)
+            if context.device != z.device or context.dtype != torch.float32:
+                return None
+            context = context.contiguous()
+        if z.shape[0] == 0:
+            return "columns", None, context
+        plan = get_plan(with_context=True) if cond_in else get_plan()
+        return ("columns", plan, context) if plan is not None and plan["d"] == z.shape[1] else None
+
+    def _invert_by_levels(self, z, importance, context, idx=(), vals=None, capture=False):
         """DAG conditioner with a deterministic gate: every variable is inverted once, after its parents -- d
         conditioner rows in total instead of (depth + 1) * d.  Same values as the fixed-point passes (non-parents are
-        masked by exact zeros either way).  Returns None when not applicable.
+        masked by exact zeros either way).  Returns None for a cyclic graph.
+
+        Under do(x_idx = vals) it is the schedule of the mutilated graph: x[:, idx] = vals is written before the first
+        level, then the remaining rows run -- fewer conditioner rows and no more levels than invert needs.
 
         A conditioner built with cond_in > 0 takes its (checked) context along: every level's rows are completed with
         context[b] by the DAGMLP, on the composed formulation, launch by launch (no graph is captured for such a pass).
 
-        On the GPU the pass of a given (gate, batch shape, node count) is captured into a hipGraph the second time it is
-        asked for and replayed from then on (`graph_invert`): with a frozen A the schedule, the row tables and the sparse
-        plans are static, and a sampling pass over MNIST is ~650 launches of 5-100 us (reference ImageExperiments.py:341-350
-        samples after post_process()).  The weight image of the normalizer is packed INSIDE the graph, so a replay reads
-        the current parameters."""
+        capture (invert alone, never an intervention): on the GPU the pass of a given (gate, batch shape, node count) is
+        captured into a hipGraph the second time it is asked for and replayed from then on (`graph_invert`): with a frozen
+        A the schedule, the row tables and the sparse plans are static, and a sampling pass over MNIST is ~650 launches of
+        5-100 us (reference ImageExperiments.py:341-350 samples after post_process()).  The weight image of the normalizer
+        is packed INSIDE the graph, so a replay reads the current parameters."""
         cond = self.conditioner
-        if not (_is_dag(cond) and self.level_schedule):
+        entry = self._levels(importance, idx)
+        if entry is None:
             return None
-        cond_in = int(getattr(cond, "cond_in", 0) or 0)
-        if not cond_in and context is not None:
-            return None                                 # the passes raise what a cond_in = 0 conditioner raises
-        if cond_in:
-            context = checked_context(context, cond_in, z)              # ValueError: missing, wrong width / rank / rows
-            if z.dim() != 2 or context.device != z.device or context.dtype != z.dtype:
-                return None
-        importance = cond.deterministic_importance()
-        if importance is None:
-            return None
-        levels, lkey = self._levels(importance)
-        if levels is None:
-            return None
-        if cond_in and z.shape[0] == 0:
+        levels, tables = entry
+        if not capture:                                 # launch by launch; invert's graphs are neither read nor added to
+            x = torch.zeros_like(z)
+            if idx:
+                x[:, list(idx)] = vals
+            if z.shape[0] == 0 or not levels:
+                return x
+            return self._invert_levels_body(z, levels, importance, context, tables, x=x)
+        if context is not None and z.shape[0] == 0:
             return torch.zeros_like(z)                  # no rows, no launch (as the column schedule answers an empty batch)
         # a captured pass bakes the ADDRESS of the importance matrix in: only A itself qualifies -- the thresholded forms
         # (s_thresh / h_thresh > 0, the state the reference's threshold sweep sets) are temporaries freed after this call
@@ -357,7 +434,7 @@ class NormalizingFlowStep(NormalizingFlow):
                      and z.dtype == torch.float32 and importance.data_ptr() == cond.A.data_ptr()
                      and len(levels) > 4 and not torch.cuda.is_current_stream_capturing())
         if not graphable:
-            return self._invert_levels_body(z, levels, importance, context)
+            return self._invert_levels_body(z, levels, importance, context, tables)
         # what a captured pass bakes in: shapes, the node count, the front, and the ADDRESSES of every parameter and buffer
         # (values may change freely; a re-bound or moved tensor must not be read through a stale pointer)
         key = (tuple(z.shape), int(getattr(self.normalizer, "nb_steps", 0)), bool(getattr(cond, "sparse_front", False)),
@@ -368,9 +445,9 @@ class NormalizingFlowStep(NormalizingFlow):
         entry = graphs.get(key)
         if entry is None:                               # first request: eager (workspaces, plans and tables come to exist)
             graphs[key] = "warm"
-            return self._invert_levels_body(z, levels, importance, context)
+            return self._invert_levels_body(z, levels, importance, context, tables)
         if entry == "eager":                            # a capture of this variant failed once: launch by launch from then on
-            return self._invert_levels_body(z, levels, importance, context)
+            return self._invert_levels_body(z, levels, importance, context, tables)
         if entry == "warm":
             import gc
             zbuf = z.clone()
@@ -385,7 +462,7 @@ class NormalizingFlowStep(NormalizingFlow):
                 with contextlib.ExitStack() as stack:
                     for _, _, make in holders:
                         stack.enter_context(make())
-                    self._invert_levels_body(zbuf, levels, importance, context)
+                    self._invert_levels_body(zbuf, levels, importance, context, tables)
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             gc_was_on = gc.isenabled()
@@ -396,7 +473,7 @@ class NormalizingFlowStep(NormalizingFlow):
                 with torch.cuda.graph(graph), contextlib.ExitStack() as stack:
                     for _, _, make in holders:
                         stack.enter_context(make())
-                    xbuf = self._invert_levels_body(zbuf, levels, importance, context)
+                    xbuf = self._invert_levels_body(zbuf, levels, importance, context, tables)
             except Exception as exc:                    # noqa: BLE001  (e.g. a host synchronisation inside a user-supplied
                 failed = exc                            # integrand / embedding module): this variant stays eager
             finally:
@@ -410,7 +487,7 @@ class NormalizingFlowStep(NormalizingFlow):
                               "runs eagerly from now on" % (failed,), RuntimeWarning, stacklevel=2)
                 graphs[key] = "eager"
                 torch.cuda.synchronize()
-                return self._invert_levels_body(z, levels, importance, context)
+                return self._invert_levels_body(z, levels, importance, context, tables)
             if len(graphs) > self.GRAPH_INVERT_MAX:
                 graphs.clear()
             entry = graphs[key] = (graph, zbuf, xbuf)
@@ -419,178 +496,24 @@ class NormalizingFlowStep(NormalizingFlow):
         graph.replay()
         return xbuf.clone()
 
-    def _invert_by_columns(self, z, context):
+    def _invert_by_columns(self, z, plan, context, idx=(), vals=None):
         """MADE conditioner: the variables are inverted in degree order, one per step, and a step evaluates only the hidden
         units that became final with the previous column (AutoregressiveConditioner.prefix_plan) -- about half of ONE masked
         forward and ONE normalizer inverse in total, where the passes below spend depth() + 1 = d of each.  The same function
-        in another fp32 summation order.  Returns None when not applicable.
+        in another fp32 summation order.
 
         A conditional MADE (cond_in > 0) is inverted the same way from its conditional plan (prefix_plan(with_context=True)):
-        the checked context heads the kernel's activation rows, the conditioner module is never called."""
+        the checked context heads the kernel's activation rows, the conditioner module is never called.
+
+        Under do(x_idx = vals) the sweep takes a pin table (gnf_made_prefix_do): x[:, idx] = vals is written first, and a
+        pinned step reads its column instead of computing it.  Affine / Spline + MADE are ONE launch either way; any other
+        normalizer is stepped through made_do_launches: one launch per FREE column, which advances through the run of pinned
+        degrees in front of it, and none for a trailing run -- (t, t + 1) for every t when nothing is pinned."""
         cond = self.conditioner
-        get_plan = getattr(cond, "prefix_plan", None)
-        if not (self.column_schedule and get_plan is not None and z.is_cuda and z.dim() == 2
-                and z.dtype == torch.float32):
-            return None
-        cond_in = int(getattr(cond, "cond_in", 0) or 0)
-        if not cond_in and context is not None:
-            return None                                 # the passes raise what a cond_in = 0 conditioner raises
-        if cond_in:
-            context = checked_context(context, cond_in, z)              # ValueError: missing, wrong width / rank / rows
-            if context.device != z.device or context.dtype != torch.float32:
-                return None
         if z.shape[0] == 0:
             # no rows, no launch: the empty result (the passes would stop at the MADE's `.view(0, -1, d)` as the reference's do)
             return torch.zeros_like(z)
-        plan = get_plan(with_context=True) if cond_in else get_plan()
-        if plan is None or plan["d"] != z.shape[1]:
-            return None
-        if cond_in:
-            context = context.contiguous()
-        z = z.contiguous()
-        x = torch.zeros_like(z)
-        B, d, out = z.shape[0], plan["d"], plan["out"]
-        with cond.hold_prefix_pack():
-            if type(self.normalizer) is AffineNormalizer:
-                # the whole inversion, one launch
-                cond.prefix_steps(z, x, 0, d, ops.MADE_NORM_AFFINE, **({"context": context} if cond_in else {}))
-                return x
-            if type(self.normalizer) is SplineNormalizer:
-                # likewise: the spline's closed-form inverse is the kernel's per-row epilogue
-                cond.prefix_steps(z, x, 0, d, ops.MADE_NORM_SPLINE, spline=(self.normalizer.nb_bins, self.normalizer.tail_bound),
-                                  **({"context": context} if cond_in else {}))
-                return x
-            h = torch.empty(B, out, dtype=torch.float32, device=z.device)
-            ws = cond.prefix_workspace(B)
-            zt = z.t().contiguous()                                          # a column of z as a one-row [1, B] problem
-            cols = torch.arange(d, dtype=torch.int32, device=z.device)
-            into = getattr(self.normalizer, "inverse_transform_into", None)
-            for t in range(d):
-                v = plan["var_host"][t]
-                cond.prefix_steps(z, x, t, t + 1, ops.MADE_NORM_NONE, h_out=h, ws=ws,
-                                  **({"context": context} if cond_in else {}))
-                # the normalizer's own inverse of that one column; the fused Monotonic kernel writes x[:, v] itself
-                if into is None or not into(zt[v:v + 1], h.view(1, B, out), x, cols[v:v + 1]):
-                    x[:, v:v + 1] = self.normalizer.inverse_transform(z[:, v:v + 1], h.view(B, 1, out), context)
-        return x
-
-    def invert(self, z, context=None):
-        """Reference :98-107: fixed point of x <- normalizer^-1(z, conditioner(x)) from x = 0, depth()+1 passes, early
-        exit once a pass changes nothing (its progress print is dropped)."""
-        import contextlib
-        with torch.no_grad(), contextlib.ExitStack() as stack:   # parameters do not change inside: build their images once
-            for _, _, make in self._holders():
-                stack.enter_context(make())
-            x = self._invert_by_levels(z, context)
-            if x is None:
-                x = self._invert_by_columns(z, context)
-            if x is not None:
-                return x
-            x = torch.zeros_like(z)
-            for _ in range(self.conditioner.depth() + 1):
-                previous = x
-                x = self.normalizer.inverse_transform(z, self.conditioner(x, context), context)
-                if torch.equal(x, previous):
-                    break
-        return x
-
-    # -- interventions ------------------------------------------------------------------------------------------
-    DO_LEVELS_MAX = 8                    # mutilated level schedules kept per step (pinned tuples of one gate)
-
-    def _do_levels(self, importance, idx):
-        """(levels, (all rows, int32 rows per level)) of the MUTILATED graph of do(x_idx): the pinned variables lose their
-        parents (their rows of the importance matrix zeroed) and leave the level lists; levels that held only pinned
-        variables vanish.  None for a cyclic graph.  Cached beside -- never in -- invert's `_levels_*` attributes, on the
-        key of `_levels` plus the pinned tuple; a trainable A caches nothing, as there."""
-        cond = self.conditioner
-        key = (None if cond.A.requires_grad else
-               (cond.A.data_ptr(), cond.A._version, float(cond.h_thresh), bool(cond.s_thresh), cond.A.device,
-                getattr(cond, "_cache_epoch", 0), tuple(sorted(idx))))
-        cache = self.__dict__.setdefault("_do_levels_cache", {})
-        if key is not None and key in cache:
-            return cache[key]
-        cut = importance.detach().clone()
-        cut[list(idx)] = 0
-        lv = cond.levels(cut, with_host=True)
-        entry = None
-        if lv is not None:
-            pinned, out = set(idx), []
-            for rows, host in lv:
-                keep = tuple(r for r in host if r not in pinned)
-                if cond.A.shape[0] == 784:              # the order inside a level that the sparse embedding kernels work in
-                    keep = _crop_order(keep)
-                if keep:
-                    out.append((rows if len(keep) == len(host) and cond.A.shape[0] != 784 else
-                                torch.as_tensor(keep, dtype=torch.long, device=rows.device), keep))
-            tables = ((torch.cat([rows for rows, _ in out]), [rows.to(torch.int32) for rows, _ in out]) if out else
-                      (None, None))
-            entry = (out, tables)
-        if key is not None:
-            if len(cache) >= self.DO_LEVELS_MAX:
-                cache.clear()
-            cache[key] = entry
-        return entry
-
-    def _intervene_by_levels(self, z, idx, vals, context):
-        """DAG conditioner, deterministic gate: the level schedule of the mutilated graph.  x[:, idx] = vals is written
-        before the first level, then `_invert_levels_body` runs on the remaining rows -- fewer conditioner rows and no
-        more levels than invert needs.  Launch by launch: no graph is captured, and invert's cache and its captured
-        graphs are not touched.  Returns None when not applicable (the conditions of `_invert_by_levels`)."""
-        cond = self.conditioner
-        if not (_is_dag(cond) and self.level_schedule):
-            return None
-        cond_in = int(getattr(cond, "cond_in", 0) or 0)
-        if not cond_in and context is not None:
-            return None
-        if cond_in:
-            context = checked_context(context, cond_in, z)
-            if z.dim() != 2 or context.device != z.device or context.dtype != z.dtype:
-                return None
-        importance = cond.deterministic_importance()
-        if importance is None:
-            return None
-        if idx:
-            entry = self._do_levels(importance, idx)
-            if entry is None:
-                return None
-            levels, tables = entry
-        else:                                           # P empty: invert's own schedule, read as invert reads it
-            levels, _ = self._levels(importance)
-            if levels is None:
-                return None
-            tables = None
-        x = torch.zeros_like(z)
-        if idx:
-            x[:, list(idx)] = vals
-        if z.shape[0] == 0 or not levels:
-            return x
-        return self._invert_levels_body(z, levels, importance, context, x=x, tables=tables)
-
-    def _intervene_by_columns(self, z, idx, vals, context):
-        """MADE conditioner: the column sweep with a pin table (gnf_made_prefix_do).  x[:, idx] = vals is written first; a
-        pinned step reads its column instead of computing it.  Affine / Spline + MADE stay ONE launch; any other normalizer
-        is stepped through AutoregressiveConditioner.made_do_launches: one launch per FREE column, which advances through
-        the run of pinned degrees in front of it, and none for a trailing run.  Returns None when not applicable (the
-        conditions of `_invert_by_columns`)."""
-        from .Conditionners.AutoregressiveConditioner import made_do_launches
-        cond = self.conditioner
-        get_plan = getattr(cond, "prefix_plan", None)
-        if not (self.column_schedule and get_plan is not None and z.is_cuda and z.dim() == 2
-                and z.dtype == torch.float32):
-            return None
-        cond_in = int(getattr(cond, "cond_in", 0) or 0)
-        if not cond_in and context is not None:
-            return None
-        if cond_in:
-            context = checked_context(context, cond_in, z)
-            if context.device != z.device or context.dtype != torch.float32:
-                return None
-        if z.shape[0] == 0:
-            return torch.zeros_like(z)
-        plan = get_plan(with_context=True) if cond_in else get_plan()
-        if plan is None or plan["d"] != z.shape[1]:
-            return None
-        kw = {"context": context.contiguous()} if cond_in else {}
+        kw = {} if context is None else {"context": context}
         z = z.contiguous()
         x = torch.zeros_like(z)
         B, d, out = z.shape[0], plan["d"], plan["out"]
@@ -598,82 +521,98 @@ class NormalizingFlowStep(NormalizingFlow):
             x[:, list(idx)] = vals
             if len(idx) == d:
                 return x                                # every degree is a trailing pinned one: no launch
-            pin = torch.zeros(d, dtype=torch.uint8, device=z.device)
+            pin = kw["pin"] = torch.zeros(d, dtype=torch.uint8, device=z.device)
             pin[list(idx)] = 1
-            kw["pin"] = pin
         with cond.hold_prefix_pack():
             if type(self.normalizer) is AffineNormalizer:
+                # the whole inversion, one launch
                 cond.prefix_steps(z, x, 0, d, ops.MADE_NORM_AFFINE, **kw)
                 return x
             if type(self.normalizer) is SplineNormalizer:
+                # likewise: the spline's closed-form inverse is the kernel's per-row epilogue
                 cond.prefix_steps(z, x, 0, d, ops.MADE_NORM_SPLINE, spline=(self.normalizer.nb_bins, self.normalizer.tail_bound),
                                   **kw)
                 return x
             h = torch.empty(B, out, dtype=torch.float32, device=z.device)
             ws = cond.prefix_workspace(B)
-            zt = z.t().contiguous()
+            zt = z.t().contiguous()                                          # a column of z as a one-row [1, B] problem
             cols = torch.arange(d, dtype=torch.int32, device=z.device)
             into = getattr(self.normalizer, "inverse_transform_into", None)
             for t0, t1 in made_do_launches(plan["var_host"], idx):
                 v = plan["var_host"][t1 - 1]            # the launch's one free column, behind t1 - 1 - t0 pinned ones
                 cond.prefix_steps(z, x, t0, t1, ops.MADE_NORM_NONE, h_out=h, ws=ws, **kw)
+                # the normalizer's own inverse of that one column; the fused Monotonic kernel writes x[:, v] itself
                 if into is None or not into(zt[v:v + 1], h.view(1, B, out), x, cols[v:v + 1]):
                     x[:, v:v + 1] = self.normalizer.inverse_transform(z[:, v:v + 1], h.view(B, 1, out), context)
         return x
 
-    def _refuse_stochastic_gate(self):
+    def _invert_by_passes(self, z, context, idx=(), vals=None):
+        """Reference :98-107: fixed point of x <- normalizer^-1(z, conditioner(x)) from x = 0, depth() + 1 passes, early exit
+        once a pass changes nothing (its progress print is dropped).  Under do(x_idx = vals):
+        x <- where(pinned, vals, normalizer^-1(z, conditioner(x))) from where(pinned, vals, 0), on the un-mutilated graph --
+        the mutilated one is never deeper."""
+        cols = list(idx)
+        x = torch.zeros_like(z)
+        if cols:
+            x[:, cols] = vals
+            if len(cols) == z.shape[1]:
+                return x                                # no free equation: the conditioner is never asked
+        for _ in range(self.conditioner.depth() + 1):
+            previous = x
+            x = self.normalizer.inverse_transform(z, self.conditioner(x, context), context)
+            if cols:
+                x[:, cols] = vals
+            if torch.equal(x, previous):
+                break
+        return x
+
+    def _by_schedule(self, z, context, idx=(), vals=None, capture=False):
+        """(x, arm) from the schedule `_fast_arm` names, or (None, "passes") where none applies.  capture: `_invert_by_levels`"""
+        arm = self._fast_arm(z, context)
+        if arm is not None and arm[0] == "columns":
+            return self._invert_by_columns(z, arm[1], arm[2], idx, vals), "columns"
+        x = None if arm is None else self._invert_by_levels(z, arm[1], arm[2], idx, vals, capture)
+        return x, ("passes" if x is None else "levels")
+
+    def invert(self, z, context=None):
+        """x with forward(x, context) = z: by levels (DAG), by columns (MADE), or by the reference's fixed-point passes"""
+        with torch.no_grad(), contextlib.ExitStack() as stack:   # parameters do not change inside: build their images once
+            for _, _, make in self._holders():
+                stack.enter_context(make())
+            x, _ = self._by_schedule(z, context, capture=True)
+            return self._invert_by_passes(z, context) if x is None else x
+
+    # -- interventions ------------------------------------------------------------------------------------------
+    def _refuse_stochastic_gate(self, what, why):
         cond = self.conditioner
         if _is_dag(cond) and cond.deterministic_importance() is None:
-            raise ValueError("NormalizingFlowStep.intervene: the DAG conditioner's gate is stochastic (stoch_gate / noise_gate); "
-                             "every evaluation of the conditioner would draw another graph than the one the intervention "
-                             "cuts.  Use a deterministic gate (stoch_gate = noise_gate = False)")
+            raise ValueError("NormalizingFlowStep.%s: the DAG conditioner's gate is stochastic (stoch_gate / noise_gate); %s.  "
+                             "Use a deterministic gate (stoch_gate = noise_gate = False)" % (what, why))
+
+    _EVERY_DRAW = "every evaluation of the conditioner would draw another graph than the one the intervention cuts"
 
     def intervene(self, z, do_index, do_value, context=None):
         """x under do(x[:, do_index] = do_value) (interventions):  x[b, i] = do_value[b, i] exactly for a pinned
         i, x[b, i] = normalizer^-1(z[b, i], conditioner(x, context)[b, i]) for every other; z[:, do_index] is ignored.  An
         empty do_index is invert(z, context), bit for bit.  Three arms on invert's conditions (`level_schedule`,
-        `column_schedule`), recorded in `_intervene_arm`: "levels" (DAG), "columns" (MADE), "passes" (anything, anywhere:
-        x <- where(pinned, v, normalizer^-1(z, conditioner(x))) from where(pinned, v, 0), depth() + 1 passes of the
-        un-mutilated graph -- the mutilated one is never deeper -- with invert's early exit).
+        `column_schedule`), recorded in `_intervene_arm`: "levels" (DAG), "columns" (MADE), "passes" (anything, anywhere).
+        Launch by launch: no graph is captured, and invert's schedule and its captured graphs are not touched.
 
         A DAG conditioner with a stochastic or noisy gate is refused as rsample refuses it: every pass and every level
         would draw another graph to mutilate."""
-        import contextlib
-        cond = self.conditioner
-        self._refuse_stochastic_gate()
+        self._refuse_stochastic_gate("intervene", self._EVERY_DRAW)
         idx, vals = do_arguments(do_index, do_value, z)
         self._intervene_arm = None
         with torch.no_grad(), contextlib.ExitStack() as stack:
             for _, _, make in self._holders():
                 stack.enter_context(make())
-            x = self._intervene_by_levels(z, idx, vals, context)
-            if x is not None:
-                self._intervene_arm = "levels"
-                return x
-            x = self._intervene_by_columns(z, idx, vals, context)
-            if x is not None:
-                self._intervene_arm = "columns"
-                return x
-            self._intervene_arm = "passes"
-            cols = list(idx)
-            x = torch.zeros_like(z)
-            if cols:
-                x[:, cols] = vals
-            if len(cols) == z.shape[1]:
-                return x                                # no free equation: the conditioner is never asked
-            for _ in range(cond.depth() + 1):
-                previous = x
-                x = self.normalizer.inverse_transform(z, cond(x, context), context)
-                if cols:
-                    x[:, cols] = vals
-                if torch.equal(x, previous):
-                    break
-        return x
+            x, self._intervene_arm = self._by_schedule(z, context, idx, vals)
+            return self._invert_by_passes(z, context, idx, vals) if x is None else x
 
     def counterfactual(self, x, do_index, do_value, context=None):
         """abduction, then action: z = forward(x, context), then intervene(z, ...).  No column is copied from x: what a
         non-descendant of the pinned variables comes back as is the inversion's own residual."""
-        self._refuse_stochastic_gate()
+        self._refuse_stochastic_gate("intervene", self._EVERY_DRAW)
         do_arguments(do_index, do_value, x)             # (the argument errors before the abduction's launches)
         with torch.no_grad():
             z, _ = self.forward(x, context)
@@ -688,29 +627,23 @@ class NormalizingFlowStep(NormalizingFlow):
 
         A DAG conditioner with a stochastic or noisy gate is refused: the backward re-evaluates the conditioner at the
         sample, and would draw another gate than the one the sample saw."""
-        cond = self.conditioner
-        if _is_dag(cond) and cond.deterministic_importance() is None:
-            raise ValueError("NormalizingFlowStep.rsample: the DAG conditioner's gate is stochastic (stoch_gate / noise_gate); "
-                             "the backward would recompute the conditioner under another draw of the gate than the sample "
-                             "saw.  Use a deterministic gate (stoch_gate = noise_gate = False)")
+        self._refuse_stochastic_gate("rsample", "the backward would recompute the conditioner under another draw of the gate "
+                                     "than the sample saw")
         return ops.InvertFn.apply(self, z, context, *[p for p in self.parameters() if p.requires_grad])
 
     def _adjoint_plan(self, x, context):
-        """the MADE plan of the adjoint arm when _invert_by_columns would be taken for this sample (and `adjoint_schedule`),
-        else None: the passes arm"""
+        """the MADE plan of the adjoint arm when `_fast_arm` names the column sweep for this sample (and `adjoint_schedule`,
+        and the conditioner can solve), else None: the passes arm.  Never raises: a context that `_fast_arm` would refuse
+        answers None as a missing one does"""
         cond = self.conditioner
-        get_plan = getattr(cond, "prefix_plan", None)
-        if not (self.adjoint_schedule and self.column_schedule and get_plan is not None
-                and getattr(cond, "adjoint_solve", None) is not None and x.is_cuda and x.dim() == 2
-                and x.dtype == torch.float32):
+        if not (self.adjoint_schedule and getattr(cond, "adjoint_solve", None) is not None
+                and bool(int(getattr(cond, "cond_in", 0) or 0)) == (context is not None)):
             return None
-        cond_in = int(getattr(cond, "cond_in", 0) or 0)
-        if bool(cond_in) != (context is not None):
+        try:
+            arm = self._fast_arm(x, context)
+        except ValueError:
             return None
-        if cond_in and (context.device != x.device or context.dtype != torch.float32):
-            return None
-        plan = get_plan(with_context=True) if cond_in else get_plan()
-        return plan if plan is not None and plan["d"] == x.shape[1] else None
+        return arm[1] if arm is not None and arm[0] == "columns" else None
 
     def _rsample_backward(self, x, context, params, g, want_context):
         """(lambda, dL/dcontext, [dL/dp for p in params]) of ops.InvertFn for the sample x and the cotangent g = dL/dx"""
@@ -780,40 +713,31 @@ class FCNormalizingFlow(NormalizingFlow):
         fused = (z.is_cuda and jac.is_cuda and jac.dim() == 1 and z.dim() == 2 and jac.shape[0] == z.shape[0]
                  and z.dtype == torch.float32 and jac.dtype == torch.float32)
         c = self.constraintsLoss()
-        plain_c = isinstance(c, float) and c == 0.
-        dev_c = torch.is_tensor(c) and c.is_cuda and c.dim() == 0 and c.dtype == torch.float32
-        # the fold applies to the factories' base density and to nothing that merely inherits from it: a subclass that
-        # overrides forward (tempered / scaled / conditional density) is called as the reference calls it
-        std_normal = (getattr(dens, "standard_normal", False)
-                      and getattr(type(dens), "_std_forward", None) is type(dens).forward)
-        if fused and std_normal and ops.nll_loss_fits(z) and (plain_c or dev_c):
+        if fused and _is_std_normal(dens) and ops.nll_loss_fits(z) and (_is_zero(c) or _is_device_scalar(c)):
             # constraints - mean(log|det J| + log N(z)) in ONE launch that reads z itself (the standard-normal base density of
             # the factories; any other z_log_density module is called as the reference calls it)
-            return ops.NllLossFn.apply(z, jac, None if plain_c else c)
+            return ops.NllLossFn.apply(z, jac, None if _is_zero(c) else c)
         logn = dens(z)
         if fused and logn.shape == jac.shape and jac.shape[0] > 0 and logn.dtype == torch.float32:
-            if plain_c:
-                return ops.NllMeanFn.apply(jac, logn)                            # -(jac + logn).mean(), one launch
-            if dev_c:
-                return ops.NllMeanFn.apply(jac, logn, c)                         # constraints - mean(...), the same launch
-            return c + ops.NllMeanFn.apply(jac, logn)
+            return _nll_mean(c, jac, logn)
         return c - (jac + logn).mean()
+
+    def _backwards(self, method, z, context):
+        """the steps' `method` (invert / rsample), last step to first, the flip between two steps undone"""
+        for k in range(len(self.steps) - 1, -1, -1):
+            x = getattr(self.steps[k], method)(z, context)
+            z = torch.flip(x, dims=[1]) if k else x
+        return z
 
     def invert(self, z, context=None):
         """Exact inverse of forward for any number of steps.  The reference (:166-169) visits steps[-0] == steps[0]
         first and never undoes the flip, so it only inverts nb_flow = 1 flows; for nb_flow = 1 this is
         identical to it."""
-        for k in range(len(self.steps) - 1, -1, -1):
-            x = self.steps[k].invert(z, context)
-            z = torch.flip(x, dims=[1]) if k else x
-        return z
+        return self._backwards("invert", z, context)
 
     def rsample(self, z, context=None):
         """invert(z, context), differentiable in z, the context and the parameters: the steps' rsample, last to first"""
-        for k in range(len(self.steps) - 1, -1, -1):
-            x = self.steps[k].rsample(z, context)
-            z = torch.flip(x, dims=[1]) if k else x
-        return z
+        return self._backwards("rsample", z, context)
 
     def _single_step(self, what):
         if len(self.steps) != 1:
@@ -834,9 +758,7 @@ class FCNormalizingFlow(NormalizingFlow):
         """the single step of a flow whose likelihood can be truncated; ValueError otherwise"""
         step = self._single_step(what)
         dens = self.z_log_density
-        # the test `loss` uses for its fold: the factories' standard normal itself, nothing that merely inherits from it
-        if not (getattr(dens, "standard_normal", False)
-                and getattr(type(dens), "_std_forward", None) is type(dens).forward):
+        if not _is_std_normal(dens):                    # (the test `loss` uses for its fold)
             raise ValueError("%s.%s: the truncated factorisation drops the pinned variables' terms log N(z_i) of a FACTORISED "
                              "base density; z_log_density here is %s, not the factories' standard normal, and a joint density "
                              "has no per-variable terms to truncate" % (type(self).__name__, what, type(dens).__name__))
@@ -852,12 +774,7 @@ class FCNormalizingFlow(NormalizingFlow):
         """constraintsLoss() - mean_b log p(x_b | do(x_S(b))): the training loss on a mix of observational and interventional
         rows, through the batch-mean launch of `loss` (ops.NllMeanFn)"""
         _, logdet, logn = self._do_step("loss_do").forward_do(x, targets, regime, context, check_regime)
-        c = self.constraintsLoss()
-        if isinstance(c, float) and c == 0.:
-            return ops.NllMeanFn.apply(logdet, logn)
-        if torch.is_tensor(c) and c.is_cuda and c.dim() == 0 and c.dtype == torch.float32:
-            return ops.NllMeanFn.apply(logdet, logn, c)
-        return c + ops.NllMeanFn.apply(logdet, logn)
+        return _nll_mean(self.constraintsLoss(), logdet, logn)
 
     def counterfactual(self, x, do_index, do_value, context=None):
         """the single step's counterfactual; ValueError for a flow of several steps"""

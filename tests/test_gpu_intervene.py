@@ -518,19 +518,21 @@ def test_level_counts_of_the_mutilated_chain():
     step = _dag_step("chain", d, 0, "affine")
     cond = step.conditioner
     imp = cond.deterministic_importance()
-    assert len(step._levels(imp)[0]) == d
-    levels, _ = step._do_levels(imp, (0,))
+    own = step._levels(imp)
+    assert len(own[0]) == d
+    levels, _ = step._levels(imp, (0,))
     assert len(levels) == d - 1 and [h for _, h in levels] == [(t,) for t in range(1, d)]      # the root pinned
-    levels, _ = step._do_levels(imp, (3,))
+    levels, _ = step._levels(imp, (3,))
     assert [h for _, h in levels] == [(0,), (1, 4), (2, 5)]                                    # the middle pinned: two chains
-    levels, _ = step._do_levels(imp, (d - 1,))
+    levels, _ = step._levels(imp, (d - 1,))
     assert len(levels) == d - 1
-    levels, tables = step._do_levels(imp, tuple(range(d)))
+    levels, tables = step._levels(imp, tuple(range(d)))
     assert levels == [] and tables == (None, None)
-    assert step._do_levels(imp, (3,)) is step._do_levels(imp, (3,))                            # cached
+    assert step._levels(imp, (3,)) is step._levels(imp, (3,))                                  # cached
     for pair in itertools.combinations(range(d), 2):                                           # ... and bounded
-        step._do_levels(imp, pair)
-        assert len(step._do_levels_cache) <= step.DO_LEVELS_MAX
+        step._levels(imp, pair)
+        assert len(step._levels_do) <= step.DO_LEVELS_MAX
+    assert step._levels(imp) is own                                                            # ... beside invert's own, kept
 
 
 @pytest.mark.parametrize("d", [6, 43])
@@ -542,12 +544,17 @@ def test_intervene_leaves_inverts_cache_and_graph_alone(d):
     xs = [step.invert(z) for _ in range(3)]                 # eager, captured, replayed
     entry = _INV_GRAPHS.get(step)
     assert entry and any(isinstance(e, tuple) for e in entry.values()), "no graph was captured: the test shows nothing"
-    key, val, all_rows = step._levels_key, step._levels_val, step._levels_all
+    imp = step.conditioner.deterministic_importance()
+    key, own = step._levels_own                             # invert's schedule: (levels, (all rows, int32 rows)) and its key
+    assert step._levels(imp) is own
     graphs = dict(entry)
-    for idx in ([0], [2, 3], []):
+    # more pinned sets than DO_LEVELS_MAX (all 15 pairs of the first six variables): the mutilated cache overflows and clears
+    pins = [[0], [2, 3], []] + [list(p) for p in itertools.combinations(range(6), 2)]
+    assert len(pins) > step.DO_LEVELS_MAX + 3
+    for idx in pins:
         step.intervene(z, idx, v[:, idx])
-        assert step._intervene_arm == "levels"
-    assert step._levels_key == key and step._levels_val is val and step._levels_all is all_rows
+        assert step._intervene_arm == "levels" and len(step._levels_do) <= step.DO_LEVELS_MAX
+    assert step._levels_own[0] == key and step._levels_own[1] is own and step._levels(imp) is own
     assert _INV_GRAPHS.get(step) == graphs                  # the same entries, none added: no graph for an intervention
     after = [step.invert(z) for _ in range(2)]
     assert all(torch.equal(x, xs[0]) for x in xs + after)

@@ -43,6 +43,7 @@ WORKSPACES = {
     "gnf_dag_gate_bwd_cols_ws_bytes": ["test_dag_conv_front_on_its_plan"],
     "gnf_monotonic_bwd_ws_bytes": ["test_monotonic_through_ops", "test_monotonic_backward_in_chunks",
                                    "test_monotonic_narrow_backward_true_f32"],
+    # (ops.py asks gnf_made_prefix_ctx_ws_bytes with cond_in = 0, which this one forwards to: the same workspace)
     "gnf_made_prefix_ws_bytes": ["test_made_inversion", "test_made_whole_inversion_in_the_workspace_form",
                                  "test_made_prefix_reads_only_lower_degrees", "test_made_monotonic_step_inverts_by_columns"],
     "gnf_made_prefix_ctx_ws_bytes": ["test_made_inversion"],
