@@ -24,6 +24,7 @@ MADE_MAX_HIDDEN = 8       # GNF_MADE_MAX_HIDDEN
 MADE_NORM_NONE, MADE_NORM_AFFINE = 0, 1
 MADE_NORM_SPLINE = 2      # GNF_MADE_NORM_SPLINE: gnf_made_prefix_spline / gnf_made_prefix_ctx_spline only
 SPLINE_MIN_BINS, SPLINE_MAX_BINS = 2, 32
+STRADE_CHUNK_VARS = 8     # GNF_STRADE_CHUNK_VARS: variables per output product of gnf_strade_levels
 DAG_PLAN_KC = 32          # GNF_DAG_PLAN_KC
 DAG_ELEM_F32, DAG_ELEM_U8 = 0, 1      # GNF_DAG_ELEM_*
 ABI_VERSION = 11          # GNF_ABI_VERSION of include/gnf_hip.h this binding was written against
@@ -41,6 +42,12 @@ class MadeNet(ctypes.Structure):
                 ("W", ctypes.c_void_p * (MADE_MAX_HIDDEN + 1)), ("b", ctypes.c_void_p * (MADE_MAX_HIDDEN + 1)),
                 ("order", ctypes.c_void_p * MADE_MAX_HIDDEN), ("off", ctypes.c_void_p * MADE_MAX_HIDDEN),
                 ("var_of_step", ctypes.c_void_p)]
+
+
+class StradeNet(ctypes.Structure):
+    """gnf_strade_net (include/gnf_hip.h): a gnf_made_net whose tables are read by level, the masks, the level offsets."""
+    _fields_ = [("made", MadeNet), ("mask", ctypes.c_void_p * (MADE_MAX_HIDDEN + 1)), ("var_off", ctypes.c_void_p),
+                ("nlev", c_int), ("widest", c_int)]
 
 
 # name -> (restype, argtypes); must list every symbol include/gnf_hip.h declares
@@ -141,6 +148,10 @@ SIGNATURES = {
                                            c_int, c_double, c_i64, ctypes.c_void_p, c_i64, c_stream]),
     "gnf_made_prefix_do": (c_int, [ctypes.POINTER(MadeNet), c_int, c_f, c_f, c_f, c_f, c_f, c_int, c_int, c_int, c_int,
                                    c_double, ctypes.c_void_p, c_i64, ctypes.c_void_p, c_i64, c_stream]),
+    "gnf_strade_pack_floats": (c_i64, [ctypes.POINTER(StradeNet), c_int]),
+    "gnf_strade_pack": (c_int, [ctypes.POINTER(StradeNet), c_int, c_f, c_stream]),
+    "gnf_strade_levels": (c_int, [ctypes.POINTER(StradeNet), c_int, c_f, c_f, c_f, c_f, c_int, c_int, c_double,
+                                  ctypes.c_void_p, c_i64, c_stream]),
     "gnf_made_adjoint_pack_floats": (c_i64, [ctypes.POINTER(MadeNet), c_int]),
     "gnf_made_adjoint_pack": (c_int, [ctypes.POINTER(MadeNet), c_int, c_f, c_stream]),
     "gnf_made_adjoint_ws_bytes": (c_i64, [ctypes.POINTER(MadeNet), c_int, c_i64]),

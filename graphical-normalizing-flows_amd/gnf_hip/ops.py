@@ -348,6 +348,78 @@ def made_prefix_steps(params, plan, pack, z, x, t0, t1, mode, h_out=None, ws=Non
     return x
 
 
+# ----------------------------------------------------------------------------- StrADE level sweep
+def _strade_net(params, masks, plan):
+    """params [W0, b0, ..., W_out, b_out], masks [M0, ..., M_out] (fp32, the layout of the weights) of a StrADE net; plan:
+    StrADEConditioner.level_plan() -> gnf_strade_net: the gnf_made_net of _made_net with the plan's level tables where the
+    degree tables stand, the masks and the level offsets.  Raw pointers: the caller keeps all three alive."""
+    net = abi.StradeNet()
+    net.made = _made_net(params, {"widths": plan["widths"], "d": plan["d"], "out": plan["out"], "max_new": plan["max_new"],
+                                  "cond_in": plan["cond_in"], "order": plan["order"], "off": plan["off"],
+                                  "var_of_step": plan["var_order"]})
+    if len(masks) != len(params) // 2:
+        raise abi.GnfError("StrADE level kernel: one mask per layer")
+    for l, M in enumerate(masks):
+        W = params[2 * l]
+        if tuple(M.shape) != tuple(W.shape) or M.device != W.device or not M.is_contiguous():
+            raise abi.GnfError("StrADE level kernel: mask %d is not a contiguous fp32 %s tensor on the weights' device"
+                               % (l, tuple(W.shape)))
+        net.mask[l] = ptr(M).value
+    net.var_off = abi.rawptr(plan["var_off"]).value
+    net.nlev, net.widest = plan["nlev"], plan["widest"]
+    return net
+
+
+@torch.no_grad()
+def strade_pack(params, masks, plan):
+    """the level kernel's weight image (mask o W and the biases in level order, a masked entry an exact zero):
+    parameter-only, one launch (StrADEConditioner.hold_level_pack builds it once for several sweeps)"""
+    params = [p.detach() for p in params]
+    net, c = _strade_net(params, masks, plan), _plan_cond_in(plan)
+    nfl = abi.load().gnf_strade_pack_floats(ctypes.byref(net), c)
+    if nfl < 0:
+        abi.check(int(nfl), "gnf_strade_pack_floats")
+    pack = _empty((int(nfl),), params[0])
+    call("gnf_strade_pack", ctypes.byref(net), c, ptr(pack), stream())
+    return pack
+
+
+@torch.no_grad()
+def strade_levels(params, masks, plan, pack, z, x, mode, context=None, spline=None, pin=None):
+    """The level-by-level inversion of a StrADE step, one launch of gnf_strade_levels: z, x [B, d] fp32 contiguous, x written
+    column by column (MADE_NORM_AFFINE, or MADE_NORM_SPLINE with spline = (nb_bins, tail_bound)).  context: the contiguous
+    fp32 [B, cond_in] device tensor of a conditional plan.  pin: the contiguous uint8 [d] device table of an intervention,
+    one byte per VARIABLE, non-zero = pinned: such a column of x, which the caller filled, is read and handed on.
+    Returns x -- or None, having launched nothing, where the library answers GNF_ESHAPE (the net's rows do not fit the
+    kernel's LDS tile, or the normalizer needs more outputs than the net has): the caller inverts by passes.  An empty
+    batch launches nothing."""
+    params = [p.detach() for p in params]
+    net, c = _strade_net(params, masks, plan), _plan_cond_in(plan)
+    B, d = x.shape
+    if pin is not None and (pin.dtype != torch.uint8 or pin.device != x.device or tuple(pin.shape) != (plan["d"],)
+                            or not pin.is_contiguous()):
+        raise abi.GnfError("strade_levels: pin must be a contiguous uint8 [%d] tensor on the device of x" % plan["d"])
+    if d != plan["d"] or not x.is_contiguous() or tuple(z.shape) != (B, d) or not z.is_contiguous() or z.device != x.device:
+        raise abi.GnfError("strade_levels: z and x must be contiguous [B, %d] on one device" % plan["d"])
+    if c == 0 and context is not None:
+        raise abi.GnfError("strade_levels: a context for a plan with cond_in = 0")
+    if c and (context is None or not context.is_cuda or context.device != x.device or context.dtype != torch.float32
+              or tuple(context.shape) != (B, c) or not context.is_contiguous()):
+        raise abi.GnfError("strade_levels: context must be a contiguous fp32 [B, %d] tensor on the device of x" % c)
+    bins, tail = 0, 0.
+    if int(mode) == MADE_NORM_SPLINE:
+        if spline is None:
+            raise abi.GnfError("strade_levels: MADE_NORM_SPLINE needs spline = (nb_bins, tail_bound)")
+        bins, tail = int(spline[0]), float(spline[1])
+    args = (ctypes.byref(net), c, ptr(context), ptr(pack), ptr(z), ptr(x), int(mode), bins, tail,
+            None if pin is None else ctypes.c_void_p(pin.data_ptr()), B, stream())
+    rc = int(abi.load().gnf_strade_levels(*args))       # (the shape checks come before any launch, also for B = 0)
+    if rc == -2:
+        return None
+    abi.check(rc, "gnf_strade_levels")
+    return x
+
+
 # ----------------------------------------------------------------------------- MADE adjoint sweep, rsample
 @torch.no_grad()
 def made_adjoint_pack(params, plan):

@@ -3,5 +3,6 @@ from .Conditioner import Conditioner
 from .CouplingConditioner import CouplingConditioner
 from .AutoregressiveConditioner import AutoregressiveConditioner
 from .DAGConditioner import DAGConditioner
+from .StrADEConditioner import StrADEConditioner
 
-__all__ = ["Conditioner", "AutoregressiveConditioner", "CouplingConditioner", "DAGConditioner"]
+__all__ = ["Conditioner", "AutoregressiveConditioner", "CouplingConditioner", "DAGConditioner", "StrADEConditioner"]

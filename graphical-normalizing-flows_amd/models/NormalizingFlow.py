@@ -371,8 +371,10 @@ class NormalizingFlowStep(NormalizingFlow):
     def _fast_arm(self, z, context):
         """which schedule inverts (z, context), and with what: ("levels", importance, checked context) for a DAG conditioner
         with a deterministic gate (`level_schedule`), ("columns", plan, checked contiguous context) for a MADE whose masks
-        are its degree rule (`column_schedule`; the plan is None for an empty batch, which needs none), None for the
-        fixed-point passes.  A conditioner built with cond_in > 0 has its context checked first -- ValueError: missing, wrong
+        are its degree rule (`column_schedule`; the plan is None for an empty batch, which needs none), ("strade", level plan,
+        checked contiguous context) for a StrADE conditioner whose masks are the rule's masks for its adjacency, under an
+        Affine or Spline normalizer (the same switch, `column_schedule`: False sends MADE and StrADE alike to the passes), None
+        for the fixed-point passes.  A conditioner built with cond_in > 0 has its context checked first -- ValueError: missing, wrong
         width / rank / rows; one with cond_in = 0 that is given a context goes to the passes, which raise what it raises."""
         cond = self.conditioner
         cond_in = int(getattr(cond, "cond_in", 0) or 0)
@@ -384,19 +386,25 @@ class NormalizingFlowStep(NormalizingFlow):
                 importance = cond.deterministic_importance()
                 if importance is not None:
                     return "levels", importance, ctx
-        get_plan = getattr(cond, "prefix_plan", None)
-        if not (self.column_schedule and get_plan is not None and z.is_cuda and z.dim() == 2
+        get_plan, get_levels = getattr(cond, "prefix_plan", None), getattr(cond, "level_plan", None)
+        if not (self.column_schedule and (get_plan is not None or get_levels is not None) and z.is_cuda and z.dim() == 2
                 and z.dtype == torch.float32):
             return None
+        if get_plan is None and type(self.normalizer) not in (AffineNormalizer, SplineNormalizer):
+            return None                                 # the level kernel inverts in its epilogue: these two or the passes
         if cond_in:
             context = checked_context(context, cond_in, z)
             if context.device != z.device or context.dtype != torch.float32:
                 return None
             context = context.contiguous()
+        name = "columns" if get_plan is not None else "strade"
         if z.shape[0] == 0:
-            return "columns", None, context
-        plan = get_plan(with_context=True) if cond_in else get_plan()
-        return ("columns", plan, context) if plan is not None and plan["d"] == z.shape[1] else None
+            return name, None, context
+        if get_plan is None:
+            plan = get_levels()
+        else:
+            plan = get_plan(with_context=True) if cond_in else get_plan()
+        return (name, plan, context) if plan is not None and plan["d"] == z.shape[1] else None
 
     def _invert_by_levels(self, z, importance, context, idx=(), vals=None, capture=False):
         """DAG conditioner with a deterministic gate: every variable is inverted once, after its parents -- d
@@ -546,6 +554,37 @@ class NormalizingFlowStep(NormalizingFlow):
                     x[:, v:v + 1] = self.normalizer.inverse_transform(z[:, v:v + 1], h.view(B, 1, out), context)
         return x
 
+    def _invert_by_strade(self, z, plan, context, idx=(), vals=None):
+        """StrADE conditioner (a masked net over a given DAG) with an Affine or Spline normalizer: the variables are inverted
+        level by level in ONE launch (StrADEConditioner.level_sweep, gnf_strade_levels), every hidden unit computed once,
+        when the variables of its parent set are known -- where the passes below spend depth() + 1 masked forwards and
+        normalizer inverses.  The same function in another fp32 summation order.  The conditioner module is never called;
+        a context heads the kernel's activation rows.
+
+        Under do(x_idx = vals) the sweep takes a pin table: x[:, idx] = vals is written first, a pinned variable keeps its
+        level and its column is read instead of computed.  Returns None, having launched nothing, when the net's rows do not
+        fit the kernel's LDS tile: the passes serve."""
+        cond = self.conditioner
+        if z.shape[0] == 0:
+            return torch.zeros_like(z)                  # no rows, no launch
+        kw = {} if context is None else {"context": context}
+        z = z.contiguous()
+        x = torch.zeros_like(z)
+        d = plan["d"]
+        if idx:
+            x[:, list(idx)] = vals
+            if len(idx) == d:
+                return x                                # no free equation: no launch
+            pin = kw["pin"] = torch.zeros(d, dtype=torch.uint8, device=z.device)
+            pin[list(idx)] = 1
+        if type(self.normalizer) is SplineNormalizer:
+            kw["spline"] = (self.normalizer.nb_bins, self.normalizer.tail_bound)
+            mode = ops.MADE_NORM_SPLINE
+        else:
+            mode = ops.MADE_NORM_AFFINE
+        with cond.hold_level_pack():
+            return cond.level_sweep(z, x, mode, **kw)
+
     def _invert_by_passes(self, z, context, idx=(), vals=None):
         """Reference :98-107: fixed point of x <- normalizer^-1(z, conditioner(x)) from x = 0, depth() + 1 passes, early exit
         once a pass changes nothing (its progress print is dropped).  Under do(x_idx = vals):
@@ -571,6 +610,9 @@ class NormalizingFlowStep(NormalizingFlow):
         arm = self._fast_arm(z, context)
         if arm is not None and arm[0] == "columns":
             return self._invert_by_columns(z, arm[1], arm[2], idx, vals), "columns"
+        if arm is not None and arm[0] == "strade":
+            x = self._invert_by_strade(z, arm[1], arm[2], idx, vals)
+            return x, ("passes" if x is None else "strade")
         x = None if arm is None else self._invert_by_levels(z, arm[1], arm[2], idx, vals, capture)
         return x, ("passes" if x is None else "levels")
 
@@ -595,7 +637,8 @@ class NormalizingFlowStep(NormalizingFlow):
         """x under do(x[:, do_index] = do_value) (interventions):  x[b, i] = do_value[b, i] exactly for a pinned
         i, x[b, i] = normalizer^-1(z[b, i], conditioner(x, context)[b, i]) for every other; z[:, do_index] is ignored.  An
         empty do_index is invert(z, context), bit for bit.  Three arms on invert's conditions (`level_schedule`,
-        `column_schedule`), recorded in `_intervene_arm`: "levels" (DAG), "columns" (MADE), "passes" (anything, anywhere).
+        `column_schedule`), recorded in `_intervene_arm`: "levels" (DAG), "columns" (MADE), "strade" (StrADE, Affine / Spline),
+        "passes" (anything, anywhere).
         Launch by launch: no graph is captured, and invert's schedule and its captured graphs are not touched.
 
         A DAG conditioner with a stochastic or noisy gate is refused as rsample refuses it: every pass and every level

@@ -35,7 +35,10 @@ class NormalLogDensity(nn.Module):
 
 
 def buildFCNormalizingFlow(nb_steps, conditioner_type, conditioner_args, normalizer_type, normalizer_args):
-    """`nb_steps` independent (conditioner, normalizer) pairs on a standard-normal base density (reference :19-32)."""
+    """`nb_steps` independent (conditioner, normalizer) pairs on a standard-normal base density (reference :19-32).
+    conditioner_type: a class, or the name "StrADE" for StrADEConditioner (its graph: conditioner_args["adjacency"])."""
+    if conditioner_type == "StrADE":
+        conditioner_type = StrADEConditioner    # noqa: F405
     return FCNormalizingFlow([NormalizingFlowStep(conditioner_type(**conditioner_args),
                                                   normalizer_type(**normalizer_args)) for _ in range(nb_steps)],
                              NormalLogDensity())

@@ -38,10 +38,11 @@ import yaml
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from models import (buildFCNormalizingFlow, DAGConditioner, CouplingConditioner, AutoregressiveConditioner,  # noqa: E402
-                    AffineNormalizer, MonotonicNormalizer, SplineNormalizer)
+                    StrADEConditioner, AffineNormalizer, MonotonicNormalizer, SplineNormalizer)
 from gnf_hip import dp  # noqa: E402
 
-COND = {"DAG": DAGConditioner, "Coupling": CouplingConditioner, "Autoregressive": AutoregressiveConditioner}
+COND = {"DAG": DAGConditioner, "Coupling": CouplingConditioner, "Autoregressive": AutoregressiveConditioner,
+        "StrADE": StrADEConditioner}
 NORM = {"affine": AffineNormalizer, "monotonic": MonotonicNormalizer, "spline": SplineNormalizer}
 DIMS = {"power": 6, "gas": 8, "hepmass": 21, "miniboone": 43, "bsds300": 63, "digits": 64, "proteins": 11}
 
@@ -122,6 +123,25 @@ def shard_batches(n, b, rank, world, gen):
     return out
 
 
+def load_adjacency(path, dim):
+    """the [dim, dim] 0/1 graph of -adjacency: a .npy array (adjacency[i][j] = 1: x_j is a parent of x_i), or a checkpoint
+    (state_dict) of a one-step DAG flow, whose get_dag() is taken after post_process(); None without a path"""
+    if path is None:
+        return None
+    if path.endswith(".npy"):
+        return np.load(path)
+    sd = torch.load(path, map_location="cpu")
+    keys = [k for k in sd if k.endswith("conditioner.A")]
+    if len(keys) != 1:
+        raise ValueError("-adjacency %s: a checkpoint of a ONE-step DAG flow is needed (found %d DAG conditioners)"
+                         % (path, len(keys)))
+    cond = DAGConditioner(dim, [8], 2)
+    with torch.no_grad():
+        cond.A.copy_(sd[keys[0]])
+    cond.post_process()                                   # (a no-op on a checkpoint saved after it: A is 0/1 already)
+    return (cond.get_dag().A.detach().cpu() != 0).to(torch.uint8).numpy()
+
+
 def build(args, dim):
     cond_t, norm_t = COND[args.conditioner], NORM[args.normalizer]
     cargs = {"in_size": dim, "hidden": args.emb_net[:-1], "out_size": args.emb_net[-1]}
@@ -129,6 +149,11 @@ def build(args, dim):
         cargs["cond_in"] = args.context_cols
     if cond_t is DAGConditioner:          # reference :83-88 (gumble_T is pinned to .5 there)
         cargs.update(l1=args.l1, gumble_T=.5, nb_epoch_update=args.nb_steps_dual, hot_encoding=True)
+    if cond_t is StrADEConditioner:       # a masked net over a GIVEN graph; without -adjacency the full triangular one
+        if args.nb_flow > 1:
+            raise ValueError("-conditioner StrADE with -nb_flow %d: one graph describes the data-side variables of a ONE-step "
+                             "flow; the variables between two steps are flipped and are not the data's" % args.nb_flow)
+        cargs["adjacency"] = load_adjacency(getattr(args, "adjacency", None), dim)
     nargs = {}
     if norm_t is MonotonicNormalizer:
         nargs = {"integrand_net": args.int_net, "cond_size": args.emb_net[-1], "nb_steps": args.nb_steps,
@@ -478,6 +503,9 @@ def parse(argv=None):
     ap.add_argument("-nb_epoch", default=10000, type=int)
     ap.add_argument("-b_size", default=100, type=int)
     ap.add_argument("-conditioner", default="DAG", choices=sorted(COND))
+    ap.add_argument("-adjacency", default=None, type=str,
+                    help="-conditioner StrADE: the graph, a [d, d] .npy array (row i: the parents of x_i) or a checkpoint of a "
+                         "one-step DAG flow (its get_dag() after post_process()); default: the full triangular graph")
     ap.add_argument("-emb_net", default=[100, 100, 100, 10], nargs="+", type=int)
     ap.add_argument("-nb_steps_dual", default=100, type=int)
     ap.add_argument("-l1", default=.2, type=float)
@@ -520,6 +548,10 @@ def parse(argv=None):
         ap.error("-sample must not be negative")
     if args.context_cols < 0:
         ap.error("-context_cols must not be negative")
+    if args.conditioner == "StrADE" and args.nb_flow > 1:
+        ap.error("-conditioner StrADE with -nb_flow > 1: one graph describes the data-side variables of a ONE-step flow")
+    if args.adjacency is not None and args.conditioner != "StrADE":
+        ap.error("-adjacency needs -conditioner StrADE")
     if args.do and args.sample <= 0:
         ap.error("-do needs -sample N (the interventional samples are drawn from the z of the plain ones)")
     if args.steps_per_replay > 1 and not args.device_batches:

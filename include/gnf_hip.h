@@ -39,7 +39,8 @@ extern "C" {
 #endif
 
 /* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_*, gnf_image_prep, gnf_dagmlp_*, gnf_dag_levels*, gnf_toy_sample, gnf_shuffle_keys, gnf_tab_batch, gnf_group_bias_*, gnf_spline_*, gnf_made_prefix*_spline, gnf_made_prefix_do, gnf_nll_do_* and gnf_affine_do_* were ADDED under this number (no existing symbol
- * changed; a binding written against the earlier 11 keeps working, and tests/test_cifar_factory.py pins the value) */
+ * changed; a binding written against the earlier 11 keeps working, and tests/test_cifar_factory.py pins the value);
+ * gnf_strade_* likewise */
 #define GNF_ABI_VERSION 11
 #define GNF_EINVAL (-1)   /* bad argument (null pointer, negative size, ...)          */
 #define GNF_ESHAPE (-2)   /* shape not supported by any compiled kernel instantiation */
@@ -473,6 +474,49 @@ int gnf_made_prefix_do(const gnf_made_net* net, int cond_in, const float* contex
                        float* h_out, int t0, int t1, int normalizer_mode, int spline_bins, double spline_tail,
                        const uint8_t* pin /* [d], by VARIABLE, device */, int64_t B, void* ws, int64_t ws_bytes,
                        gnf_stream_t stream);
+
+/* ---- StrADE level sweep: inverting a masked net over a GIVEN DAG level by level (StrADEConditioner) --------------------
+ * The prefix kernel's idea with "degree" replaced by "topological level": a MADE whose masks encode an arbitrary DAG
+ * (models/Conditionners/StrADEConditioner.py: strade_masks) assigns every hidden unit a parent set; the unit's level is the
+ * largest level of a variable in its set (-1 for the empty set) and it is FINAL once the variables of the levels up to its
+ * own are known.  Level t of the sweep computes, layer by layer, the hidden units of level t - 1 from the units of level
+ * < t below them, then the outputs of EVERY variable of level t, inverts those variables and hands them on.  Units and
+ * variables are kept in LEVEL order, so "every unit of level < t" is a contiguous K range; inside that range the entries
+ * the mask forbids are exact zeros of the weight image, which gnf_strade_pack writes as mask ? W : 0.
+ *   net->made: the descriptor of gnf_made_prefix with the tables read by LEVEL: order[l] [width[l]] = the units of layer l
+ *     in a stable sort by level, off[l] [nlev + 1] with off[l][t] = number of units of level < t (the empty-set units
+ *     count from t = 0 on), var_of_step [d] = the variables in a stable sort by level, max_new = the largest number of
+ *     units of one level (the last excepted) in a layer.
+ *   mask[l], l = 0..nh: the fp32 0/1 masks in the layout of W[l]; read by gnf_strade_pack alone.
+ *   var_off [nlev + 1] (device, int32): var_off[t] = number of variables of level < t; nlev = depth + 1 levels,
+ *     1 <= nlev <= d; widest (host) = the largest number of variables of one level.
+ *   pack: >= gnf_strade_pack_floats(net, cond_in) floats, 16-byte aligned (else GNF_EINVAL), written by gnf_strade_pack;
+ *     parameter-only, valid until a parameter, a mask or the graph changes.
+ *   gnf_strade_levels: the whole inversion of B rows in ONE launch, the tile's activation rows
+ *     [context | x in level order | hidden 0 | ...] in LDS only (no workspace).  z, x [B, d] and context [B, cond_in]
+ *     contiguous, dword-aligned rows, nothing more is assumed.  normalizer_mode: GNF_MADE_NORM_AFFINE (out >= 2) or
+ *     GNF_MADE_NORM_SPLINE (out >= 3 spline_bins - 1; bins and tail as for gnf_spline_inv), with the arithmetic of
+ *     gnf_affine_inv / gnf_spline_inv; any other mode is GNF_EINVAL.  The outputs of a level are produced in chunks of
+ *     GNF_STRADE_CHUNK_VARS variables.
+ *   pin: NULL, or [d] bytes on the device, one per VARIABLE, non-zero = pinned (do(x_P = v), as gnf_made_prefix_do): a
+ *     pinned variable keeps its level and x[b, v], which the caller filled, is handed on in place of outputs and inverse;
+ *     a chunk whose variables are all pinned computes no output product.  pin == NULL is a kernel without that branch.
+ *   fp32 with a fixed summation order for a given (net, cond_in, B); no atomics; rows never interact.  B == 0 launches
+ *   nothing.  GNF_ESHAPE when a tile of 4 rows does not fit in LDS (160 KB): the caller inverts by passes.  GNF_EINVAL:
+ *   a NULL table or operand with rows to compute, nlev outside 1..d, widest outside 1..d, cond_in < 0, B < 0. */
+#define GNF_STRADE_CHUNK_VARS 8
+typedef struct {
+  gnf_made_net made;
+  const float* mask[GNF_MADE_MAX_HIDDEN + 1];
+  const int32_t* var_off;
+  int nlev;
+  int widest;
+} gnf_strade_net;
+int64_t gnf_strade_pack_floats(const gnf_strade_net* net, int cond_in);
+int gnf_strade_pack(const gnf_strade_net* net, int cond_in, float* pack, gnf_stream_t stream);
+int gnf_strade_levels(const gnf_strade_net* net, int cond_in, const float* context, const float* pack, const float* z,
+                      float* x, int normalizer_mode, int spline_bins, double spline_tail,
+                      const uint8_t* pin /* [d], by VARIABLE, device, or NULL */, int64_t B, gnf_stream_t stream);
 
 /* ---- MADE adjoint sweep: lambda with J^T lambda = g for one MADE step (NormalizingFlowStep.rsample's backward) ----------
  * The step is z = S(x; context): h = MADE(context, x), z[b, i] = normalizer(x[b, i], h[b, i, :]).  In degree order
