@@ -124,6 +124,8 @@ SIGNATURES = {
                                   c_i64, c_i64, c_stream]),
     "gnf_monotonic_inv_scatter": (c_int, [c_f, ctypes.POINTER(MonoNet), c_f, c_f, c_i64, c_i64, c_i64, c_f, c_f, c_int, c_f,
                                           ctypes.c_void_p, c_i64, c_i64, c_i64, c_stream]),
+    "gnf_monotonic_inv_route": (c_int, [ctypes.POINTER(MonoNet), c_int, c_i64, c_i64, ctypes.c_char_p, c_int]),
+    "gnf_monotonic_inv_kernel": (ctypes.c_char_p, []),
     "gnf_monotonic_bwd_ws_bytes": (c_i64, [ctypes.POINTER(MonoNet), c_int, c_i64, c_i64]),
     "gnf_monotonic_bwd": (c_int, [c_f, ctypes.POINTER(MonoNet), c_f, c_f, c_i64, c_i64, c_i64, c_f, c_f, c_int, c_f,
                                   c_f, c_f, c_f, c_i64, c_i64, c_i64, ctypes.POINTER(ctypes.c_void_p),

@@ -30,12 +30,14 @@
 #include "gnf_gemm.h"
 #include "gnf_linear_tall.h"
 #include "gnf_monotonic.h"
+#include <cstdio>
 #include <cstdlib>
 
 // kernel family of the process' last forward / backward launch (gnf_monotonic_fwd_kernel / _bwd_kernel: reporting only; NOT
 // thread-local -- autograd runs the backward on its own thread and the caller asks from another)
 static const char* volatile g_fwd_kernel = "";
 static const char* volatile g_bwd_kernel = "";
+// (the inverse's reporter keeps the route of the last launch and formats it when asked: gnf_monotonic_inv_kernel)
 
 namespace {
 
@@ -2311,10 +2313,17 @@ struct FwdImage {
       : lds(lds_fwd_image(L)), lds_one(lds_one_matrix(L)), wlds(lds <= kLdsImage), swap(!wlds && L.NH > 1 && lds_one <= kLdsImage) {}
 };
 
+// what a route instantiated, for the inverse's query and reporter (gnf_monotonic_inv_route / _inv_kernel): the family and its
+// template arguments in declaration order, written where the kernel is picked
+struct MonoTemplate {
+  const char* family;
+  struct { const char* key; int val; } arg[4];     // key == nullptr: no such argument
+};
+
 // the persistent kernels: a wavefront per 16-element group.  The forward of every narrow net but the split form below, and the
 // inverse of what has too many groups (or too few nodes) to split the quadrature over wavefronts.
 template <bool INV>
-MonoLaunch persistent_route(const MonoLayout& L, int64_t n, const FwdImage& im) {
+MonoLaunch persistent_route(const MonoLayout& L, int64_t n, const FwdImage& im, MonoTemplate* t = nullptr) {
   const int64_t ngroups = (n + 15) / 16;
   int64_t grid = (ngroups + kWaves - 1) / kWaves;
   const int64_t per_cu = ((im.wlds && im.lds > kLdsBudget / 2) || im.swap) ? 1 : 2;   // resident workgroups per CU
@@ -2323,11 +2332,13 @@ MonoLaunch persistent_route(const MonoLayout& L, int64_t n, const FwdImage& im) 
   MonoLaunch r{nullptr, (unsigned)grid, 64 * kWaves, wm == 1 ? im.lds : wm == 2 ? im.lds_one : 0, wm != 0, "mono_fwd_k"};
   if (L.EX > 0 && !im.swap)                                           // peeled narrow net (HM = 3: H in {49, 50, 51})
     r.kernel = with_ex(L.EX, [&](auto ex) -> MonoKernel {
+      if (t) *t = {"mono_fwd_x_k", {{"HM", 3}, {"EX", GNF_INT(ex)}, {"WM", im.wlds ? 1 : 0}, {"INV", INV}}};
       return im.wlds ? mono_fwd_x_k<3, GNF_INT(ex), 1, INV> : mono_fwd_x_k<3, GNF_INT(ex), 0, INV>;
     });
   else
     r.kernel = with_ht(L.HT, [&](auto ht) -> MonoKernel {
       constexpr int HT = GNF_INT(ht);
+      if (t) *t = {"mono_fwd_k", {{"HT", HT}, {"WM", wm}, {"INV", INV}, {nullptr, 0}}};
       return wm == 1 ? mono_fwd_k<HT, 1, INV> : wm == 2 ? mono_fwd_k<HT, 2, INV> : mono_fwd_k<HT, 0, INV>;
     });
   return r;
@@ -2346,10 +2357,15 @@ MonoLaunch fwd_route(const MonoLayout& L, int64_t n, bool true_f32) {
   return r;
 }
 
-MonoLaunch inv_route(const MonoLayout& L, int64_t n, int S) {
+struct InvRoute { MonoLaunch l; MonoTemplate t; };
+InvRoute inv_route(const MonoLayout& L, int64_t n, int S) {
   const FwdImage im(L);
   const int64_t ngroups = (n + 15) / 16;
-  if (im.swap || ngroups > 512 || S < 7) return persistent_route<true>(L, n, im);
+  MonoTemplate t{"", {}};
+  if (im.swap || ngroups > 512 || S < 7) {
+    const MonoLaunch p = persistent_route<true>(L, n, im, &t);
+    return {p, t};
+  }
   // fewer groups than a resident wave of workgroups: split the quadrature nodes over the workgroup's wavefronts
   const bool peeled = L.EX > 0;                                       // up to kSplitWavesX wavefronts per group, else kSplitWaves
   const bool quarter = ngroups < 256;                                 // groups of 4 elements x 4 node pairs (see above)
@@ -2364,10 +2380,13 @@ MonoLaunch inv_route(const MonoLayout& L, int64_t n, int S) {
                  im.lds + (size_t)(2 * 32 + 2 * 3 * 32 * epg + 2 * 3 * epg) * kF, true, ""};
     r.kernel = with_ex(L.EX, [&](auto ex) -> MonoKernel {
       constexpr int EX = GNF_INT(ex);
-      if (epg == 2) return ks_waves <= 8 ? mono_inv_ks_x_k<3, EX, 2, 8> : mono_inv_ks_x_k<3, EX, 2, kSplitWavesX>;
+      t = {"mono_inv_ks_x_k", {{"HM", 3}, {"EX", EX}, {"epg", epg}, {"waves", ks_waves <= 8 ? 8 : kSplitWavesX}}};
+      // two elements per workgroup: S <= 31 puts at most (48 * 2 + 15) / 16 = 6 wavefronts here, so MAXW = 8 always holds
+      // them and <3, EX, 2, kSplitWavesX> has no shape that reaches it (not instantiated)
+      if (epg == 2) return ks_waves <= 8 ? mono_inv_ks_x_k<3, EX, 2, 8> : nullptr;
       return ks_waves <= 8 ? mono_inv_ks_x_k<3, EX, 4, 8> : mono_inv_ks_x_k<3, EX, 4, kSplitWavesX>;
     });
-    return r;
+    return {r, t};
   }
   const int pairs = (S + 2) / 2, want = quarter ? (pairs + 3) / 4 : pairs, cap = peeled ? kSplitWavesX : kSplitWaves;
   const int nw = want < cap ? want : cap;
@@ -2376,15 +2395,29 @@ MonoLaunch inv_route(const MonoLayout& L, int64_t n, int S) {
     constexpr int EPG = GNF_INT(epg_);
     if (peeled)
       return with_ex(L.EX, [&](auto ex) -> MonoKernel {
+        t = {"mono_inv_split_x_k", {{"HM", 3}, {"EX", GNF_INT(ex)}, {"WM", im.wlds ? 1 : 0}, {"EPG", EPG}}};
         return im.wlds ? mono_inv_split_x_k<3, GNF_INT(ex), 1, EPG> : mono_inv_split_x_k<3, GNF_INT(ex), 0, EPG>;
       });
     return with_ht(L.HT, [&](auto ht) -> MonoKernel {
+      t = {"mono_inv_split_k", {{"HT", GNF_INT(ht)}, {"WM", im.wlds ? 1 : 0}, {"EPG", EPG}, {nullptr, 0}}};
       return im.wlds ? mono_inv_split_k<GNF_INT(ht), 1, EPG> : mono_inv_split_k<GNF_INT(ht), 0, EPG>;
     });
   };
   r.kernel = quarter ? pick(Int<4>{}) : pick(Int<16>{});
-  return r;
+  return {r, t};
 }
+
+// one line per inverse route: "family<KEY=value,...> block=.. grid=.. lds=.." (the query and the reporter share it).
+// -> characters written, or -1 where buf is too short
+int format_inv_route(const InvRoute& r, char* buf, int len) {
+  int o = snprintf(buf, len, "%s<", r.t.family);
+  for (int i = 0; i < 4 && r.t.arg[i].key && o >= 0 && o < len; ++i)
+    o += snprintf(buf + o, len - o, "%s%s=%d", i ? "," : "", r.t.arg[i].key, r.t.arg[i].val);
+  if (o >= 0 && o < len) o += snprintf(buf + o, len - o, "> block=%u grid=%u lds=%zu", r.l.block, r.l.grid, r.l.lds);
+  return o >= 0 && o < len ? o : -1;
+}
+InvRoute g_inv_route{{}, {"", {}}};      // the last inverse launch of the process (reporting only, not synchronised)
+char g_inv_line[160];
 
 
 // ---------------------------------------------------------------------------------------
@@ -2803,6 +2836,22 @@ int gnf_monotonic_pack(const gnf_mono_net* net, float* pack, gnf_stream_t stream
 
 const char* gnf_monotonic_fwd_kernel(void) { return g_fwd_kernel; }
 const char* gnf_monotonic_bwd_kernel(void) { return g_bwd_kernel; }
+const char* gnf_monotonic_inv_kernel(void) {
+  if (!g_inv_route.t.family[0] || format_inv_route(g_inv_route, g_inv_line, (int)sizeof g_inv_line) < 0) return "";
+  return g_inv_line;
+}
+
+int gnf_monotonic_inv_route(const gnf_mono_net* net, int S, int64_t B, int64_t d, char* buf, int len) {
+  const int HT = pick_ht(net);                       // the checks of prologue() that need no device pointer, in its order
+  if (HT < 0) return GNF_ESHAPE;
+  if (!buf || len < 1 || S < 1 || B < 0 || d <= 0) return GNF_EINVAL;
+  if (net->nl - 1 > kMaxNH) return GNF_ESHAPE;
+  buf[0] = 0;
+  if (B == 0) return 0;                              // an empty batch launches nothing
+  const InvRoute r = inv_route(net_layout(net, HT), B * d, S);
+  if (!r.l.kernel) return GNF_ESHAPE;
+  return format_inv_route(r, buf, len) < 0 ? GNF_EINVAL : 0;
+}
 
 int gnf_monotonic_fwd(const float* pack, const gnf_mono_net* net, const float* x, const float* h, int64_t h_sb,
                       int64_t h_sd, int64_t h_sc, const float* cc_w, const float* cc_t, int S, float* z,
@@ -2825,7 +2874,9 @@ int gnf_monotonic_inv_scatter(const float* pack, const gnf_mono_net* net, const 
   a.h = h; a.h_sb = h_sb; a.h_sd = h_sd; a.h_sc = h_sc;
   a.ccw = cc_w; a.cct = cc_t; a.S = S; a.zt = z; a.xo = x; a.n = B * d; a.d = d;
   a.xo_row = x_row_off; a.xo_sd = x_sd;
-  return launch(inv_route(a.L, a.n, S), a, (hipStream_t)stream);      // (leaves the forward's reporter alone)
+  const InvRoute r = inv_route(a.L, a.n, S);
+  g_inv_route = r;                                                    // (leaves the forward's reporter alone)
+  return launch(r.l, a, (hipStream_t)stream);
 }
 
 int gnf_monotonic_inv(const float* pack, const gnf_mono_net* net, const float* z, const float* h, int64_t h_sb,

@@ -40,7 +40,7 @@ extern "C" {
 
 /* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_*, gnf_image_prep, gnf_dagmlp_*, gnf_dag_levels*, gnf_toy_sample, gnf_shuffle_keys, gnf_tab_batch, gnf_group_bias_*, gnf_spline_*, gnf_made_prefix*_spline, gnf_made_prefix_do, gnf_nll_do_* and gnf_affine_do_* were ADDED under this number (no existing symbol
  * changed; a binding written against the earlier 11 keeps working, and tests/test_cifar_factory.py pins the value);
- * gnf_strade_* likewise */
+ * gnf_strade_* likewise, and gnf_monotonic_inv_route / gnf_monotonic_inv_kernel */
 #define GNF_ABI_VERSION 11
 #define GNF_EINVAL (-1)   /* bad argument (null pointer, negative size, ...)          */
 #define GNF_ESHAPE (-2)   /* shape not supported by any compiled kernel instantiation */
@@ -361,6 +361,18 @@ int gnf_monotonic_inv_scatter(const float* pack, const gnf_mono_net* net,
                               const float* z, const float* h, int64_t h_sb, int64_t h_sd, int64_t h_sc,
                               const float* cc_w, const float* cc_t, int S,
                               float* x, const int32_t* x_row_off, int64_t x_sd, int64_t B, int64_t d, gnf_stream_t stream);
+/* Which kernel the inverse runs.  gnf_monotonic_inv_route(): the route gnf_monotonic_inv / _inv_scatter would take for this
+ * net, S and [B, d] problem, as one line in buf (len bytes, NUL included; too short: GNF_EINVAL):
+ *   "<family><<template arguments>> block=<workgroup size> grid=<workgroups> lds=<dynamic LDS bytes>", e.g.
+ *   "mono_inv_split_k<HT=2,WM=1,EPG=4> block=192 grid=9 lds=9104" -- families and arguments: mono_fwd_k<HT,WM,INV>,
+ *   mono_fwd_x_k<HM,EX,WM,INV>, mono_inv_ks_x_k<HM,EX,epg,waves>, mono_inv_split_x_k<HM,EX,WM,EPG>, mono_inv_split_k<HT,WM,EPG>
+ *   (DESIGN.md section 6 has the table of conditions).  Host arithmetic only: nothing is launched, no device pointer is read
+ *   (net->W / net->b may be NULL); GNF_ESHAPE / GNF_EINVAL for the nets and S / B / d the entry points refuse with them; an
+ *   empty batch gives the empty line.
+ * gnf_monotonic_inv_kernel(): the same line for the last inverse launch of this PROCESS ("" before the first); reporting
+ *   only, not synchronised.  The returned buffer is rewritten by the next call. */
+int gnf_monotonic_inv_route(const gnf_mono_net* net, int S, int64_t B, int64_t d, char* buf, int len);
+const char* gnf_monotonic_inv_kernel(void);
 /* Backward with UMNN's conventions: gx = gz*f(x;h) + gjac*df/dx(x;h) (Leibniz rule);
  * gh, gW, gb = quadrature of df/dh, df/dtheta weighted by gz*xT/2, plus the gjac path,
  * plus gz on h[..,0].  gW[l]/gb[l] are WRITTEN (same shapes as W[l]/b[l]).
