@@ -24,6 +24,7 @@ MADE_MAX_HIDDEN = 8       # GNF_MADE_MAX_HIDDEN
 MADE_NORM_NONE, MADE_NORM_AFFINE = 0, 1
 MADE_NORM_SPLINE = 2      # GNF_MADE_NORM_SPLINE: gnf_made_prefix_spline / gnf_made_prefix_ctx_spline only
 SPLINE_MIN_BINS, SPLINE_MAX_BINS = 2, 32
+SPLINE_FWD, SPLINE_BWD, SPLINE_INV = 0, 1, 2      # `which` of gnf_spline_route
 STRADE_CHUNK_VARS = 8     # GNF_STRADE_CHUNK_VARS: variables per output product of gnf_strade_levels
 DAG_PLAN_KC = 32          # GNF_DAG_PLAN_KC
 DAG_ELEM_F32, DAG_ELEM_U8 = 0, 1      # GNF_DAG_ELEM_*
@@ -63,6 +64,8 @@ SIGNATURES = {
                                c_i64, c_i64, c_i64, c_i64, c_stream]),
     "gnf_spline_inv": (c_int, [c_f, c_f, c_i64, c_i64, c_i64, c_i64, c_int, c_double, c_f, ctypes.c_void_p, c_i64, c_i64,
                                c_i64, c_stream]),
+    "gnf_spline_route": (c_int, [c_int, ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_i64, c_i64, ctypes.c_void_p,
+                                 c_i64, c_i64, c_i64, c_int, ctypes.c_char_p, c_int]),
     "gnf_logsum_rows_fwd": (c_int, [c_f, c_f, c_i64, c_i64, c_stream]),
     "gnf_logsum_rows_bwd": (c_int, [c_f, c_f, c_f, c_i64, c_i64, c_stream]),
     "gnf_normal_logdensity_fwd": (c_int, [c_f, c_f, c_i64, c_i64, c_stream]),

@@ -12,6 +12,7 @@
 // The backward sends the gradient rows back the same way.  The forward's tiles are whole rows of the batch (kTile / d of
 // them, or a row in chunks of kTile columns when d > kTile), so that log|det J| and the Normal log-density of a row are
 // reduced inside the workgroup in a fixed order: no atomics, deterministic.
+#include <stdio.h>
 #include "gnf_spline.h"
 
 namespace {
@@ -234,12 +235,63 @@ __global__ __launch_bounds__(kTile) void spline_inv_k(const float* __restrict__ 
 
 size_t lds_bytes(int K, bool red) { return 4 * (size_t)round_up4(kTile * spl_pitch(K)) + (red ? 16 * kTile : 0); }
 
-int check_common(int K, double T, int64_t h_c, int64_t B, int64_t d) {
-  if (K < kSplMinBins || K > kSplMaxBins || !(T > 0.) || !(T < 3.0e38)) return GNF_EINVAL;
+// ---- the host's decisions, made ONCE: the three entry points launch from a SplPlan and gnf_spline_route prints one ----
+enum { kSplFwd = 0, kSplBwd = 1, kSplInv = 2 };
+
+struct SplPlan {
+  int RT, nchunk;                           // forward: whole rows per workgroup, chunks of a row; 0 and 1 for the element tiles
+  int64_t grid, tiles16, gtiles16;          // workgroups (0: an empty batch); staged tiles on the 16-byte path, of h and of gh
+  size_t lds;
+  HLay l, gl;                               // gl: the backward's gh
+  bool g16;                                 // gh is as wide as the rows: stage_out may take the 16-byte path
+};
+
+// tiles i < count starting at element i step: how many have (e0 sd) % 4 == 0 (the condition of stage_in / stage_out)
+int64_t tiles_on_16(int64_t count, int64_t step, int64_t sd) {
+  int64_t n = 0;
+  for (int r = 0; r < 4 && r < count; ++r)
+    if ((r * (step & 3) * (sd & 3)) % 4 == 0) n += (count - r + 3) / 4;
+  return n;
+}
+
+// the checks the entry points share (T apart, which the query is not given), in their order, then the launch's numbers.
+// others_ok: the entry point's remaining arguments, which it needs only where something is launched
+int spline_plan(int which, const void* h, int64_t h_sb, int64_t h_sd, int64_t h_sc, int64_t h_c, int K, int64_t B, int64_t d,
+                const void* gh, int64_t g_sb, int64_t g_sd, int64_t g_sc, bool others_ok, SplPlan& p) {
+  p = SplPlan{};
+  if (K < kSplMinBins || K > kSplMaxBins) return GNF_EINVAL;
   if (B < 0 || d <= 0) return GNF_EINVAL;
   if (h_c < 3 * K - 1) return GNF_ESHAPE;
+  if (B == 0) return 0;
+  if (!h || (which == kSplBwd && !gh) || !others_ok) return GNF_EINVAL;
+  const int C = 3 * K - 1;
+  if (which == kSplFwd) {
+    p.RT = d >= kTile ? 1 : (int)(kTile / d);
+    p.nchunk = p.RT == 1 ? (int)((d + kTile - 1) / kTile) : 1;
+    p.grid = (B + p.RT - 1) / p.RT;
+  } else {
+    if (B > INT64_MAX / d) return GNF_ESHAPE;
+    p.RT = 0;
+    p.nchunk = 1;
+    p.grid = (B * d + kTile - 1) / kTile;
+  }
+  if (p.grid > 0x7fffffff) return GNF_ESHAPE;
+  p.lds = lds_bytes(K, which == kSplFwd);
+  p.l = make_lay((const float*)h, h_sb, h_sd, h_sc, d, C);
+  // a chunk of a row starts a multiple of kTile past the row, which leaves (e0 sd) % 4 alone
+  const int64_t step = which == kSplFwd ? p.RT * d : kTile;
+  if (p.l.flat == 2) p.tiles16 = tiles_on_16(p.grid, step, h_sd) * p.nchunk;
+  if (which == kSplBwd) {
+    p.gl = make_lay((const float*)gh, g_sb, g_sd, g_sc, d, C);
+    p.g16 = g_sd == C;
+    if (p.gl.flat == 2 && p.g16) p.gtiles16 = tiles_on_16(p.grid, step, g_sd);
+  }
   return 0;
 }
+
+bool bad_tail(double T) { return !(T > 0.) || !(T < 3.0e38); }
+
+const char* lay_name(const HLay& l, bool can16) { return l.flat == 2 && can16 ? "span16" : l.flat ? "span4" : "rows"; }
 
 }  // namespace
 
@@ -247,45 +299,56 @@ extern "C" {
 
 int gnf_spline_fwd(const float* x, const float* h, int64_t h_sb, int64_t h_sd, int64_t h_sc, int64_t h_c, int K, double T,
                    float* z, float* jac, float* logdet, float* logn, int64_t B, int64_t d, gnf_stream_t stream) {
-  if (const int rc = check_common(K, T, h_c, B, d)) return rc;
+  if (bad_tail(T)) return GNF_EINVAL;
+  SplPlan p;
+  if (const int rc = spline_plan(kSplFwd, h, h_sb, h_sd, h_sc, h_c, K, B, d, nullptr, 0, 0, 0, x && z, p)) return rc;
   if (B == 0) return 0;
-  if (!x || !h || !z) return GNF_EINVAL;
-  const int RT = d >= kTile ? 1 : (int)(kTile / d);
-  const int64_t grid = (B + RT - 1) / RT;
-  if (grid > 0x7fffffff) return GNF_ESHAPE;
-  const HLay l = make_lay(h, h_sb, h_sd, h_sc, d, 3 * K - 1);
-  const hipError_t e = gnf_launch_lds(spline_fwd_k, dim3((unsigned)grid), dim3(kTile), lds_bytes(K, true), (hipStream_t)stream,
-                                      x, h, l, K, T, z, jac, logdet, logn, B, d, RT);
+  const hipError_t e = gnf_launch_lds(spline_fwd_k, dim3((unsigned)p.grid), dim3(kTile), p.lds, (hipStream_t)stream,
+                                      x, h, p.l, K, T, z, jac, logdet, logn, B, d, p.RT);
   return e == hipSuccess ? 0 : (int)e;
 }
 
 int gnf_spline_bwd(const float* x, const float* h, int64_t h_sb, int64_t h_sd, int64_t h_sc, int64_t h_c, int K, double T,
                    const float* gz, const float* gjac, const float* glogdet, const float* glogn, float* gx, float* gh,
                    int64_t g_sb, int64_t g_sd, int64_t g_sc, int64_t B, int64_t d, gnf_stream_t stream) {
-  if (const int rc = check_common(K, T, h_c, B, d)) return rc;
+  if (bad_tail(T)) return GNF_EINVAL;
+  SplPlan p;
+  if (const int rc = spline_plan(kSplBwd, h, h_sb, h_sd, h_sc, h_c, K, B, d, gh, g_sb, g_sd, g_sc, x != nullptr, p)) return rc;
   if (B == 0) return 0;
-  if (!x || !h || !gh) return GNF_EINVAL;
-  const int64_t N = B * d, grid = (N + kTile - 1) / kTile;
-  if (grid > 0x7fffffff) return GNF_ESHAPE;
-  const int C = 3 * K - 1;
-  const HLay l = make_lay(h, h_sb, h_sd, h_sc, d, C), gl = make_lay(gh, g_sb, g_sd, g_sc, d, C);
-  const hipError_t e = gnf_launch_lds(spline_bwd_k, dim3((unsigned)grid), dim3(kTile), lds_bytes(K, false), (hipStream_t)stream,
-                                      x, h, l, K, T, gz, gjac, glogdet, glogn, gx, gh, gl, N, d);
+  const hipError_t e = gnf_launch_lds(spline_bwd_k, dim3((unsigned)p.grid), dim3(kTile), p.lds, (hipStream_t)stream,
+                                      x, h, p.l, K, T, gz, gjac, glogdet, glogn, gx, gh, p.gl, B * d, d);
   return e == hipSuccess ? 0 : (int)e;
 }
 
 int gnf_spline_inv(const float* z, const float* h, int64_t h_sb, int64_t h_sd, int64_t h_sc, int64_t h_c, int K, double T,
                    float* x, const int32_t* out_cols, int64_t out_width, int64_t B, int64_t d, gnf_stream_t stream) {
-  if (const int rc = check_common(K, T, h_c, B, d)) return rc;
-  if (out_cols && out_width <= 0) return GNF_EINVAL;
+  if (bad_tail(T)) return GNF_EINVAL;
+  const bool no_width = out_cols && out_width <= 0;
+  SplPlan p;
+  if (const int rc = spline_plan(kSplInv, h, h_sb, h_sd, h_sc, h_c, K, B, d, nullptr, 0, 0, 0, z && x && !no_width, p))
+    return rc;
+  if (no_width) return GNF_EINVAL;                                      // refused for an empty batch too
   if (B == 0) return 0;
-  if (!z || !h || !x) return GNF_EINVAL;
-  const int64_t N = B * d, grid = (N + kTile - 1) / kTile;
-  if (grid > 0x7fffffff) return GNF_ESHAPE;
-  const HLay l = make_lay(h, h_sb, h_sd, h_sc, d, 3 * K - 1);
-  const hipError_t e = gnf_launch_lds(spline_inv_k, dim3((unsigned)grid), dim3(kTile), lds_bytes(K, false), (hipStream_t)stream,
-                                      z, h, l, K, T, x, out_cols, out_width, N, d);
+  const hipError_t e = gnf_launch_lds(spline_inv_k, dim3((unsigned)p.grid), dim3(kTile), p.lds, (hipStream_t)stream,
+                                      z, h, p.l, K, T, x, out_cols, out_width, B * d, d);
   return e == hipSuccess ? 0 : (int)e;
+}
+
+int gnf_spline_route(int which, const void* h, int64_t h_sb, int64_t h_sd, int64_t h_sc, int64_t h_c, int K, int64_t B,
+                     int64_t d, const void* gh, int64_t g_sb, int64_t g_sd, int64_t g_sc, int scatter, char* buf, int len) {
+  if (which < kSplFwd || which > kSplInv || !buf || len < 1) return GNF_EINVAL;
+  SplPlan p;
+  if (const int rc = spline_plan(which, h, h_sb, h_sd, h_sc, h_c, K, B, d, gh, g_sb, g_sd, g_sc, true, p)) return rc;
+  buf[0] = 0;
+  if (p.grid == 0) return 0;                                            // an empty batch launches nothing
+  static const char* const kName[] = {"spline_fwd_k", "spline_bwd_k", "spline_inv_k"};
+  int o = snprintf(buf, len, "%s rows_per_wg=%d chunks=%d grid=%lld lds=%zu h=%s tiles16=%lld", kName[which], p.RT, p.nchunk,
+                   (long long)p.grid, p.lds, lay_name(p.l, true), (long long)p.tiles16);
+  if (which == kSplBwd && o >= 0 && o < len)
+    o += snprintf(buf + o, len - o, " gh=%s gtiles16=%lld", lay_name(p.gl, p.g16), (long long)p.gtiles16);
+  if (which == kSplInv && o >= 0 && o < len) o += snprintf(buf + o, len - o, " out=%s", scatter ? "cols" : "plain");
+  if (o < 0 || o >= len) { buf[0] = 0; return GNF_EINVAL; }
+  return 0;
 }
 
 }  // extern "C"

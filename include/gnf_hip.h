@@ -40,7 +40,7 @@ extern "C" {
 
 /* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_*, gnf_image_prep, gnf_dagmlp_*, gnf_dag_levels*, gnf_toy_sample, gnf_shuffle_keys, gnf_tab_batch, gnf_group_bias_*, gnf_spline_*, gnf_made_prefix*_spline, gnf_made_prefix_do, gnf_nll_do_* and gnf_affine_do_* were ADDED under this number (no existing symbol
  * changed; a binding written against the earlier 11 keeps working, and tests/test_cifar_factory.py pins the value);
- * gnf_strade_* likewise, and gnf_monotonic_inv_route / gnf_monotonic_inv_kernel */
+ * gnf_strade_* likewise, and gnf_monotonic_inv_route / gnf_monotonic_inv_kernel and gnf_spline_route */
 #define GNF_ABI_VERSION 11
 #define GNF_EINVAL (-1)   /* bad argument (null pointer, negative size, ...)          */
 #define GNF_ESHAPE (-2)   /* shape not supported by any compiled kernel instantiation */
@@ -94,6 +94,20 @@ int gnf_spline_bwd(const float* x, const float* h, int64_t h_sb, int64_t h_sd, i
                    int64_t g_sb, int64_t g_sd, int64_t g_sc, int64_t B, int64_t d, gnf_stream_t stream);
 int gnf_spline_inv(const float* z, const float* h, int64_t h_sb, int64_t h_sd, int64_t h_sc, int64_t h_c, int K, double T,
                    float* x, const int32_t* out_cols, int64_t out_width, int64_t B, int64_t d, gnf_stream_t stream);
+/* How the three entry points above would run a problem: which = 0 (fwd), 1 (bwd), 2 (inv) and the h address, strides, h_c,
+ * K, B and d the entry point itself would get; gh and its strides for which = 1 (ignored otherwise); scatter != 0: inv with
+ * out_cols.  One line in buf (len bytes, NUL included; too short: GNF_EINVAL):
+ *   "spline_fwd_k rows_per_wg=<RT> chunks=<nchunk> grid=<workgroups> lds=<dynamic LDS bytes> h=<span16|span4|rows>
+ *    tiles16=<staged tiles of h that take the 16-byte path>", then " gh=<span16|span4|rows> gtiles16=<..>" for bwd and
+ *   " out=<plain|cols>" for inv.  fwd gives a workgroup RT = 128 / d whole rows, or one row in chunks of 128 columns
+ *   (grid x chunks staged tiles); spline_bwd_k and spline_inv_k tile the B d elements by 128 whatever the rows are:
+ *   rows_per_wg=0 chunks=1.  h= names the layout's route (DESIGN.md section 6 has the table of conditions): span16 is
+ *   decided per tile, and tiles16 counts the tiles that take it, the others going by dwords.
+ * Host arithmetic only, from the function the entry points launch from: nothing is launched, no pointer is dereferenced (h
+ * and gh count by their low four bits alone, NULL still being refused), GNF_EINVAL / GNF_ESHAPE as the entry points
+ * (the tail bound, which the query is not given, apart); an empty batch gives the empty line. */
+int gnf_spline_route(int which, const void* h, int64_t h_sb, int64_t h_sd, int64_t h_sc, int64_t h_c, int K, int64_t B,
+                     int64_t d, const void* gh, int64_t g_sb, int64_t g_sd, int64_t g_sc, int scatter, char* buf, int len);
 
 /* ---- row reductions: models/NormalizingFlow.py:70, NormalizingFlowFactories.py:15-16 --
  * logsum:  out[b] = sum_i log(jac[b,i]);        bwd: gjac[b,i] = g[b]/jac[b,i]

@@ -14,6 +14,7 @@ import torch
 
 import misaligned
 import poison
+import spline_cases
 import spline_ref as S
 from oracle import gnf_oracle as O
 
@@ -404,13 +405,24 @@ def _ops_case(K=8, T=3., B=37, d=5, layout="contig"):
     return S.to_bin_middles(x, h, K, T), h, _layout(h, layout)
 
 
+def _ops_shapes(layout):
+    """(B, d) of the hygiene cases: the short rows, and a chunked row (two chunks, the second of one lane) for the layouts
+    spline_cases.ALIGN names"""
+    return [(37, 5)] + [(B, d) for B, d, K, lay in spline_cases.ALIGN if lay == layout and K == 8]
+
+
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_three_arms_normalizer_entry_points(layout):
+    for B, d in _ops_shapes(layout):
+        _three_arms_normalizer_entry_points(layout, B, d)
+
+
+def _three_arms_normalizer_entry_points(layout, B, d):
     from gnf_hip import ops
     K, T = 8, 3.
 
     def run():
-        x, h, hd = _ops_case(K, T, layout=layout)
+        x, h, hd = _ops_case(K, T, B, d, layout=layout)
         xd, hd = cu(x).requires_grad_(True), hd.detach().requires_grad_(True)
         z, jac, ld, ln = ops.SplineFn.apply(xd, hd, K, T, True, True)
         ((z * z).sum() + jac.sum() + ld.sum() + ln.sum()).backward()
@@ -437,11 +449,16 @@ def test_three_arms_prefix_entry_points(c):
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_dword_aligned_operands(layout, k):
     """every fp32 array of the three entry points 4 k bytes past a 16-byte boundary: the same bits as the aligned call, and
-    not a bit outside the arrays"""
+    not a bit outside the arrays.  On the chunked row the span then starts off the 16-byte grid in every tile, which all go
+    by dwords (tests/test_spline_routes_host.py asserts the route)"""
+    for B, d in _ops_shapes(layout):
+        _dword_aligned_operands(layout, k, B, d)
+
+
+def _dword_aligned_operands(layout, k, B, d):
     from gnf_hip import ops
     K, T = 8, 3.
-    x, h, hd = _ops_case(K, T, layout=layout)
-    B, d = x.shape
+    x, h, hd = _ops_case(K, T, B, d, layout=layout)
     g = torch.Generator().manual_seed(9)
     cot = [cu(torch.randn(B, d, generator=g)), cu(torch.randn(B, d, generator=g)), cu(torch.randn(B, generator=g)),
            cu(torch.randn(B, generator=g))]
