@@ -1,6 +1,8 @@
 // What the two MADE kernels share (gnf_made_prefix.hip: the forward column sweep of an inversion; gnf_made_adjoint.hip: the
 // transposed sweep of its adjoint): the layout host and device agree on, the degree-ordered weight image, and the inner
-// product of one (layer, step).  Everything sits in an anonymous namespace, as the kernels of every unit do.
+// product of one (layer, step) -- layer_step over a prefix, suffix_step over a suffix of a transposed image.  The two StrADE
+// kernels (gnf_strade.h) run the same steps on level tables.  Everything sits in an anonymous namespace, as the kernels of
+// every unit do.
 #pragma once
 #include "gnf_common.h"
 
@@ -182,6 +184,75 @@ __device__ __forceinline__ void layer_step(const float* __restrict__ W, int ldw,
     for (; k < K; k += G) s0 = fmaf(w[k], a[k], s0);
     const float v = group_sum<G>((s0 + s1) + (s2 + s3)) + bias[u];
     if (j == 0 && r < nrows) dst[(size_t)r * dstride + u] = relu ? relu_keep_nan(v) : v;
+  }
+  __syncthreads();
+}
+
+// dst[r][u] = sum_{k0 <= k < K} W[u][k] in[r][k] for the n units u of this step and the tile's rows r < nrows, times the
+// unit's ReLU decision (gate: dst holds its activation).  W points at the first of those units' rows of a transposed
+// image (rows_avail of them follow).  layer_step's two inner products on a range.  Ends in a barrier.
+template <int TB>
+__device__ __forceinline__ void suffix_step(const float* __restrict__ W, int ldw, int rows_avail, int n, int k0, int K,
+                                            const float* in, int istride, float* dst, int dstride, bool gate, int nrows,
+                                            float* red) {
+  const int tid = threadIdx.x;
+  if (TB == 16 && n >= 8) {
+    const int wave = tid >> 6, lane = tid & 63, m = lane & 15, q = lane >> 4;
+    const float* a = in + (size_t)(m < nrows ? m : nrows - 1) * istride;
+    const int nchunks = (K + 15) >> 4;
+    for (int nt = 0; nt * 16 < n; ++nt) {
+      const int urow = nt * 16 + m < rows_avail ? nt * 16 + m : rows_avail - 1;
+      const float* w = W + (size_t)urow * ldw + 4 * q;
+      f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+      for (int ch = (k0 >> 4) + wave; ch < nchunks; ch += 4) {
+        const int kb = ch * 16 + 4 * q;
+        const f32x4 wv = ld4(w + ch * 16);
+        const float a0 = kb >= k0 && kb < K ? a[kb] : 0.f;
+        const float a1 = kb + 1 >= k0 && kb + 1 < K ? a[kb + 1] : 0.f;
+        const float a2 = kb + 2 >= k0 && kb + 2 < K ? a[kb + 2] : 0.f;
+        const float a3 = kb + 3 >= k0 && kb + 3 < K ? a[kb + 3] : 0.f;
+        c0 = mfma(a0, wv[0], c0);
+        c1 = mfma(a1, wv[1], c1);
+        c0 = mfma(a2, wv[2], c0);
+        c1 = mfma(a3, wv[3], c1);
+      }
+      c0 += c1;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[wave * 256 + (q * 4 + r) * 16 + m] = c0[r];     // D: row 4 q + r, column m
+      __syncthreads();
+      {
+        const int rm = tid >> 4, u = nt * 16 + (tid & 15);
+        if (u < n && rm < nrows) {
+          const float v = ((red[tid] + red[256 + tid]) + red[512 + tid]) + red[768 + tid];
+          float* o = dst + (size_t)rm * dstride + u;
+          *o = !gate || *o > 0.f ? v : 0.f;
+        }
+      }
+      __syncthreads();
+    }
+    return;
+  }
+  constexpr int G = kThreads / TB;
+  const int r = tid / G, j = tid % G;
+  const float* a = in + (size_t)(r < nrows ? r : nrows - 1) * istride;
+  for (int u = 0; u < n; ++u) {
+    const float* w = W + (size_t)u * ldw;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int k = k0 + j;
+    for (; k + 3 * G < K; k += 4 * G) {
+      const float w0 = w[k], w1 = w[k + G], w2 = w[k + 2 * G], w3 = w[k + 3 * G];
+      s0 = fmaf(w0, a[k], s0);
+      s1 = fmaf(w1, a[k + G], s1);
+      s2 = fmaf(w2, a[k + 2 * G], s2);
+      s3 = fmaf(w3, a[k + 3 * G], s3);
+    }
+    for (; k < K; k += G) s0 = fmaf(w[k], a[k], s0);
+    const float v = group_sum<G>((s0 + s1) + (s2 + s3));
+    if (j == 0 && r < nrows) {
+      float* o = dst + (size_t)r * dstride + u;
+      *o = !gate || *o > 0.f ? v : 0.f;
+    }
   }
   __syncthreads();
 }

@@ -30,17 +30,10 @@
 //   - in a mixed chunk the product is computed for the whole chunk and the per-variable choice is made AFTER it, in the
 //     epilogue, where it is a per-thread select with no barrier inside.
 // The hidden units are computed as ever: later levels read them.  pin == NULL instantiates a kernel without the branch.
-#include "gnf_made.h"
+#include "gnf_strade.h"
 #include "gnf_spline.h"
 
 namespace {
-
-constexpr int kChunkVars = GNF_STRADE_CHUNK_VARS;      // variables whose outputs one output product computes
-
-struct StradePackArgs {
-  PackArgs p;
-  const float* M[kMaxH + 1];
-};
 
 struct LevelArgs {
   StepArgs s;
@@ -49,27 +42,11 @@ struct LevelArgs {
   int hstride;                  // floats per row of hbuf: min(widest, kChunkVars) * out
 };
 
-// the level-ordered image of mask o W: rows and columns permuted as pack_elem permutes them (the plan's tables stand where
-// the degree tables stand), a masked entry an exact zero whatever the weight holds; biases behind each layer
+// the level-ordered image of mask o W (strade_pack_elem), biases behind each layer
 __global__ void strade_pack_k(StradePackArgs a, float* __restrict__ pack) {
   const MadeLayout& L = a.p.lay;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < L.pack_floats; e += (int64_t)gridDim.x * blockDim.x) {
-    int l = 0;
-    while (l < L.nh && e >= L.w_off[l + 1]) ++l;
-    float v = 0.f;
-    if (e < L.b_off[l]) {
-      const int64_t i = e - L.w_off[l];
-      const int r = (int)(i / L.ldw[l]), k = (int)(i - (int64_t)r * L.ldw[l]);
-      if (k < L.K[l]) {
-        const int64_t src = (int64_t)pack_src_row(a.p, l, r) * L.K[l] + pack_src_col(a.p, l, k);
-        v = a.M[l][src] != 0.f ? a.p.W[l][src] : 0.f;
-      }
-    } else {
-      const int r = (int)(e - L.b_off[l]);
-      if (r < L.rows[l]) v = a.p.b[l][pack_src_row(a.p, l, r)];
-    }
-    pack[e] = v;
-  }
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < L.pack_floats; e += (int64_t)gridDim.x * blockDim.x)
+    pack[e] = strade_pack_elem(a, e);
 }
 
 // (out of line for the reason given at made_prefix_k's: the fp64 exponentials would cost every path its registers)
@@ -145,10 +122,6 @@ __global__ __launch_bounds__(kThreads) void strade_levels_k(LevelArgs a, const f
   }
 }
 
-int64_t lds_bytes(const MadeLayout& lay, int TB, int hstride) {
-  return 4 * ((int64_t)kRedFloats + round_up(TB * hstride, 4) + (int64_t)TB * lay.A);
-}
-
 template <int TB>
 int launch(const LevelArgs& a, size_t smem, int64_t grid, hipStream_t st, const float* pack, const float* context,
            const float* z, float* x, int mode, int64_t B, const uint8_t* pin) {
@@ -156,14 +129,6 @@ int launch(const LevelArgs& a, size_t smem, int64_t grid, hipStream_t st, const 
   const hipError_t e = pin ? gnf_launch_lds(strade_levels_k<TB, true>, g, b, smem, st, a, pack, context, z, x, mode, B, pin)
                            : gnf_launch_lds(strade_levels_k<TB, false>, g, b, smem, st, a, pack, context, z, x, mode, B, pin);
   return e == hipSuccess ? 0 : (int)e;
-}
-
-int strade_layout(const gnf_strade_net* net, int cond_in, MadeLayout* lay) {
-  if (!net) return GNF_EINVAL;
-  const int rc = make_layout(&net->made, cond_in, lay);
-  if (rc) return rc;
-  if (net->nlev < 1 || net->nlev > net->made.d || net->widest < 1 || net->widest > net->made.d) return GNF_EINVAL;
-  return 0;
 }
 
 }  // namespace
@@ -182,11 +147,7 @@ int gnf_strade_pack(const gnf_strade_net* net, int cond_in, float* pack, gnf_str
   if (rc) return rc;
   if (!pack) return GNF_EINVAL;
   if ((uintptr_t)pack & 15) return GNF_EINVAL;          // the sweep kernel reads the image's rows as 16-byte quads
-  if (fill_pack_args(&net->made, &a.p)) return GNF_EINVAL;
-  for (int l = 0; l <= net->made.nh; ++l) {
-    if (!net->mask[l]) return GNF_EINVAL;
-    a.M[l] = net->mask[l];
-  }
+  if (strade_fill_pack_args(net, &a)) return GNF_EINVAL;
   const int64_t blocks = (a.p.lay.pack_floats + 255) / 256;
   hipLaunchKernelGGL(strade_pack_k, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream, a,
                      pack);
@@ -211,16 +172,9 @@ int gnf_strade_levels(const gnf_strade_net* net, int cond_in, const float* conte
     a.s.spl_K = spline_bins;
     a.s.spl_T = spline_tail;
   }
-  const int nv = net->widest < kChunkVars ? net->widest : kChunkVars;
-  if ((int64_t)nv * m.out > (1 << 24)) return GNF_ESHAPE;
-  a.hstride = nv * m.out;
-  // batch rows per workgroup: tile_rows on what one product computes at most (hidden units of a level, outputs of a chunk),
-  // then halved until the tile's rows fit in LDS.  Decided from (net, cond_in, B) alone: a fixed summation order
-  gnf_made_net probe = m;
-  if (a.hstride > probe.max_new) probe.max_new = a.hstride;
-  int TB = tile_rows(&probe, B);
-  while (TB > 4 && lds_bytes(a.s.lay, TB, a.hstride) > kLdsBytes) TB /= 2;
-  if (lds_bytes(a.s.lay, TB, a.hstride) > kLdsBytes) return GNF_ESHAPE;
+  // batch rows per workgroup: strade_tile_rows (gnf_strade.h), which the adjoint sweep asks as well
+  const int TB = strade_tile_rows(net, a.s.lay, B, &a.hstride);
+  if (!TB) return GNF_ESHAPE;
   if (B == 0) return 0;
   if (!pack || !z || !x || !m.var_of_step || !net->var_off || (cond_in > 0 && !context)) return GNF_EINVAL;
   if ((uintptr_t)pack & 15) return GNF_EINVAL;          // rows of the weight image are read as 16-byte quads (ld4)
@@ -234,7 +188,7 @@ int gnf_strade_levels(const gnf_strade_net* net, int cond_in, const float* conte
   const int64_t grid = (B + TB - 1) / TB;
   if (grid > 0x7fffffff) return GNF_ESHAPE;
   hipStream_t st = (hipStream_t)stream;
-  const size_t smem = (size_t)lds_bytes(a.s.lay, TB, a.hstride);
+  const size_t smem = (size_t)strade_levels_lds_bytes(a.s.lay, TB, a.hstride);
   switch (TB) {
     case 4: return launch<4>(a, smem, grid, st, pack, context, z, x, normalizer_mode, B, pin);
     case 8: return launch<8>(a, smem, grid, st, pack, context, z, x, normalizer_mode, B, pin);

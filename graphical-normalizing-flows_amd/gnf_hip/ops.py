@@ -470,6 +470,57 @@ def made_adjoint(params, plan, pack, x, g, jac, dzdh, context=None, force_ws=Fal
     return lam
 
 
+# ----------------------------------------------------------------------------- StrADE adjoint sweep, rsample
+@torch.no_grad()
+def strade_adjoint_pack(params, masks, plan):
+    """the StrADE adjoint kernel's weight image: the level image of strade_pack followed by every layer of mask o W
+    transposed (gnf_strade_adjoint_pack); parameter-only, one launch (StrADEConditioner.hold_adjoint_pack builds it once
+    for several solves)"""
+    params = [p.detach() for p in params]
+    net, c = _strade_net(params, masks, plan), _plan_cond_in(plan)
+    nfl = abi.load().gnf_strade_adjoint_pack_floats(ctypes.byref(net), c)
+    if nfl < 0:
+        abi.check(int(nfl), "gnf_strade_adjoint_pack_floats")
+    pack = _empty((int(nfl),), params[0])
+    call("gnf_strade_adjoint_pack", ctypes.byref(net), c, ptr(pack), stream())
+    return pack
+
+
+@torch.no_grad()
+def strade_adjoint(params, masks, plan, pack, x, g, jac, dzdh, context=None, force_ws=False):
+    """lambda [B, d] with J^T lambda = g for the StrADE step whose sample is x (gnf_strade_adjoint, one launch): x, g, jac
+    [B, d] and dzdh [B, d, out] fp32 contiguous, jac the normalizer's own derivative dz_i/dx_i, dzdh[b, i, :] = dz_bi/dh_bi
+    by variable index; context: the contiguous [B, cond_in] tensor of a conditional plan.  force_ws (tests): keep the
+    tile's rows in the workspace even when they fit in LDS -- the same bits.  An empty batch launches nothing."""
+    params = [p.detach() for p in params]
+    net, c = _strade_net(params, masks, plan), _plan_cond_in(plan)
+    B, d = x.shape
+    ok = lambda t, shape: (t.is_cuda and t.device == x.device and t.dtype == torch.float32 and tuple(t.shape) == shape
+                           and t.is_contiguous())
+    if d != plan["d"] or not (ok(x, (B, d)) and ok(g, (B, d)) and ok(jac, (B, d)) and ok(dzdh, (B, d, plan["out"]))):
+        raise abi.GnfError("strade_adjoint: x, g, jac [B, %d] and dzdh [B, %d, %d] must be contiguous fp32 device tensors"
+                           % (plan["d"], plan["d"], plan["out"]))
+    if (context is not None) != (c > 0) or (c > 0 and not ok(context, (B, c))):
+        raise abi.GnfError("strade_adjoint: context must be a contiguous fp32 [B, %d] tensor on the device of x (None for "
+                           "cond_in = 0)" % c)
+    lam = torch.empty_like(x)
+    args = lambda w: (ctypes.byref(net), c, ptr(context), ptr(pack), ptr(x), ptr(g), ptr(jac), ptr(dzdh), ptr(lam), B,
+                      int(bool(force_ws)), None if w is None else ctypes.c_void_p(w.data_ptr()),
+                      0 if w is None else w.numel() * 4, stream())
+    if not force_ws:
+        # a tile whose rows fit in LDS needs no workspace; the library says when it does not
+        rc = abi.load().gnf_strade_adjoint(*args(None))
+        if rc == 0:
+            return lam
+        if rc != -3:
+            abi.check(rc, "gnf_strade_adjoint")
+    nbytes = abi.load().gnf_strade_adjoint_workspace_bytes(ctypes.byref(net), c, B)
+    if nbytes < 0:
+        abi.check(int(nbytes), "gnf_strade_adjoint_workspace_bytes")
+    call("gnf_strade_adjoint", *args(_ws(nbytes, x)))
+    return lam
+
+
 class InvertFn(torch.autograd.Function):
     """x = step^-1(z; theta, context) with the gradient of the implicit function theorem (NormalizingFlowStep.rsample).
     Forward: step.invert, the same kernels and bits.  Backward, for a cotangent g = dL/dx: lambda solves J^T lambda = g

@@ -265,3 +265,33 @@ class StrADEConditioner(Conditioner):
         plan, params, masks = self.level_plan(), self._params(), self._masks()
         pack = self._held_pack if self._held_pack is not None else ops.strade_pack(params, masks, plan)
         return ops.strade_levels(params, masks, plan, pack, z, x, mode, context=context, spline=spline, pin=pin)
+
+    # -- the adjoint of that sweep (NormalizingFlowStep.rsample's backward) -------------------------------------------------
+    adjoint_levels = False               # opt-in: rsample's backward solves J^T lambda = g on gnf_strade_adjoint (one launch)
+    _held_adjoint = None
+
+    def hold_adjoint_pack(self):
+        """context manager: the adjoint kernel's weight image (the level image and every layer transposed), built once for
+        the adjoint_solve calls inside"""
+        @contextlib.contextmanager
+        def hold():
+            prev = self._held_adjoint
+            plan = self.level_plan()
+            if prev is None and plan is not None:
+                self._held_adjoint = ops.strade_adjoint_pack(self._params(), self._masks(), plan)
+            try:
+                yield
+            finally:
+                self._held_adjoint = prev
+        return hold()
+
+    def adjoint_solve(self, x, g, jac, dzdh, context=None):
+        """lambda [B, d] with J^T lambda = g for the step whose sample is x, on the HIP adjoint level kernel
+        (gnf_hip.ops.strade_adjoint, one launch): jac [B, d] the normalizer's dz_i/dx_i, dzdh [B, d, out] its dz_i/dh_i;
+        `context`: the checked [B, cond_in] context.  None when level_plan() is None (a hand-edited mask): the passes serve"""
+        plan = self.level_plan()
+        if plan is None:
+            return None
+        params, masks = self._params(), self._masks()
+        pack = self._held_adjoint if self._held_adjoint is not None else ops.strade_adjoint_pack(params, masks, plan)
+        return ops.strade_adjoint(params, masks, plan, pack, x, g, jac, dzdh, context=context)

@@ -677,11 +677,21 @@ class NormalizingFlowStep(NormalizingFlow):
     def _adjoint_plan(self, x, context):
         """the MADE plan of the adjoint arm when `_fast_arm` names the column sweep for this sample (and `adjoint_schedule`,
         and the conditioner can solve), else None: the passes arm.  Never raises: a context that `_fast_arm` would refuse
-        answers None as a missing one does"""
+        answers None as a missing one does.  A StrADE conditioner with `adjoint_levels` on answers its level plan, whatever
+        the normalizer and however the sample was inverted: the solve reads jac and dz/dh alone."""
         cond = self.conditioner
+        cond_in = int(getattr(cond, "cond_in", 0) or 0)
         if not (self.adjoint_schedule and getattr(cond, "adjoint_solve", None) is not None
-                and bool(int(getattr(cond, "cond_in", 0) or 0)) == (context is not None)):
+                and bool(cond_in) == (context is not None)):
             return None
+        if getattr(cond, "prefix_plan", None) is None:
+            if not (getattr(cond, "adjoint_levels", False) and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32):
+                return None
+            if context is not None and (context.device != x.device or context.dtype != torch.float32
+                                        or tuple(context.shape) != (x.shape[0], cond_in)):
+                return None
+            plan = cond.level_plan()
+            return plan if plan is not None and plan["d"] == x.shape[1] else None
         try:
             arm = self._fast_arm(x, context)
         except ValueError:

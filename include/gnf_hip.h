@@ -40,7 +40,8 @@ extern "C" {
 
 /* 11 still: gnf_lenet_gated_*, gnf_lenet_rows_*, gnf_image_prep, gnf_dagmlp_*, gnf_dag_levels*, gnf_toy_sample, gnf_shuffle_keys, gnf_tab_batch, gnf_group_bias_*, gnf_spline_*, gnf_made_prefix*_spline, gnf_made_prefix_do, gnf_nll_do_* and gnf_affine_do_* were ADDED under this number (no existing symbol
  * changed; a binding written against the earlier 11 keeps working, and tests/test_cifar_factory.py pins the value);
- * gnf_strade_* likewise, and gnf_monotonic_inv_route / gnf_monotonic_inv_kernel and gnf_spline_route */
+ * gnf_strade_* (gnf_strade_adjoint* among them) likewise, and gnf_monotonic_inv_route / gnf_monotonic_inv_kernel and
+ * gnf_spline_route */
 #define GNF_ABI_VERSION 11
 #define GNF_EINVAL (-1)   /* bad argument (null pointer, negative size, ...)          */
 #define GNF_ESHAPE (-2)   /* shape not supported by any compiled kernel instantiation */
@@ -572,6 +573,41 @@ int64_t gnf_made_adjoint_ws_bytes(const gnf_made_net* net, int cond_in, int64_t 
 int gnf_made_adjoint(const gnf_made_net* net, int cond_in, const float* context, const float* pack, const float* x,
                      const float* g, const float* jac, const float* dzdh, float* lambda, int64_t B, int force_ws, void* ws,
                      int64_t ws_bytes, gnf_stream_t stream);
+
+/* ---- StrADE adjoint sweep: lambda with J^T lambda = g for one StrADE step (rsample's backward, adjoint_levels) -----------
+ * gnf_made_adjoint with "degree" replaced by "topological level", on the tables of gnf_strade_levels.  In level order
+ * J = dz/dx = diag(jac) + N with N[p'][p] != 0 only where the level of p' is above the level of p, so J^T lambda = g is
+ * solved from the last level down, a whole level at once:
+ *   lambda[b, v] = (g[b, v] - u) / jac[b, v],  v = var_of_step[p], var_off[t] <= p < var_off[t + 1],
+ *   u = the cotangent that reaches x[b, v] through the masked net when the outputs of every variable v' of a later level
+ *       carry the cotangent lambda[b, v'] * dzdh[b, v', :].
+ * One launch does the whole solve: it first replays the hidden units from x with the arithmetic and the tile height of
+ * gnf_strade_levels for the same (net, cond_in, B) (4 rows where that sweep answers GNF_ESHAPE), keeping the ReLU
+ * decisions act > 0, and then walks t = nlev-1 .. 0, finalising per level the cotangents of the hidden units of level t
+ * (contractions over the suffix [off[l+1][t], width) of the layer above; the suffix start is not the mask: forbidden
+ * entries inside it are exact zeros of the image) and u for the level's variables in chunks of GNF_STRADE_CHUNK_VARS.
+ *   net, cond_in: as for gnf_strade_levels; the masks are read by gnf_strade_adjoint_pack alone.
+ *   pack: >= gnf_strade_adjoint_pack_floats(net, cond_in) floats, 16-byte aligned (else GNF_EINVAL), written by
+ *     gnf_strade_adjoint_pack: the image of gnf_strade_pack, bit for bit, followed by every layer TRANSPOSED (layer l as
+ *     [in_features][out_features rounded up to 16], the tail zero, a masked entry an exact zero whatever the weight holds).
+ *     Parameter-only, valid until a parameter, a mask or the graph changes.
+ *   x, g, jac, lambda: [B, d] contiguous; context: [B, cond_in] contiguous (NULL for cond_in = 0); dzdh: [B, d, out]
+ *     contiguous, by VARIABLE index, dzdh[b, i, k] = dz[b, i] / dh[b, i, k].  All dword-aligned, nothing more is assumed.
+ *     jac != 0.  The normalizer is not named: jac and dzdh are all the kernel knows of it.
+ *   ws: >= gnf_strade_adjoint_workspace_bytes(net, cond_in, B) bytes (spelt out, not abbreviated as the other queries are: the
+ *     forward sweep of a StrADE net takes no workspace, and tests/test_strade_masks.py pins that by name); may be NULL when the tile's rows
+ *     [context | x | hidden ... | d out output cotangents] fit in LDS (160 KB), GNF_EWS tells otherwise -- never GNF_ESHAPE
+ *     for want of LDS.  force_ws != 0 keeps the rows in ws even when they would fit: the same code on another pointer,
+ *     the same bits (a test hook).
+ *   fp32 with a fixed summation order for a given (net, cond_in, B); no atomics; rows never interact.  B == 0 launches
+ *   nothing.  GNF_EINVAL: a NULL operand or table with rows to compute, a misaligned pack, B < 0, and what
+ *   gnf_strade_levels refuses of a net.  Every check comes before any launch. */
+int64_t gnf_strade_adjoint_pack_floats(const gnf_strade_net* net, int cond_in);
+int gnf_strade_adjoint_pack(const gnf_strade_net* net, int cond_in, float* pack, gnf_stream_t stream);
+int64_t gnf_strade_adjoint_workspace_bytes(const gnf_strade_net* net, int cond_in, int64_t B);
+int gnf_strade_adjoint(const gnf_strade_net* net, int cond_in, const float* context, const float* pack, const float* x,
+                       const float* g, const float* jac, const float* dzdh, float* lambda, int64_t B, int force_ws, void* ws,
+                       int64_t ws_bytes, gnf_stream_t stream);
 
 /* ---- MNISTCNN convolutional front: models/MLP.py:36-41 as the DAG embedding net --------
  * (ImageExperiments / NormalizingFlowFactories.py:83-86: size_img = [1,28,28]).
