@@ -162,11 +162,15 @@ SIGNATURES = {
     "gnf_made_adjoint_ws_bytes": (c_i64, [ctypes.POINTER(MadeNet), c_int, c_i64]),
     "gnf_made_adjoint": (c_int, [ctypes.POINTER(MadeNet), c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i64, c_int,
                                  ctypes.c_void_p, c_i64, c_stream]),
+    "gnf_made_adjoint_do": (c_int, [ctypes.POINTER(MadeNet), c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p, c_f,
+                                    c_i64, c_int, ctypes.c_void_p, c_i64, c_stream]),
     "gnf_strade_adjoint_pack_floats": (c_i64, [ctypes.POINTER(StradeNet), c_int]),
     "gnf_strade_adjoint_pack": (c_int, [ctypes.POINTER(StradeNet), c_int, c_f, c_stream]),
     "gnf_strade_adjoint_workspace_bytes": (c_i64, [ctypes.POINTER(StradeNet), c_int, c_i64]),
     "gnf_strade_adjoint": (c_int, [ctypes.POINTER(StradeNet), c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i64, c_int,
                                    ctypes.c_void_p, c_i64, c_stream]),
+    "gnf_strade_adjoint_do": (c_int, [ctypes.POINTER(StradeNet), c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f, ctypes.c_void_p,
+                                      c_f, c_i64, c_int, ctypes.c_void_p, c_i64, c_stream]),
     "gnf_dag_loss_prep": (c_int, [c_f, c_f, c_float, c_f, c_i64, c_stream]),
     "gnf_dag_loss_value": (c_int, [c_f, c_f, c_f, c_f, c_float, c_f, c_f, c_f, c_f, c_int, c_f, c_f, c_i64, c_stream]),
     "gnf_dag_loss_bwd": (c_int, [c_f, c_f, c_f, c_f, c_f, c_i64, c_stream]),

@@ -26,6 +26,14 @@
 //
 // Every __syncthreads() is reached by all 256 threads: the branches around suffix_step / layer_step depend on the tables
 // alone, which are the same for every lane.
+//
+// An intervention do(x_P = v) (gnf_strade_adjoint_do, rsample_do's backward) hands a pin table over, one byte per VARIABLE.
+// A pinned variable keeps its level; its lambda := 0 and the cotangent row of its outputs is exact zeros, both by SELECTION
+// (jac and dzdh of a pinned element are never read), and gdo = g - u is dL/dv.  What the table makes dead is skipped: the
+// levels above t_last, the last level that holds a free variable, have u = 0 exactly and contract nothing, phase 1 replays
+// the units up to level t_last - 1 only (no layer step at all when every variable is pinned), and a chunk whose variables
+// are all pinned skips its first-layer contraction when the caller takes no gdo.  Those branches depend on the tables and
+// the gdo pointer alone.  Instantiated with and without pins: pin == NULL launches the kernel of gnf_strade_adjoint.
 #include "gnf_strade.h"
 
 namespace {
@@ -91,12 +99,13 @@ struct AdjArgs {
   int gos;
 };
 
-template <int TB, bool kLds>
+template <int TB, bool kLds, bool kPin>
 __global__ __launch_bounds__(kThreads) void strade_adjoint_k(AdjArgs p, const float* __restrict__ pack,
                                                              const float* __restrict__ context, const float* __restrict__ x,
                                                              const float* __restrict__ g, const float* __restrict__ jac,
                                                              const float* __restrict__ dzdh, float* __restrict__ lam,
-                                                             float* ws, int64_t B) {
+                                                             float* ws, int64_t B, const uint8_t* __restrict__ pin,
+                                                             float* __restrict__ gdo) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const StepArgs& s = p.s;
   const MadeLayout& L = s.lay;
@@ -110,6 +119,15 @@ __global__ __launch_bounds__(kThreads) void strade_adjoint_k(AdjArgs p, const fl
   // [TB][A] activations, then cotangents | [TB][gos] output cotangents
   float* act = kLds ? smem + kRedFloats + kSmallFloats : ws + (size_t)row0 * (A + gos);
   float* go = act + (size_t)TB * A;
+  // the last level that holds a free variable, -1 when every variable is pinned (the tables: uniform over the workgroup)
+  int t_last = nlev - 1;
+  if (kPin)
+    for (; t_last >= 0; --t_last) {
+      bool any_free = false;
+      for (int q = p.var_off[t_last]; q < p.var_off[t_last + 1]; ++q) any_free |= pin[s.var_of_step[q]] == 0;
+      if (any_free) break;
+    }
+  const int t_end = kPin ? t_last + 1 : nlev;  // phase 1 replays the units of level < t_end - 1
 
   // ---- phase 1: the hidden units of the sweep that produced x (strade_levels_k's loop without outputs and inverse)
   for (int i = tid; i < TB * A; i += kThreads) act[i] = 0.f;
@@ -118,7 +136,7 @@ __global__ __launch_bounds__(kThreads) void strade_adjoint_k(AdjArgs p, const fl
   for (int i = tid; i < nrows * c; i += kThreads) act[(size_t)(i / c) * A + i % c] = context[row0 * c + i];
   for (int i = tid; i < nrows * d; i += kThreads) act[(size_t)(i / d) * A + c + i % d] = x[(row0 + i / d) * d + s.var_of_step[i % d]];
   __syncthreads();
-  for (int t = 0; t < nlev; ++t)
+  for (int t = 0; t < t_end; ++t)
     for (int l = 0; l < nh; ++l) {
       const int n0 = t >= 1 ? s.off[l][t - 1] : 0, n1 = s.off[l][t];  // the units of level t - 1 (t = 0: the empty-set units)
       if (n1 == n0) continue;                                         // (uniform: the tables are the same for every lane)
@@ -131,9 +149,10 @@ __global__ __launch_bounds__(kThreads) void strade_adjoint_k(AdjArgs p, const fl
   const int KO = d * out;
   for (int t = nlev - 1; t >= 0; --t) {
     const int p0 = p.var_off[t], p1 = p.var_off[t + 1];               // the level's variables, positions in level order
+    const bool live = !kPin || t <= t_last;                           // a level above the last free one contracts nothing
     for (int l = nh - 1; l >= 0; --l) {
       const int n0 = s.off[l][t], n1 = s.off[l][t + 1];               // the units of level t
-      if (n1 == n0) continue;                                         // (uniform)
+      if (n1 == n0 || !live) continue;                                // (uniform)
       const bool last = l == nh - 1;
       suffix_step<TB>(pack + p.t_off[l + 1] + (size_t)n0 * p.ldt[l + 1], p.ldt[l + 1], L.rows[l] - n0, n1 - n0,
                       last ? p1 * out : s.off[l + 1][t], last ? KO : L.rows[l + 1],
@@ -147,15 +166,29 @@ __global__ __launch_bounds__(kThreads) void strade_adjoint_k(AdjArgs p, const fl
       const bool mine = tid < nrows * nv;
       const int r = mine ? tid / nv : 0, j = mine ? tid % nv : 0;
       const int v = s.var_of_step[q0 + j];
-      // asked for before the product, which hides the latency
+      const bool pinned = kPin && pin[v] != 0;
+      // a chunk of pinned variables needs its u for gdo alone (uniform: the table and the pointer)
+      bool with_u = live;
+      if (kPin && live && !gdo) {
+        with_u = false;
+        for (int jj = 0; jj < nv; ++jj) with_u |= pin[s.var_of_step[q0 + jj]] == 0;
+      }
+      // asked for before the product, which hides the latency (jac of a pinned element is not read: it may hold anything)
       const float gv = mine ? g[(row0 + r) * d + v] : 0.f;
-      const float jv = mine ? jac[(row0 + r) * d + v] : 1.f;
-      suffix_step<TB>(pack + p.t_off[0] + (size_t)(c + q0) * p.ldt[0], p.ldt[0], d - q0, nv, k0, K,
-                      nh == 0 ? go : act + L.act_off[0], nh == 0 ? gos : A, ubuf, kChunkVars, false, nrows, red);
+      const float jv = mine && !pinned ? jac[(row0 + r) * d + v] : 1.f;
+      if (with_u)
+        suffix_step<TB>(pack + p.t_off[0] + (size_t)(c + q0) * p.ldt[0], p.ldt[0], d - q0, nv, k0, K,
+                        nh == 0 ? go : act + L.act_off[0], nh == 0 ? gos : A, ubuf, kChunkVars, false, nrows, red);
       if (mine) {
-        const float lv = (gv - ubuf[r * kChunkVars + j]) / jv;
-        lam[(row0 + r) * d + v] = lv;
-        lbuf[r * kChunkVars + j] = lv;
+        if (pinned) {
+          lam[(row0 + r) * d + v] = 0.f;
+          if (gdo) gdo[(row0 + r) * d + v] = live ? gv - ubuf[r * kChunkVars + j] : gv;
+        } else {
+          const float lv = (gv - ubuf[r * kChunkVars + j]) / jv;
+          lam[(row0 + r) * d + v] = lv;
+          lbuf[r * kChunkVars + j] = lv;
+          if (kPin && gdo) gdo[(row0 + r) * d + v] = 0.f;
+        }
       }
       __syncthreads();
       // the cotangents of these variables' outputs, read by the levels below (never by this level: its suffixes start at p1)
@@ -166,8 +199,9 @@ __global__ __launch_bounds__(kThreads) void strade_adjoint_k(AdjArgs p, const fl
           const int64_t rem = i - rr * per_row;
           const int jj = (int)(rem / out), kk = (int)(rem - (int64_t)jj * out);
           const int vv = s.var_of_step[q0 + jj];
+          // exact zeros for a pinned variable: its dzdh is not read
           go[(size_t)rr * gos + (size_t)(q0 + jj) * out + kk] =
-              lbuf[rr * kChunkVars + jj] * dzdh[((row0 + rr) * d + vv) * out + kk];
+              kPin && pin[vv] != 0 ? 0.f : lbuf[rr * kChunkVars + jj] * dzdh[((row0 + rr) * d + vv) * out + kk];
         }
       }
       __syncthreads();          // lbuf and ubuf are free for the next chunk; go is complete for the level below
@@ -183,11 +217,20 @@ int64_t ws_floats(const AdjLayout& a, int64_t B) { return (B + 15) / 16 * 16 * (
 
 template <int TB>
 int launch(const AdjArgs& p, bool lds, size_t smem, int64_t grid, hipStream_t st, const float* pack, const float* context,
-           const float* x, const float* g, const float* jac, const float* dzdh, float* lam, float* ws, int64_t B) {
-  hipError_t e = lds ? gnf_launch_lds(strade_adjoint_k<TB, true>, dim3((unsigned)grid), dim3(kThreads), smem, st, p, pack,
-                                      context, x, g, jac, dzdh, lam, ws, B)
-                     : gnf_launch_lds(strade_adjoint_k<TB, false>, dim3((unsigned)grid), dim3(kThreads), smem, st, p, pack,
-                                      context, x, g, jac, dzdh, lam, ws, B);
+           const float* x, const float* g, const float* jac, const float* dzdh, float* lam, float* ws, int64_t B,
+           const uint8_t* pin, float* gdo) {
+  const dim3 gr((unsigned)grid), bl(kThreads);
+  hipError_t e;
+  if (pin)
+    e = lds ? gnf_launch_lds(strade_adjoint_k<TB, true, true>, gr, bl, smem, st, p, pack, context, x, g, jac, dzdh, lam, ws,
+                             B, pin, gdo)
+            : gnf_launch_lds(strade_adjoint_k<TB, false, true>, gr, bl, smem, st, p, pack, context, x, g, jac, dzdh, lam, ws,
+                             B, pin, gdo);
+  else
+    e = lds ? gnf_launch_lds(strade_adjoint_k<TB, true, false>, gr, bl, smem, st, p, pack, context, x, g, jac, dzdh, lam, ws,
+                             B, pin, gdo)
+            : gnf_launch_lds(strade_adjoint_k<TB, false, false>, gr, bl, smem, st, p, pack, context, x, g, jac, dzdh, lam, ws,
+                             B, pin, gdo);
   return e == hipSuccess ? 0 : (int)e;
 }
 
@@ -229,14 +272,19 @@ int64_t gnf_strade_adjoint_workspace_bytes(const gnf_strade_net* net, int cond_i
   return 4 * ws_floats(a, B);
 }
 
-int gnf_strade_adjoint(const gnf_strade_net* net, int cond_in, const float* context, const float* pack, const float* x,
-                       const float* g, const float* jac, const float* dzdh, float* lambda, int64_t B, int force_ws, void* ws,
-                       int64_t ws_bytes, gnf_stream_t stream) {
+}  // extern "C"
+
+namespace {
+
+int adjoint_run(const gnf_strade_net* net, int cond_in, const float* context, const float* pack, const float* x,
+                const float* g, const float* jac, const float* dzdh, float* lambda, const uint8_t* pin, float* gdo, int64_t B,
+                int force_ws, void* ws, int64_t ws_bytes, gnf_stream_t stream) {
   AdjLayout lay;
   const int rc = make_adj_layout(net, cond_in, &lay);
   if (rc) return rc;
   const gnf_made_net& m = net->made;
   if (B < 0) return GNF_EINVAL;
+  if (gdo && !pin) return GNF_EINVAL;                                // dL/dv of no intervention
   if (B == 0) return 0;
   if (!pack || !x || !g || !jac || !dzdh || !lambda || !m.var_of_step || !net->var_off || (cond_in > 0 && !context))
     return GNF_EINVAL;
@@ -268,10 +316,28 @@ int gnf_strade_adjoint(const gnf_strade_net* net, int cond_in, const float* cont
   hipStream_t st = (hipStream_t)stream;
   float* w = (float*)ws;
   switch (TB) {
-    case 4: return launch<4>(p, lds, smem, grid, st, pack, context, x, g, jac, dzdh, lambda, w, B);
-    case 8: return launch<8>(p, lds, smem, grid, st, pack, context, x, g, jac, dzdh, lambda, w, B);
-    default: return launch<16>(p, lds, smem, grid, st, pack, context, x, g, jac, dzdh, lambda, w, B);
+    case 4: return launch<4>(p, lds, smem, grid, st, pack, context, x, g, jac, dzdh, lambda, w, B, pin, gdo);
+    case 8: return launch<8>(p, lds, smem, grid, st, pack, context, x, g, jac, dzdh, lambda, w, B, pin, gdo);
+    default: return launch<16>(p, lds, smem, grid, st, pack, context, x, g, jac, dzdh, lambda, w, B, pin, gdo);
   }
+}
+
+}  // namespace
+
+extern "C" {
+
+int gnf_strade_adjoint(const gnf_strade_net* net, int cond_in, const float* context, const float* pack, const float* x,
+                       const float* g, const float* jac, const float* dzdh, float* lambda, int64_t B, int force_ws, void* ws,
+                       int64_t ws_bytes, gnf_stream_t stream) {
+  return adjoint_run(net, cond_in, context, pack, x, g, jac, dzdh, lambda, nullptr, nullptr, B, force_ws, ws, ws_bytes,
+                     stream);
+}
+
+// ... and with a pin table (do(x_P = v)): pin == NULL is the call above
+int gnf_strade_adjoint_do(const gnf_strade_net* net, int cond_in, const float* context, const float* pack, const float* x,
+                          const float* g, const float* jac, const float* dzdh, float* lambda, const uint8_t* pin, float* gdo,
+                          int64_t B, int force_ws, void* ws, int64_t ws_bytes, gnf_stream_t stream) {
+  return adjoint_run(net, cond_in, context, pack, x, g, jac, dzdh, lambda, pin, gdo, B, force_ws, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

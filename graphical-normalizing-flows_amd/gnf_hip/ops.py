@@ -436,11 +436,16 @@ def made_adjoint_pack(params, plan):
 
 
 @torch.no_grad()
-def made_adjoint(params, plan, pack, x, g, jac, dzdh, context=None, force_ws=False):
+def made_adjoint(params, plan, pack, x, g, jac, dzdh, context=None, force_ws=False, pin=None, gdo=False):
     """lambda [B, d] with J^T lambda = g for the MADE step whose sample is x (gnf_made_adjoint, one launch): x, g, jac
     [B, d] and dzdh [B, d, out] fp32 contiguous, jac the normalizer's own derivative dz_i/dx_i, dzdh[b, i, :] = dz_bi/dh_bi;
     context: the contiguous [B, cond_in] tensor of a conditional plan.  force_ws (tests): keep the tile's rows in the
-    workspace even when they fit in LDS -- the same bits."""
+    workspace even when they fit in LDS -- the same bits.
+
+    pin: the contiguous uint8 [d] device table of an intervention, one byte per VARIABLE, non-zero = pinned
+    (gnf_made_adjoint_do): lambda is +0 at a pinned column and jac / dzdh are not read there.  gdo=True (with a table) returns
+    (lambda, gdo): gdo = g - u = dL/dv at pinned columns, +0 at free ones.  Without a table the call is the un-pinned entry
+    point, the same launch and bits."""
     params = [p.detach() for p in params]
     net, c = _made_net(params, plan), _plan_cond_in(plan)
     B, d = x.shape
@@ -452,22 +457,32 @@ def made_adjoint(params, plan, pack, x, g, jac, dzdh, context=None, force_ws=Fal
     if (context is not None) != (c > 0) or (c > 0 and not ok(context, (B, c))):
         raise abi.GnfError("made_adjoint: context must be a contiguous fp32 [B, %d] tensor on the device of x (None for "
                            "cond_in = 0)" % c)
+    if pin is not None and (pin.dtype != torch.uint8 or pin.device != x.device or tuple(pin.shape) != (plan["d"],)
+                            or not pin.is_contiguous()):
+        raise abi.GnfError("made_adjoint: pin must be a contiguous uint8 [%d] tensor on the device of x" % plan["d"])
+    if gdo and pin is None:
+        raise abi.GnfError("made_adjoint: gdo is the gradient of the pinned values: it needs a pin table")
     lam = torch.empty_like(x)
-    args = lambda w: (ctypes.byref(net), c, ptr(context), ptr(pack), ptr(x), ptr(g), ptr(jac), ptr(dzdh), ptr(lam), B,
+    gd = torch.empty_like(x) if gdo else None
+    # the un-pinned entry point when there is no table: its call sites and counters stay as they are
+    entry = "gnf_made_adjoint" if pin is None else "gnf_made_adjoint_do"
+    do = () if pin is None else (ctypes.c_void_p(pin.data_ptr()), ptr(gd))
+    args = lambda w: (ctypes.byref(net), c, ptr(context), ptr(pack), ptr(x), ptr(g), ptr(jac), ptr(dzdh), ptr(lam), *do, B,
                       int(bool(force_ws)), None if w is None else ctypes.c_void_p(w.data_ptr()),
                       0 if w is None else w.numel() * 4, stream())
+    done = lambda: (lam, gd) if gdo else lam
     if not force_ws:
         # a tile whose rows fit in LDS needs no workspace; the library says when it does not
-        rc = abi.load().gnf_made_adjoint(*args(None))
+        rc = getattr(abi.load(), entry)(*args(None))
         if rc == 0:
-            return lam
+            return done()
         if rc != -3:
-            abi.check(rc, "gnf_made_adjoint")
+            abi.check(rc, entry)
     nbytes = abi.load().gnf_made_adjoint_ws_bytes(ctypes.byref(net), c, B)
     if nbytes < 0:
         abi.check(int(nbytes), "gnf_made_adjoint_ws_bytes")
-    call("gnf_made_adjoint", *args(_ws(nbytes, x)))
-    return lam
+    call(entry, *args(_ws(nbytes, x)))
+    return done()
 
 
 # ----------------------------------------------------------------------------- StrADE adjoint sweep, rsample
@@ -487,11 +502,16 @@ def strade_adjoint_pack(params, masks, plan):
 
 
 @torch.no_grad()
-def strade_adjoint(params, masks, plan, pack, x, g, jac, dzdh, context=None, force_ws=False):
+def strade_adjoint(params, masks, plan, pack, x, g, jac, dzdh, context=None, force_ws=False, pin=None, gdo=False):
     """lambda [B, d] with J^T lambda = g for the StrADE step whose sample is x (gnf_strade_adjoint, one launch): x, g, jac
     [B, d] and dzdh [B, d, out] fp32 contiguous, jac the normalizer's own derivative dz_i/dx_i, dzdh[b, i, :] = dz_bi/dh_bi
     by variable index; context: the contiguous [B, cond_in] tensor of a conditional plan.  force_ws (tests): keep the
-    tile's rows in the workspace even when they fit in LDS -- the same bits.  An empty batch launches nothing."""
+    tile's rows in the workspace even when they fit in LDS -- the same bits.  An empty batch launches nothing.
+
+    pin: the contiguous uint8 [d] device table of an intervention, one byte per VARIABLE, non-zero = pinned
+    (gnf_strade_adjoint_do): lambda is +0 at a pinned column and jac / dzdh are not read there.  gdo=True (with a table) returns
+    (lambda, gdo): gdo = g - u = dL/dv at pinned columns, +0 at free ones.  Without a table the call is the un-pinned entry
+    point, the same launch and bits."""
     params = [p.detach() for p in params]
     net, c = _strade_net(params, masks, plan), _plan_cond_in(plan)
     B, d = x.shape
@@ -503,22 +523,32 @@ def strade_adjoint(params, masks, plan, pack, x, g, jac, dzdh, context=None, for
     if (context is not None) != (c > 0) or (c > 0 and not ok(context, (B, c))):
         raise abi.GnfError("strade_adjoint: context must be a contiguous fp32 [B, %d] tensor on the device of x (None for "
                            "cond_in = 0)" % c)
+    if pin is not None and (pin.dtype != torch.uint8 or pin.device != x.device or tuple(pin.shape) != (plan["d"],)
+                            or not pin.is_contiguous()):
+        raise abi.GnfError("strade_adjoint: pin must be a contiguous uint8 [%d] tensor on the device of x" % plan["d"])
+    if gdo and pin is None:
+        raise abi.GnfError("strade_adjoint: gdo is the gradient of the pinned values: it needs a pin table")
     lam = torch.empty_like(x)
-    args = lambda w: (ctypes.byref(net), c, ptr(context), ptr(pack), ptr(x), ptr(g), ptr(jac), ptr(dzdh), ptr(lam), B,
+    gd = torch.empty_like(x) if gdo else None
+    # the un-pinned entry point when there is no table: its call sites and counters stay as they are
+    entry = "gnf_strade_adjoint" if pin is None else "gnf_strade_adjoint_do"
+    do = () if pin is None else (ctypes.c_void_p(pin.data_ptr()), ptr(gd))
+    args = lambda w: (ctypes.byref(net), c, ptr(context), ptr(pack), ptr(x), ptr(g), ptr(jac), ptr(dzdh), ptr(lam), *do, B,
                       int(bool(force_ws)), None if w is None else ctypes.c_void_p(w.data_ptr()),
                       0 if w is None else w.numel() * 4, stream())
+    done = lambda: (lam, gd) if gdo else lam
     if not force_ws:
         # a tile whose rows fit in LDS needs no workspace; the library says when it does not
-        rc = abi.load().gnf_strade_adjoint(*args(None))
+        rc = getattr(abi.load(), entry)(*args(None))
         if rc == 0:
-            return lam
+            return done()
         if rc != -3:
-            abi.check(rc, "gnf_strade_adjoint")
+            abi.check(rc, entry)
     nbytes = abi.load().gnf_strade_adjoint_workspace_bytes(ctypes.byref(net), c, B)
     if nbytes < 0:
         abi.check(int(nbytes), "gnf_strade_adjoint_workspace_bytes")
-    call("gnf_strade_adjoint", *args(_ws(nbytes, x)))
-    return lam
+    call(entry, *args(_ws(nbytes, x)))
+    return done()
 
 
 class InvertFn(torch.autograd.Function):
@@ -543,6 +573,32 @@ class InvertFn(torch.autograd.Function):
         context = rest.pop(0) if ctx.has_context else None
         lam, gctx, gparams = ctx.step._rsample_backward(x, context, rest, g.contiguous(), ctx.needs_input_grad[2])
         return (None, lam, gctx, *gparams)
+
+
+class InterveneFn(torch.autograd.Function):
+    """x = step.intervene(z, idx, vals, context) -- the same kernels, the same bits -- with the gradient of the implicit
+    function theorem on the mutilated system (NormalizingFlowStep.rsample_do; the sibling of InvertFn).  The equations of
+    the free variables are kept, those of the pinned ones are x_P = vals.  Backward, for g = dL/dx: lambda_P = 0,
+    J_FF^T lambda_F = g_F; dL/dz = lambda (exact zeros at the pinned columns), dL/dvals = g_P - (N^T lambda)_P, and
+    dL/dtheta, dL/dcontext are ONE vjp of the step's forward at x with cotangent -lambda.  `idx`: the pinned variables, a
+    tuple of ints; `vals` [B, S]: their values (autograd's expand reduces the gradient to the caller's do_value)."""
+
+    @staticmethod
+    def forward(ctx, step, z, idx, vals, context, *params):
+        x = step.intervene(z, list(idx), vals.detach(), context)
+        ctx.step, ctx.idx = step, tuple(idx)
+        ctx.has_context = context is not None
+        ctx.save_for_backward(x, *(() if context is None else (context,)), *params)
+        return x
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, *rest = ctx.saved_tensors                    # (raises when a parameter was modified in place since the sample)
+        context = rest.pop(0) if ctx.has_context else None
+        lam, gvals, gctx, gparams = ctx.step._rsample_do_backward(x, context, rest, g.contiguous(), ctx.idx,
+                                                                  ctx.needs_input_grad[4], ctx.needs_input_grad[3])
+        return (None, lam, None, gvals, gctx, *gparams)
 
 
 # ----------------------------------------------------------------------------- row reductions

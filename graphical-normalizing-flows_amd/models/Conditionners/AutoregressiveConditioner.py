@@ -308,10 +308,12 @@ class AutoregressiveConditioner(Conditioner):
                 self._held_adjoint = prev
         return hold()
 
-    def adjoint_solve(self, x, g, jac, dzdh, context=None):
+    def adjoint_solve(self, x, g, jac, dzdh, context=None, pin=None, want_gdo=False):
         """lambda [B, d] with J^T lambda = g for the step whose sample is x, on the HIP adjoint kernel (gnf_hip.ops.made_adjoint,
         one launch): jac [B, d] the normalizer's dz_i/dx_i, dzdh [B, d, out] its dz_i/dh_i; `context`: the checked
-        [B, cond_in] context of a conditional conditioner"""
+        [B, cond_in] context of a conditional conditioner.  pin (uint8 [d] on the device, by variable): the solve under
+        do(x_pin = v) -- lambda is 0 at a pinned column; want_gdo: (lambda, gdo) with gdo = dL/dv at the pinned columns"""
         plan, params = self.prefix_plan(with_context=bool(self.cond_in)), self._prefix_params()
         pack = self._held_adjoint if self._held_adjoint is not None else ops.made_adjoint_pack(params, plan)
-        return ops.made_adjoint(params, plan, pack, x, g, jac, dzdh, context=context)
+        do = {} if pin is None and not want_gdo else {"pin": pin, "gdo": want_gdo}
+        return ops.made_adjoint(params, plan, pack, x, g, jac, dzdh, context=context, **do)

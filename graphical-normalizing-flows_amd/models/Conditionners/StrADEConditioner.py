@@ -285,13 +285,16 @@ class StrADEConditioner(Conditioner):
                 self._held_adjoint = prev
         return hold()
 
-    def adjoint_solve(self, x, g, jac, dzdh, context=None):
+    def adjoint_solve(self, x, g, jac, dzdh, context=None, pin=None, want_gdo=False):
         """lambda [B, d] with J^T lambda = g for the step whose sample is x, on the HIP adjoint level kernel
         (gnf_hip.ops.strade_adjoint, one launch): jac [B, d] the normalizer's dz_i/dx_i, dzdh [B, d, out] its dz_i/dh_i;
-        `context`: the checked [B, cond_in] context.  None when level_plan() is None (a hand-edited mask): the passes serve"""
+        `context`: the checked [B, cond_in] context.  None when level_plan() is None (a hand-edited mask): the passes serve.
+        pin (uint8 [d] on the device, by variable): the solve under do(x_pin = v) -- lambda is 0 at a pinned column;
+        want_gdo: (lambda, gdo) with gdo = dL/dv at the pinned columns"""
         plan = self.level_plan()
         if plan is None:
             return None
         params, masks = self._params(), self._masks()
         pack = self._held_adjoint if self._held_adjoint is not None else ops.strade_adjoint_pack(params, masks, plan)
-        return ops.strade_adjoint(params, masks, plan, pack, x, g, jac, dzdh, context=context)
+        do = {} if pin is None and not want_gdo else {"pin": pin, "gdo": want_gdo}
+        return ops.strade_adjoint(params, masks, plan, pack, x, g, jac, dzdh, context=context, **do)

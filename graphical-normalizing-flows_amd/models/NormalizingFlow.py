@@ -203,6 +203,15 @@ class NormalizingFlow(nn.Module):
         """what the observation x would have been under do(x[:, do_index] = do_value): abduct z = forward(x), intervene"""
         raise NotImplementedError
 
+    def rsample_do(self, z, do_index, do_value, context=None):
+        """intervene(...) as a differentiable function of z, do_value (a tensor that requires grad), the context and the
+        parameters"""
+        raise NotImplementedError
+
+    def rcounterfactual(self, x, do_index, do_value, context=None):
+        """counterfactual(...) as a differentiable function of x, do_value, the context and the parameters"""
+        raise NotImplementedError
+
     def getConditioners(self):
         raise NotImplementedError
 
@@ -736,6 +745,94 @@ class NormalizingFlowStep(NormalizingFlow):
         gctx = grads.pop() if want_context else None
         return lam, gctx, grads
 
+    # -- differentiable interventional sampling -----------------------------------------------------------------
+    def rsample_do(self, z, do_index, do_value, context=None):
+        """x = intervene(z, do_index, do_value, context) -- the same arm (recorded in `_intervene_arm`), the same bits --
+        with gradients for z, do_value, the context and the step's parameters (rsample under an intervention).
+        The equations of the free variables F are kept, those of the pinned variables P read x_P = v.  With J = D + N at the
+        sample and g = dL/dx:  lambda_P = 0,  J_FF^T lambda_F = g_F,  dL/dz = lambda (exact zeros at the pinned columns),
+        dL/dv = g_P - (N^T lambda)_P,  dL/dtheta and dL/dc one vjp of the forward with cotangent -lambda.  Pinned
+        quantities are selected, never multiplied away: the normalizer is not evaluated at a pinned element.
+
+        do_value: a float (no gradient), or a tensor -- 0-dim, [S] or [B, S]; when it requires grad, its gradient comes
+        back in its own shape.  An empty do_index is rsample(z, context): the same bits, forward and backward.  The
+        backward's arm is recorded in `_rsample_arm` as rsample records it.  A stochastic DAG gate is refused."""
+        self._refuse_stochastic_gate("rsample_do", "the backward would recompute the conditioner under another draw of the "
+                                     "gate than the sample saw")
+        idx, vals = do_arguments(do_index, do_value.detach() if torch.is_tensor(do_value) else do_value, z)
+        if torch.is_tensor(do_value) and do_value.requires_grad:
+            # the value path, not detached: autograd's expand reduces the gradient to do_value's own shape
+            vals = do_value.to(device=z.device, dtype=z.dtype).expand(z.shape[0], len(idx))
+        return ops.InterveneFn.apply(self, z, idx, vals, context, *[p for p in self.parameters() if p.requires_grad])
+
+    def rcounterfactual(self, x, do_index, do_value, context=None):
+        """counterfactual(x, do_index, do_value, context), bit for bit, differentiable: the abduction z = forward(x, context)
+        WITH grad, then rsample_do.  Gradients reach x and, through the abduction too, the parameters and the context."""
+        self._refuse_stochastic_gate("rsample_do", "the backward would recompute the conditioner under another draw of the "
+                                     "gate than the sample saw")
+        do_arguments(do_index, do_value, x)             # (the argument errors before the abduction's launches)
+        z, _ = self.forward(x, context)
+        return self.rsample_do(z, do_index, do_value, context)
+
+    def _rsample_do_backward(self, x, context, params, g, idx, want_context, want_value):
+        """(lambda, dL/dvals [B, S] or None, dL/dcontext, [dL/dp for p in params]) of ops.InterveneFn for the sample x under
+        do(x[:, idx] = vals) and the cotangent g = dL/dx"""
+        cols = list(idx)
+        if not cols:
+            lam, gctx, grads = self._rsample_backward(x, context, params, g, want_context)
+            return lam, (g[:, :0] if want_value else None), gctx, grads
+        self._rsample_arm = None
+        B, d = x.shape
+        if B == 0:
+            return torch.zeros_like(x), (g[:, cols] if want_value else None), None, [None] * len(params)
+        if len(cols) == d:
+            # no free equation: nothing depends on z, the context or a parameter, and x = vals
+            self._rsample_arm = ("passes", 0)
+            return torch.zeros_like(x), (g[:, cols] if want_value else None), None, [None] * len(params)
+        want_context = bool(want_context and context is not None)
+        pin = torch.zeros(d, dtype=torch.uint8, device=x.device)
+        pin[cols] = 1
+        pinned = pin.bool()
+        with torch.enable_grad():
+            xa, xb = x.detach().requires_grad_(True), x.detach()
+            ctx = context.detach().requires_grad_(True) if want_context else context
+            h = self.conditioner(xa, ctx)
+            # the normalizer never sees a pinned element: benign detached stand-ins there, chosen by selection, so that the
+            # pinned columns of h receive an exactly zero cotangent whatever the normalizer's derivatives would be at vals
+            hs = torch.where(pinned.view(1, d, 1), torch.zeros_like(h), h)
+            zz, jac = self.normalizer(torch.where(pinned, torch.zeros_like(xb), xb), hs, ctx)
+        jac = jac.detach()
+        zero = torch.zeros_like(g)
+        plan = self._adjoint_plan(x, context)
+        gdo = None
+        if plan is not None:
+            dzdh, = torch.autograd.grad(zz, hs, torch.ones_like(zz), retain_graph=True)
+            kw = {} if context is None else {"context": context.detach().contiguous()}
+            res = self.conditioner.adjoint_solve(x.contiguous(), g, jac.contiguous(), dzdh.contiguous(), pin=pin,
+                                                 want_gdo=bool(want_value), **kw)
+            lam, gdo = res if want_value else (res, None)
+            self._rsample_arm = ("adjoint", 0)
+        else:
+            # lambda <- where(pinned, 0, (g - N^T lambda) / jac): exact by nilpotency, as in _rsample_backward
+            lam, n, nl, confirmed = torch.where(pinned, zero, g / jac), 0, None, False
+            for _ in range(self.conditioner.depth()):
+                nl, = torch.autograd.grad(zz, xa, lam, retain_graph=True, allow_unused=True)
+                n += 1
+                new = torch.where(pinned, zero, (g if nl is None else g - nl) / jac)
+                confirmed = torch.equal(new, lam)       # then nl is N^T lambda of the lambda returned
+                lam = new
+                if confirmed:
+                    break
+            if want_value:
+                if not confirmed:
+                    nl, = torch.autograd.grad(zz, xa, lam, retain_graph=True, allow_unused=True)
+                gdo = g if nl is None else g - nl
+            self._rsample_arm = ("passes", n)
+        wrt = list(params) + ([ctx] if want_context else [])
+        grads = list(torch.autograd.grad(zz, wrt, -lam, allow_unused=True)) if wrt else []
+        gctx = grads.pop() if want_context else None
+        return lam, (gdo[:, cols] if want_value else None), gctx, grads
+
 
 class FCNormalizingFlow(NormalizingFlow):
     """Steps applied in sequence on flat [B, d] data."""
@@ -833,6 +930,14 @@ class FCNormalizingFlow(NormalizingFlow):
         """the single step's counterfactual; ValueError for a flow of several steps"""
         return self._single_step("counterfactual").counterfactual(x, do_index, do_value, context)
 
+    def rsample_do(self, z, do_index, do_value, context=None):
+        """the single step's rsample_do (intervene, differentiable); ValueError for a flow of several steps"""
+        return self._single_step("rsample_do").rsample_do(z, do_index, do_value, context)
+
+    def rcounterfactual(self, x, do_index, do_value, context=None):
+        """the single step's rcounterfactual (counterfactual, differentiable); ValueError for a flow of several steps"""
+        return self._single_step("rcounterfactual").rcounterfactual(x, do_index, do_value, context)
+
 
 class CNNormalizingFlow(FCNormalizingFlow):
     """Multi-scale image flow (reference :172-226): after every scale the image is cut into d_c x d_h x d_w blocks;
@@ -902,6 +1007,14 @@ class CNNormalizingFlow(FCNormalizingFlow):
 
     def counterfactual(self, x, do_index, do_value, context=None):
         raise ValueError(_SINGLE_STEP % ("CNNormalizingFlow.counterfactual", len(self.steps)) + "; a multi-scale flow has "
+                         "none of one step's equations even with a single scale: its latent is cut and re-interleaved")
+
+    def rsample_do(self, z, do_index, do_value, context=None):
+        raise ValueError(_SINGLE_STEP % ("CNNormalizingFlow.rsample_do", len(self.steps)) + "; a multi-scale flow has none "
+                         "of one step's equations even with a single scale: its latent is cut and re-interleaved")
+
+    def rcounterfactual(self, x, do_index, do_value, context=None):
+        raise ValueError(_SINGLE_STEP % ("CNNormalizingFlow.rcounterfactual", len(self.steps)) + "; a multi-scale flow has "
                          "none of one step's equations even with a single scale: its latent is cut and re-interleaved")
 
     def _do_step(self, what):

@@ -573,6 +573,24 @@ int64_t gnf_made_adjoint_ws_bytes(const gnf_made_net* net, int cond_in, int64_t 
 int gnf_made_adjoint(const gnf_made_net* net, int cond_in, const float* context, const float* pack, const float* x,
                      const float* g, const float* jac, const float* dzdh, float* lambda, int64_t B, int force_ws, void* ws,
                      int64_t ws_bytes, gnf_stream_t stream);
+/* ... under an intervention do(x_P = v) (NormalizingFlowStep.rsample_do's backward).  The equations of the free set F are
+ * kept, those of the pinned set P become x_P = v, so lambda_P = 0, lambda_F solves J_FF^T lambda_F = g_F, and
+ * dL/dv = g_P - (N^T lambda)_P.  In the sweep, at a pinned step t: u_t as above, lambda_t := 0, gdo_t := g_t - u_t, and the
+ * cotangent row of the variable's outputs is exact zeros -- all by SELECTION: jac[b, v] and dzdh[b, v, :] of a pinned v are
+ * never read and may hold 0, inf or NaN.
+ *   pin: [d] bytes on the device, one per VARIABLE (not per step), non-zero = pinned; any address, read byte by byte (the
+ *     table of gnf_made_prefix_do).  NULL: the call above, the same kernel, the same bits; then gdo must be NULL too
+ *     (GNF_EINVAL otherwise).  An all-zero table gives those bits as well.
+ *   gdo: [B, d] contiguous, dword-aligned, or NULL.  lambda is written everywhere: lambda at free columns, +0 at pinned
+ *     ones; gdo, when given, likewise: g - u at pinned columns, +0 at free ones.
+ *   Skipped, because the table makes it dead: with t_last the last free step (derived from the table inside the kernel),
+ *   the steps t > t_last have u = 0 exactly and run no contraction (lambda = 0, gdo = g), and the replay stops at the hidden
+ *   units of degree t_last - 1; every variable pinned runs no layer step at all; with gdo == NULL a pinned step skips the
+ *   first-layer contraction behind its u.  ws: gnf_made_adjoint_ws_bytes, as above.  Everything else as above. */
+int gnf_made_adjoint_do(const gnf_made_net* net, int cond_in, const float* context, const float* pack, const float* x,
+                        const float* g, const float* jac, const float* dzdh, float* lambda,
+                        const uint8_t* pin /* [d], by VARIABLE, device, or NULL */, float* gdo /* [B, d] or NULL */,
+                        int64_t B, int force_ws, void* ws, int64_t ws_bytes, gnf_stream_t stream);
 
 /* ---- StrADE adjoint sweep: lambda with J^T lambda = g for one StrADE step (rsample's backward, adjoint_levels) -----------
  * gnf_made_adjoint with "degree" replaced by "topological level", on the tables of gnf_strade_levels.  In level order
@@ -608,6 +626,17 @@ int64_t gnf_strade_adjoint_workspace_bytes(const gnf_strade_net* net, int cond_i
 int gnf_strade_adjoint(const gnf_strade_net* net, int cond_in, const float* context, const float* pack, const float* x,
                        const float* g, const float* jac, const float* dzdh, float* lambda, int64_t B, int force_ws, void* ws,
                        int64_t ws_bytes, gnf_stream_t stream);
+/* ... under an intervention do(x_P = v): gnf_made_adjoint_do with levels for degrees.  pin ([d] bytes by VARIABLE, device,
+ * any address; NULL = the call above, then gdo must be NULL: GNF_EINVAL otherwise) and gdo ([B, d] or NULL) as there:
+ * lambda is +0 at pinned columns, gdo is g - u at pinned columns and +0 at free ones, jac and dzdh of a pinned element are
+ * never read.  A pinned variable keeps its level.  Skipped: the levels above the last level that holds a free variable
+ * (u = 0 exactly: no contraction, and the replay stops below that level; no layer step at all when every variable is
+ * pinned), and, with gdo == NULL, the first-layer contraction of a chunk whose variables are all pinned.
+ * ws: gnf_strade_adjoint_workspace_bytes, as above. */
+int gnf_strade_adjoint_do(const gnf_strade_net* net, int cond_in, const float* context, const float* pack, const float* x,
+                          const float* g, const float* jac, const float* dzdh, float* lambda,
+                          const uint8_t* pin /* [d], by VARIABLE, device, or NULL */, float* gdo /* [B, d] or NULL */,
+                          int64_t B, int force_ws, void* ws, int64_t ws_bytes, gnf_stream_t stream);
 
 /* ---- MNISTCNN convolutional front: models/MLP.py:36-41 as the DAG embedding net --------
  * (ImageExperiments / NormalizingFlowFactories.py:83-86: size_img = [1,28,28]).
